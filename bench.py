@@ -17,7 +17,10 @@ column form and `forms` carries step time and per-phase times of BOTH in the one
 bench lines for profiles/; the driver's line is the default config 2).  `--protocol core` = SURVEY section 8d's P-core (no
 error block inside the timed iterations).
 
-Prints ONE JSON line on rank 0 (see the task contract) with
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run times `--steps` steps once after `--warmup` steps and reports the
+headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `final_mse`, `config`, `step`); `--dump-outputs DIR`
+then writes what the timed path returned after its last step -- W, H and the error traces of nnlm_run() -- as DIR/<name>.npy (fp64).
+`--full` adds, in the same line, what takes runs of its own (`--repeats` timed regions, default 3, `value` the first):
   roofline            the kernel with the largest share of the step (HIP-event timed inside this process; the two half-steps' plain cross
                       products are launches of one kernel and count as one class): at config 2 the A-streaming cross product, HBM bound,
   roofline_secondary  the next class by time (config 2: the persistent SCD sweep, bound by dependent latency),
@@ -30,7 +33,9 @@ Prints ONE JSON line on rank 0 (see the task contract) with
                       factors the GPU had after its warm-up), plus one full iteration on ONE thread (n.threads = 1 is R's default),
   call                (N = 1, default config) SURVEY 8d's call-level metric: n.iteration / wall time of ONE nnlm_c_nnmf() -- the .Call
                       entry: handle, code object, allocations, upload of A, 200 iterations, download -- from a cold process, both modes,
-  mse_check           GPU and CPU mse after the same number of iterations from the same state.
+  mse_check           GPU and CPU mse after the same number of iterations from the same state,
+  forms               (N > 1, `--form both`) the all-reduce form timed beside the column form,
+  phases_ms, kernels  per-phase HIP-event times of a profiled replay of the same steps.
 """
 import argparse
 import json
@@ -85,6 +90,25 @@ def run_steps(h, cfg, steps, trace):
     r = h.run(cfg["reg"], cfg["reg"], steps, -1.0, 0, False, cfg["inner"], INNER_TOL, cfg["method"], trace if trace > 0 else 999999)
     assert r["n_iteration"] == steps
     return r
+
+
+DUMP_LIMIT = 60_000_000  # bytes of array data in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """Write every array as fp64 `path`/<name>.npy.  Should the arrays exceed DUMP_LIMIT bytes (large --size), each one over 1 MB is
+    replaced by the same fixed share of its entries: flat indices sorted(default_rng(0).choice(size, count, replace=False)), identical
+    from run to run."""
+    os.makedirs(path, exist_ok=True)
+    big = {name for name, a in arrays.items() if 8 * np.size(a) > 1 << 20}
+    room = DUMP_LIMIT - 8 * sum(np.size(a) for name, a in arrays.items() if name not in big)
+    total = 8 * sum(np.size(arrays[name]) for name in big)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if name in big and total > room:
+            count = a.size * room // total
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, count, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def pmc_traffic(kernel, config=2, f64=False):
@@ -430,15 +454,20 @@ def main():
     ap.add_argument("--trace", type=int, default=None, help="error block every TRACE steps (R default: 2 for MSE, 100 for MKL); 0 = never")
     ap.add_argument("--protocol", default="default", choices=["default", "core"], help="core: no error block inside the timed iterations (SURVEY 8d)")
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--cpu-iters", type=int, default=2, help="outer iterations of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions (the first one is `value`; all are listed)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: repeated timed regions, profiled replay "
+                                                         "(roofline, phases, kernels), CPU baseline, other configs, both multi-GPU forms, call-level metric")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write W, H and the error traces of the last timed step to DIR/<name>.npy (fp64)")
+    ap.add_argument("--cpu-iters", type=int, default=2, help="(--full) outer iterations of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--repeats", type=int, default=None, help="(--full) timed regions, default 3 (the first one is `value`; all are listed); "
+                                                              "a plain run times one")
     ap.add_argument("--size", default=None, help="n,m,k override for quick experiments (reported in config)")
-    ap.add_argument("--others", type=int, default=1, help="1: after the headline (N = 1, default config) also time strict-fp64 config 2 and fp32 configs 3 and 5 "
-                                                          "for a few iterations each -> other_configs; 0: skip")
+    ap.add_argument("--others", type=int, default=1, help="(--full) 1: after the headline (N = 1, default config) also time strict-fp64 config 2 and fp32 "
+                                                          "configs 3 and 5 for a few iterations each -> other_configs; 0: skip")
     ap.add_argument("--form", default=os.environ.get("NNLM_SHARD_DENSE", "both"), choices=["cols", "reduce", "both"],
                     help="N > 1, dense square loss: cols = column-sharded half-steps + one all-gather each (`value` of `both`), reduce = contraction-sharded "
-                         "+ one all-reduce of [G | C] + all-gather, both = time the two forms in one invocation -> forms")
-    ap.add_argument("--call", type=int, default=1, help="1: (N = 1, default config) also time one cold nnlm_c_nnmf() call per mode in a child process -> call")
+                         "+ one all-reduce of [G | C] + all-gather, both = (--full) time the two forms in one invocation -> forms")
+    ap.add_argument("--call", type=int, default=1, help="(--full) 1: (N = 1, default config) also time one cold nnlm_c_nnmf() call per mode in a child "
+                                                        "process -> call")
     ap.add_argument("--call-iters", type=int, default=200, help="max.iter of the call-level metric (SURVEY 8d: 200)")
     ap.add_argument("--call-probe", default=None, choices=["f32", "f64"], help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -512,7 +541,8 @@ def main():
         h.errors()
     run_steps(h, cfg, args.warmup, trace)
     times, mses = [], []
-    for _ in range(max(args.repeats, 1)):
+    repeats = (3 if args.repeats is None else max(args.repeats, 1)) if args.full else 1
+    for _ in range(repeats):
         barrier()
         t0 = time.perf_counter()
         r = run_steps(h, cfg, args.steps, trace)
@@ -520,68 +550,72 @@ def main():
         times.append(max_over_ranks(time.perf_counter() - t0))
         mses.append(float(r["mse_error"][-1]))
     elapsed, final_mse = times[0], mses[0]
+    if args.dump_outputs and rank == 0:  # what a caller of nnlm_run() receives after the last timed step (read back outside the timed region)
+        W, H = h.get_factors()
+        dump_outputs(args.dump_outputs, dict(W=W, H=H, **{nm: r[nm] for nm in ("mse_error", "mkl_error", "target_error", "average_epoch")}))
 
-    # replay the same K steps with per-kernel HIP events (on the library's own stream) for the roofline block
-    h.profile_reset()
-    h.profile_enable(True)
-    barrier()
-    t0 = time.perf_counter()
-    run_steps(h, cfg, args.steps, trace)
-    barrier()
-    prof_elapsed = time.perf_counter() - t0
-    kern = profile_scopes(h)
-    h.profile_enable(False)
-    # per-phase time of a step, MAX over ranks (one SCALE line then shows where the step goes: what shards, what every rank repeats,
-    # what the collectives cost)
-    phase_tot = [kern[nm]["total_ms"] for nm in SCOPES]
-    if dist is not None:
-        import torch
-        tt = torch.tensor(phase_tot, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        phase_tot = [float(v) for v in tt]
-    phases_ms = {nm: v / args.steps for nm, v in zip(SCOPES, phase_tot) if v > 0}
-    main_forms = sweep_forms_of(h)
-
-    # --form both (N > 1, dense square loss): the same steps once more in the all-reduce form north_star words -- one timed region and
-    # one profiled replay -- so that ONE line prices the [G | C] all-reduce against the all-gather-only default
-    forms = None
-    if dist is not None and args.form == "both" and cfg["method"] < 3 and not cfg["na"] and k <= 64:
-        forms = {"cols": dict(ms_per_step=1e3 * times[0] / args.steps, phases_ms=dict(phases_ms))}
-        h.comm_set_form("reduce")
-        run_steps(h, cfg, args.warmup, trace)
-        barrier()
-        t0 = time.perf_counter()
-        rr = run_steps(h, cfg, args.steps, trace)
-        barrier()
-        t_red = max_over_ranks(time.perf_counter() - t0)
+    if args.full:
+        # replay the same K steps with per-kernel HIP events (on the library's own stream) for the roofline block
         h.profile_reset()
         h.profile_enable(True)
         barrier()
+        t0 = time.perf_counter()
         run_steps(h, cfg, args.steps, trace)
         barrier()
-        kern_r = profile_scopes(h)
+        prof_elapsed = time.perf_counter() - t0
+        kern = profile_scopes(h)
         h.profile_enable(False)
-        tot_r = [kern_r[nm]["total_ms"] for nm in SCOPES]
-        import torch
-        tt = torch.tensor(tot_r, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        forms["reduce"] = dict(ms_per_step=1e3 * t_red / args.steps, final_mse=float(rr["mse_error"][-1]),
-                               phases_ms={nm: float(v) / args.steps for nm, v in zip(SCOPES, tt) if float(v) > 0})
-        forms["note"] = ("cols (`value`): a rank forms the cross product of ITS columns over the whole contraction, sweeps them, ONE all-gather per "
-                         "half-step; reduce (north_star's wording): contraction-sharded [Gram | cross product], ONE all-reduce, column-sharded "
-                         "sweep, ONE all-gather; same steps, the reduce region follows the cols regions from the factors they left")
-        h.comm_set_form("cols")
+        # per-phase time of a step, MAX over ranks (one SCALE line then shows where the step goes: what shards, what every rank repeats,
+        # what the collectives cost)
+        phase_tot = [kern[nm]["total_ms"] for nm in SCOPES]
+        if dist is not None:
+            import torch
+            tt = torch.tensor(phase_tot, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            phase_tot = [float(v) for v in tt]
+        phases_ms = {nm: v / args.steps for nm, v in zip(SCOPES, phase_tot) if v > 0}
+        main_forms = sweep_forms_of(h)
 
-    # GPU mse after `cpu_iters` iterations from the warmed state (what the CPU sample reproduces)
-    gpu_check = None
-    Ww = Hw = None
-    if args.cpu_iters > 0 and world == 1 and not force_comm:
-        # the state the timed region started from, reproduced (the loop is deterministic): the CPU sample starts there too.
-        # (Taken here, not between warm-up and timing: a host round trip there lets the clocks drop before the timed region.)
-        h.set_factors(k, W0, H0)
-        run_steps(h, cfg, args.warmup, trace)
-        Ww, Hw = h.get_factors()
-        gpu_check = run_steps(h, cfg, args.cpu_iters, trace)
+        # --form both (N > 1, dense square loss): the same steps once more in the all-reduce form north_star words -- one timed region and
+        # one profiled replay -- so that ONE line prices the [G | C] all-reduce against the all-gather-only default
+        forms = None
+        if dist is not None and args.form == "both" and cfg["method"] < 3 and not cfg["na"] and k <= 64:
+            forms = {"cols": dict(ms_per_step=1e3 * times[0] / args.steps, phases_ms=dict(phases_ms))}
+            h.comm_set_form("reduce")
+            run_steps(h, cfg, args.warmup, trace)
+            barrier()
+            t0 = time.perf_counter()
+            rr = run_steps(h, cfg, args.steps, trace)
+            barrier()
+            t_red = max_over_ranks(time.perf_counter() - t0)
+            h.profile_reset()
+            h.profile_enable(True)
+            barrier()
+            run_steps(h, cfg, args.steps, trace)
+            barrier()
+            kern_r = profile_scopes(h)
+            h.profile_enable(False)
+            tot_r = [kern_r[nm]["total_ms"] for nm in SCOPES]
+            import torch
+            tt = torch.tensor(tot_r, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            forms["reduce"] = dict(ms_per_step=1e3 * t_red / args.steps, final_mse=float(rr["mse_error"][-1]),
+                                   phases_ms={nm: float(v) / args.steps for nm, v in zip(SCOPES, tt) if float(v) > 0})
+            forms["note"] = ("cols (`value`): a rank forms the cross product of ITS columns over the whole contraction, sweeps them, ONE all-gather per "
+                             "half-step; reduce (north_star's wording): contraction-sharded [Gram | cross product], ONE all-reduce, column-sharded "
+                             "sweep, ONE all-gather; same steps, the reduce region follows the cols regions from the factors they left")
+            h.comm_set_form("cols")
+
+        # GPU mse after `cpu_iters` iterations from the warmed state (what the CPU sample reproduces)
+        gpu_check = None
+        Ww = Hw = None
+        if args.cpu_iters > 0 and world == 1 and not force_comm:
+            # the state the timed region started from, reproduced (the loop is deterministic): the CPU sample starts there too.
+            # (Taken here, not between warm-up and timing: a host round trip there lets the clocks drop before the timed region.)
+            h.set_factors(k, W0, H0)
+            run_steps(h, cfg, args.warmup, trace)
+            Ww, Hw = h.get_factors()
+            gpu_check = run_steps(h, cfg, args.cpu_iters, trace)
 
     if rank != 0:
         h.close()
@@ -591,33 +625,9 @@ def main():
 
     s = 8 if args.precision == "f64" else 4
     inner, method = cfg["inner"], cfg["method"]
-    roofline, secondary, all_blocks, shares = analyse(cfg, args.config, kern, n, m, k, s, world, main_forms)
-
     ms_step = 1e3 * elapsed / args.steps
     step = step_block(cfg, n, m, k, s, trace, ms_step)
 
-    cpu = mse_check = None
-    if args.cpu_iters > 0 and world == 1 and not force_comm:  # the CPU baseline is timed on rank 0 at N=1 only
-        cpu, rc = cpu_baseline(A, Ww, Hw, k, cfg, args.cpu_iters, trace if trace > 0 else 999999)
-        g, c_ = float(gpu_check["mse_error"][-1]), float(rc["mse_error"][-1])
-        mse_check = dict(iterations_from_warm_state=args.cpu_iters, gpu=g, cpu=c_, rel_diff=abs(g - c_) / c_,
-                         gpu_average_epoch=float(np.sum(gpu_check["average_epoch"]) / args.cpu_iters), cpu_average_epoch=cpu["average_epoch"])
-
-    ms_all = [1e3 * t / args.steps for t in times]
-    # the rest of the picture in the same line (task 3): the .Call boundary's default mode and the other single-GPU configs
-    others = None
-    if args.others and world == 1 and not force_comm and args.config == 2 and args.precision == "f32" and args.protocol == "default":
-        h.close()
-        others = {}
-        for key, cid, pr, st, wu in (("config2_strict_f64", 2, "f64", 16, 3), ("config3_kl_lee_f32", 3, "f32", 8, 2), ("config5_na_reg_f32", 5, "f32", 12, 2)):
-            try:
-                others[key] = other_config(cid, pr, n, m, k, local_rank, st, wu)
-            except Exception as e:  # (never lose the headline over a secondary measurement)
-                others[key] = dict(error=f"{type(e).__name__}: {e}")
-    call = None
-    if args.call and world == 1 and not force_comm and args.config == 2 and args.precision == "f32" and args.protocol == "default":
-        del A  # (the child processes generate their own copy: 1.6 GB each way)
-        call = call_metric(n, m, k, local_rank, args.call_iters)
     out = {
         "metric": "nnmf iterations/sec + final MSE, dense A 20000x10000 k=50, 1/2/4/8 GPU",
         "value": args.steps / elapsed,
@@ -642,25 +652,51 @@ def main():
                                     if args.form == "reduce" and method < 3 and not cfg["na"] else
                                     f"columns sharded x{world} (cross product, Gram, sweep of a rank's columns) + 1 RCCL all-gather per half-step")
                                    if (world > 1 or force_comm) else "1 GPU")},
-        "repeats": {"ms_per_step": ms_all, "min": min(ms_all), "median": float(np.median(ms_all)), "max": max(ms_all),
-                    "final_mse": mses, "note": "consecutive timed regions of `steps` iterations each; `value` is the first"},
-        "roofline": roofline,
-        "roofline_secondary": secondary,
-        "roofline_all": all_blocks,
-        "other_configs": others,
-        "forms": forms,
-        "call": call,
         "step": step,
-        "cpu_baseline": cpu,
-        "mse_check": mse_check,
-        "phases_ms": dict(phases_ms, note="HIP-event time per step of each phase in the profiled replay, max over ranks; 'gram' = Gram fold + split copy; "
-                                           "'err_reduce' = reduction of the fused error sums; N > 1: 'allgather' / 'allreduce' = the RCCL call between two events on its stream "
-                                           "(includes waiting for the slowest rank), 'unpack' = scatter of the gathered slabs (+ split copy + Gram sum)"),
-        "kernels": kern,
-        "kernel_time_share": shares,
-        "profiled_ms_per_step": 1e3 * prof_elapsed / args.steps,
         "upload_and_prep_s": upload_s,
     }
+    if args.full:
+        roofline, secondary, all_blocks, shares = analyse(cfg, args.config, kern, n, m, k, s, world, main_forms)
+        cpu = mse_check = None
+        if args.cpu_iters > 0 and world == 1 and not force_comm:  # the CPU baseline is timed on rank 0 at N=1 only
+            cpu, rc = cpu_baseline(A, Ww, Hw, k, cfg, args.cpu_iters, trace if trace > 0 else 999999)
+            g, c_ = float(gpu_check["mse_error"][-1]), float(rc["mse_error"][-1])
+            mse_check = dict(iterations_from_warm_state=args.cpu_iters, gpu=g, cpu=c_, rel_diff=abs(g - c_) / c_,
+                             gpu_average_epoch=float(np.sum(gpu_check["average_epoch"]) / args.cpu_iters), cpu_average_epoch=cpu["average_epoch"])
+
+        ms_all = [1e3 * t / args.steps for t in times]
+        # the rest of the picture in the same line (task 3): the .Call boundary's default mode and the other single-GPU configs
+        others = None
+        if args.others and world == 1 and not force_comm and args.config == 2 and args.precision == "f32" and args.protocol == "default":
+            h.close()
+            others = {}
+            for key, cid, pr, st, wu in (("config2_strict_f64", 2, "f64", 16, 3), ("config3_kl_lee_f32", 3, "f32", 8, 2), ("config5_na_reg_f32", 5, "f32", 12, 2)):
+                try:
+                    others[key] = other_config(cid, pr, n, m, k, local_rank, st, wu)
+                except Exception as e:  # (never lose the headline over a secondary measurement)
+                    others[key] = dict(error=f"{type(e).__name__}: {e}")
+        call = None
+        if args.call and world == 1 and not force_comm and args.config == 2 and args.precision == "f32" and args.protocol == "default":
+            del A  # (the child processes generate their own copy: 1.6 GB each way)
+            call = call_metric(n, m, k, local_rank, args.call_iters)
+        out.update({
+            "repeats": {"ms_per_step": ms_all, "min": min(ms_all), "median": float(np.median(ms_all)), "max": max(ms_all),
+                        "final_mse": mses, "note": "consecutive timed regions of `steps` iterations each; `value` is the first"},
+            "roofline": roofline,
+            "roofline_secondary": secondary,
+            "roofline_all": all_blocks,
+            "other_configs": others,
+            "forms": forms,
+            "call": call,
+            "cpu_baseline": cpu,
+            "mse_check": mse_check,
+            "phases_ms": dict(phases_ms, note="HIP-event time per step of each phase in the profiled replay, max over ranks; 'gram' = Gram fold + split copy; "
+                                               "'err_reduce' = reduction of the fused error sums; N > 1: 'allgather' / 'allreduce' = the RCCL call between two events on its stream "
+                                               "(includes waiting for the slowest rank), 'unpack' = scatter of the gathered slabs (+ split copy + Gram sum)"),
+            "kernels": kern,
+            "kernel_time_share": shares,
+            "profiled_ms_per_step": 1e3 * prof_elapsed / args.steps,
+        })
     h.close()   # (communicator and process group go first: anything RCCL still prints must not follow the JSON line)
     if dist is not None:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 TAG=$1; CFG=$2; PREC=$3; STEPS=${4:-10}; shift 4
 OUT=$R/gpurun_out/prof
 mkdir -p $OUT
-BENCH="python $R/bench.py --config $CFG --precision $PREC --steps $STEPS --warmup 2 --cpu-iters 0 --repeats 1 --others 0 --call 0 $*"
+BENCH="python $R/bench.py --full --config $CFG --precision $PREC --steps $STEPS --warmup 2 --cpu-iters 0 --repeats 1 --others 0 --call 0 $*"
 (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG} -o p -- $BENCH > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/${TAG}_prof.err; echo "rocprof exit=$?")
 f=$(find $OUT/prof_${TAG} -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $OUT/${TAG}_kernel_stats.csv && head -16 "$f" | cut -c1-170
 rm -rf $OUT/prof_${TAG}

@@ -12,7 +12,7 @@ if [[ $WHAT == *tests* ]]; then
   (cd $R && timeout 1500 python -m pytest tests -m gpu -x -q > $O/${TAG}_gputests.log 2>&1; echo "gpu tests exit=$?"; tail -3 $O/${TAG}_gputests.log)
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 900 python $R/bench.py --steps 20 --warmup 5 > $O/${TAG}_cfg2_bench.json 2> $O/${TAG}_cfg2_bench.err; echo "bench exit=$?"
+  timeout 900 python $R/bench.py --full --steps 20 --warmup 5 > $O/${TAG}_cfg2_bench.json 2> $O/${TAG}_cfg2_bench.err; echo "bench exit=$?"
   python - <<PY
 import json
 d = json.load(open("$O/${TAG}_cfg2_bench.json"))

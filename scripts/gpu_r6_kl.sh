@@ -2,7 +2,7 @@
 # A/B of the KL tile kernel's starting states (in-kernel against the wh_store GEMM), strict config 5 / 3b timings
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
-B="python $R/bench.py --steps 6 --warmup 2 --cpu-iters 0 --repeats 2 --others 0 --call 0"
+B="python $R/bench.py --full --steps 6 --warmup 2 --cpu-iters 0 --repeats 2 --others 0 --call 0"
 for v in own gemm; do
   [ $v == gemm ] && export NNLM_KL_INIT_GEMM=1 || unset NNLM_KL_INIT_GEMM
   timeout 600 $B --config 3 --precision f32 > $O/kl_${v}_cfg3.json 2> $O/kl_${v}_cfg3.err; echo "cfg3 $v exit=$?"

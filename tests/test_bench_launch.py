@@ -111,3 +111,31 @@ def test_roofline_block_is_the_dominant_kernel_with_a_real_bound():
     assert roof["traffic"] is not None and 0.9 < roof["traffic"] / by < 1.3  # (PMC bytes per launch from the committed summaries)
     assert sec["bound"] == "latency" and "sweep_scd_qw_kernel" in sec["kernel"]
     assert {"xprod_h", "xprod_w", "xprod_w_err", "sweep_h", "sweep_w"} <= set(blocks)
+
+
+def test_dump_outputs_writes_fp64_within_the_limit_and_samples_the_same_entries_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: every array as fp64 <name>.npy; under the limit whole, beyond it each array over 1 MB as the same fixed seeded
+    sample of its entries in every run (so two builds' dumps compare entry for entry), small arrays (the traces) still whole."""
+    import numpy as np
+    bench = _bench()
+    rng = np.random.default_rng(3)
+    arrays = dict(W=rng.random((500, 300)).astype(np.float32), H=rng.random((300, 600)), mse_error=np.arange(5.0))
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for nm, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{nm}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    limit = 1_500_000
+    monkeypatch.setattr(bench, "DUMP_LIMIT", limit)
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    data = 0
+    for nm, a in arrays.items():
+        got, again = np.load(tmp_path / "a" / f"{nm}.npy"), np.load(tmp_path / "b" / f"{nm}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, again)
+        if nm == "mse_error":
+            assert np.array_equal(got, a)
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, got.size, replace=False))
+            assert 0 < got.size < a.size and np.array_equal(got, a.ravel()[idx].astype(np.float64))
+        data += got.nbytes
+    assert data <= limit

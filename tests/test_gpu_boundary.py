@@ -362,7 +362,7 @@ def test_bench_multi_gpu_branch_runs_with_a_forced_one_rank_communicator(tmp_pat
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
-    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--cpu-iters", "0", "--repeats", "1",
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full", "--cpu-iters", "0", "--repeats", "1",
             "--size", "3000,2000,20"]
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NNLM_BENCH_FORCE_COMM="1")
     def line_of(environment):
@@ -380,6 +380,49 @@ def test_bench_multi_gpu_branch_runs_with_a_forced_one_rank_communicator(tmp_pat
         assert line["n_gpus"] == 1 and line["steps"] == 6 and line["value"] > 0 and line["scaling"] == "strong"
     assert "all-gather" in sharded["config"]["parallelism"] and plain["config"]["parallelism"] == "1 GPU"
     assert abs(sharded["final_mse"] - plain["final_mse"]) < 1e-6 * plain["final_mse"]
+
+
+def test_plain_bench_line_is_the_headline_and_its_dump_is_what_the_timed_steps_computed(tmp_path):
+    """A plain bench.py run (no --full) times --steps steps once and prints the headline alone: what takes runs of its own (profiled
+    replay, CPU baseline, other configurations, call-level metric, repeated regions) belongs to --full.  --dump-outputs DIR writes what
+    its timed nnlm_run() returned after the last step -- W, H and the error traces -- and that must be what the same warm-up and steps
+    compute on a handle of this process from bench.py's own seeded inputs."""
+    import json
+    import subprocess
+    import bench  # (the repository root is on sys.path: tests/conftest.py)
+    n, m, k, steps, warmup = 3000, 2000, 20, 6, 2
+    cmd = [sys.executable, bench.__file__, "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--size", f"{n},{m},{k}",
+           "--dump-outputs", str(tmp_path)]
+    env = {v: x for v, x in os.environ.items() if v not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "NNLM_BENCH_FORCE_COMM")}
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, check=True, timeout=600).stdout.strip().splitlines()
+    assert len(out) == 1, out[-3:]
+    line = json.loads(out[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "final_mse"):
+        assert key in line, key
+    assert line["steps"] == steps and line["unit"] == "iterations/s" and line["higher_is_better"] is True
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-9 * 1e3
+    assert not {"repeats", "roofline", "kernels", "phases_ms", "cpu_baseline", "other_configs", "call", "forms"} & set(line)
+
+    cfg = bench.CONFIGS[2]
+    A, W0, H0 = bench.make_inputs(n, m, k, cfg["na"])
+    cus = int(os.environ.get("NNLM_TEST_CUS", "0") or 0)
+    _lib.debug_set_cus(0)  # (plan the launches as bench.py's process does, for the device's own CU count)
+    try:
+        with nnlm_amd.Handle(0, _lib.PREC_F32) as h:
+            h.set_matrix(A)
+            h.set_factors(k, W0, H0)
+            bench.run_steps(h, cfg, warmup, cfg["trace"])
+            r = bench.run_steps(h, cfg, steps, cfg["trace"])
+            W, H = h.get_factors()
+    finally:
+        _lib.debug_set_cus(cus)
+    want = dict(W=W, H=H, mse_error=r["mse_error"], mkl_error=r["mkl_error"], target_error=r["target_error"], average_epoch=r["average_epoch"])
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{nm}.npy" for nm in want)
+    for nm, w in want.items():
+        got = np.load(tmp_path / f"{nm}.npy")
+        assert got.dtype == np.float64 and got.shape == w.shape, (nm, got.dtype, got.shape, w.shape)
+        assert np.allclose(got, w, rtol=1e-12, atol=0.0), (nm, relF(got, w))
+    assert abs(float(np.load(tmp_path / "mse_error.npy")[-1]) - line["final_mse"]) <= 1e-12 * line["final_mse"]
 
 
 def test_profile_scopes_account_for_the_step_and_the_fused_error_reduction_is_not_a_pass_over_A():
