@@ -88,6 +88,16 @@ int nnlm_c_nnmf(const double *A, int n, int m, unsigned k,
                 double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
                 int *n_trace, unsigned *n_iteration, int *warned,
                 const nnlm_callbacks *cb);
+/* nnlm_c_nnmf on a sparse A (canonical CSC, see nnlm_set_matrix_csc); the arguments after k are those of nnlm_c_nnmf.  Methods 1 and 2. */
+int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k,
+                    const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                    const double alpha[3], const double beta[3],
+                    unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning,
+                    unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                    double *W_out, double *H_out,
+                    double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                    int *n_trace, unsigned *n_iteration, int *warned,
+                    const nnlm_callbacks *cb);
 
 /*
  * Replaces c_nnlm (reference src/nnlm.cpp:4-53; signature src/RcppExports.cpp:10-27).
@@ -98,6 +108,12 @@ int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q,
                 const double alpha[3], const int *mask, const double *beta0,
                 unsigned max_iter, double rel_tol, int n_threads, int method,
                 double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
+/* nnlm_c_nnlm with a sparse y (n x q, canonical CSC, see nnlm_set_matrix_csc); x stays dense; the arguments after q are those of
+ * nnlm_c_nnlm.  Methods 1 and 2. */
+int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                    const double alpha[3], const int *mask, const double *beta0,
+                    unsigned max_iter, double rel_tol, int n_threads, int method,
+                    double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
 
 /* ------------------------------------------------------------------------------------------
  * Resident API: the same path with A kept in HBM across calls.  The one-shot entries are thin
@@ -122,7 +138,17 @@ int nnlm_abi_version(void);
  * NNLM_PREC_F32 only: NNLM_ERR_UNSUPPORTED when A holds a finite entry beyond FLT_MAX or its largest entry is below 2^-100
  * (the 4-byte resident copy cannot represent it; NNLM_PREC_F64 takes such a matrix, as the reference does). */
 int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m);
-/* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag. */
+/* Sparse A, n x m in canonical CSC: colptr[m+1] (colptr[0] = 0, non-decreasing, colptr[m] = nnz; 64-bit, so nnz may exceed 2^31),
+ * rowidx[nnz] strictly increasing within a column, 0 <= rowidx < n, x[nnz] finite (rowidx / x may be NULL when nnz = 0).  Absent
+ * entries are ZEROS, not missing.  Replaces whatever matrix the handle held (nnlm_set_matrix does the same in reverse).  The handle keeps
+ * the CSC and the CSR of the same matrix in HBM (values in the mode's type, int32 indices, int64 pointers) and nothing n x m sized.
+ * NNLM_ERR_ARG for a non-canonical structure or a non-finite value; NNLM_PREC_F32 applies nnlm_set_matrix's range rule
+ * (NNLM_ERR_UNSUPPORTED).  nnz = 0, empty rows and empty columns are legal.  On such a handle nnlm_half_step, nnlm_iterate, nnlm_run and
+ * nnlm_errors work for methods 1 and 2 (square loss), at any rank, with masks; methods 3 and 4 (KL loss), nnlm_comm_init and
+ * nnlm_debug_partial return NNLM_ERR_UNSUPPORTED.  nnlm_errors' KL sum leaves out the zeros' -eps log(wh + eps), at most 3.7e-15 each. */
+int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag.  Sparse A: n m and 0, and kl_const counts
+ * the zeros ((n m - nnz) eps log eps). */
 int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const);
 
 /* Set rank, factors (W n x k, H k x m; NULL = zeros) and masks (NULL = none). */
@@ -156,7 +182,8 @@ int nnlm_sync(nnlm_handle *h);
 
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",
- * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack". */
+ * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack";
+ * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block). */
 int nnlm_profile_enable(nnlm_handle *h, int on);
 int nnlm_profile_get(nnlm_handle *h, const char *name, double *total_ms, long long *launches);
 int nnlm_profile_reset(nnlm_handle *h);
@@ -216,7 +243,8 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * round of four-column wavefronts, at most 32 columns per CU), -1 none yet), "sweep_groups_w" /
  * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "kl_form_w" / "kl_form_h" (KL solver of the
  * last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
- * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet). */
+ * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
+ * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies). */
 int nnlm_get_info(nnlm_handle *h, const char *key, double *value);
 
 #ifdef __cplusplus

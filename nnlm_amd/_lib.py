@@ -30,6 +30,7 @@ EXPORTS = [
     "nnlm_profile_get", "nnlm_profile_reset", "nnlm_comm_unique_id", "nnlm_comm_init", "nnlm_comm_info",
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
     "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
+    "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
 ]
 
 
@@ -71,9 +72,16 @@ def load():
     lib.nnlm_c_nnmf.argtypes = [dp, C.c_int, C.c_int, C.c_uint, dp, dp, ip, ip, dp, dp, C.c_uint, C.c_double, C.c_int,
                                 C.c_int, C.c_int, C.c_uint, C.c_double, C.c_int, C.c_uint, dp, dp, dp, dp, dp, dp, ip,
                                 C.POINTER(C.c_uint), ip, C.POINTER(Callbacks)]
+    lp = C.POINTER(C.c_longlong)
+    lib.nnlm_c_nnmf_csc.restype = C.c_int
+    lib.nnlm_c_nnmf_csc.argtypes = [C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnmf.argtypes[3:]
     lib.nnlm_c_nnlm.restype = C.c_int
     lib.nnlm_c_nnlm.argtypes = [dp, dp, C.c_int, C.c_int, C.c_int, dp, ip, dp, C.c_uint, C.c_double, C.c_int, C.c_int,
                                 dp, ip, C.POINTER(Callbacks)]
+    lib.nnlm_c_nnlm_csc.restype = C.c_int
+    lib.nnlm_c_nnlm_csc.argtypes = [dp, C.c_int, C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnlm.argtypes[5:]
+    lib.nnlm_set_matrix_csc.restype = C.c_int
+    lib.nnlm_set_matrix_csc.argtypes = [vp, C.c_int, C.c_int, lp, ip, dp]
     lib.nnlm_create.restype = C.c_int
     lib.nnlm_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     lib.nnlm_destroy.restype = None
@@ -167,6 +175,17 @@ def _lgl(mask, shape):
     return np.array(np.asarray(mask).reshape(shape) != 0, dtype=np.int32, order="F")
 
 
+def _lp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_longlong))
+
+
+def _csc_arrays(indptr, indices, data):
+    """CSC arrays in the types of the C ABI (int64 pointers, int32 indices, fp64 values), contiguous; the structure is passed as it is
+    (nnlm_set_matrix_csc checks it: canonicalisation is the caller's, see api.as_csc)."""
+    return (np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32),
+            np.ascontiguousarray(data, dtype=np.float64))
+
+
 def _vec3(v):
     return np.array(v, dtype=np.float64).reshape(3)
 
@@ -243,6 +262,54 @@ def c_nnlm(x, y, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callb
     return dict(coefficient=np.ascontiguousarray(coef), n_iteration=int(nit.value))
 
 
+def c_nnmf_csc(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+               inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf on a sparse A given as canonical CSC arrays (indptr[m+1], indices, data) of shape (n, m); square loss (methods 1, 2)."""
+    lib = load()
+    n, m = (int(v) for v in shape)
+    ptr, idx, val = _csc_arrays(indptr, indices, data)
+    k = int(k)
+    Wi = _f64(W, (n, k)) if W is not None and np.size(W) > 0 else None
+    Hi = _f64(H, (k, m)) if H is not None and np.size(H) > 0 else None
+    Wm_, Hm_ = _lgl(Wm, (n, k)), _lgl(Hm, (k, m))
+    al, be = _vec3(alpha), _vec3(beta)
+    cap = lib.nnlm_trace_capacity(int(max_iter), int(trace) if int(trace) > 0 else 1)
+    Wo = np.zeros((n, k), order="F")
+    Ho = np.zeros((k, m), order="F")
+    mse, mkl, terr, ep = (np.zeros(cap) for _ in range(4))
+    n_trace, n_it, warned = C.c_int(0), C.c_uint(0), C.c_int(0)
+    rc = lib.nnlm_c_nnmf_csc(n, m, _lp(ptr), _ip(idx), _dp(val), k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
+                             float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
+                             float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
+                             _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
+                             C.byref(callbacks) if callbacks is not None else None)
+    _check(rc)
+    e = n_trace.value
+    return dict(W=np.ascontiguousarray(Wo), H=np.ascontiguousarray(Ho), mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(),
+                target_error=terr[:e].copy(), average_epoch=ep[:e].copy(), n_iteration=int(n_it.value),
+                warning=bool(warned.value))
+
+
+def c_nnlm_csc(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
+    """c_nnlm with a sparse y (canonical CSC arrays of shape (n, q)); x stays dense; square loss (methods 1, 2)."""
+    lib = load()
+    x = _f64(x)
+    n, p = x.shape
+    if int(y_shape[0]) != n:
+        raise ValueError("y has %d rows, x has %d" % (int(y_shape[0]), n))
+    q = int(y_shape[1])
+    ptr, idx, val = _csc_arrays(y_indptr, y_indices, y_data)
+    b0 = _f64(beta0, (p, q)) if beta0 is not None and np.size(beta0) > 0 else None
+    mk = _lgl(mask, (p, q))
+    al = _vec3(alpha)
+    coef = np.zeros((p, q), order="F")
+    nit = C.c_int(0)
+    rc = lib.nnlm_c_nnlm_csc(_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val), _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol),
+                             int(n_threads), int(method), _dp(coef), C.byref(nit), C.byref(callbacks) if callbacks is not None else None)
+    _check(rc)
+    return dict(coefficient=np.ascontiguousarray(coef), n_iteration=int(nit.value))
+
+
 # ----------------------------------------------------------------------------------------------
 # resident API
 # ----------------------------------------------------------------------------------------------
@@ -279,6 +346,13 @@ class Handle:
         A = _f64(A)
         self.n, self.m = A.shape
         self._ck(self._lib.nnlm_set_matrix(self._h, _dp(A), self.n, self.m))
+
+    def set_matrix_csc(self, indptr, indices, data, shape):
+        """Sparse A of shape (n, m) as CSC arrays (canonical: see nnlm_set_matrix_csc; absent entries are zeros)."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
 
     def matrix_info(self):
         nn, am, kc = C.c_double(0), C.c_int(0), C.c_double(0)
@@ -357,7 +431,8 @@ class Handle:
         self._ck(self._lib.nnlm_comm_set_form(self._h, FORMS[form] if isinstance(form, str) else int(form)))
 
     def get_info(self, key):
-        """cus, sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h."""
+        """cus, sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
+        matrix_nnz (-1 for a dense matrix), matrix_bytes."""
         v = C.c_double(0)
         self._ck(self._lib.nnlm_get_info(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import time
 import warnings
+from collections import namedtuple
 
 import numpy as np
 
@@ -25,6 +26,64 @@ from . import _lib
 
 class NnlmStop(ValueError):
     """R's stop()."""
+
+
+# ------------------------------------------------------------------------------------------------
+# sparse input
+# ------------------------------------------------------------------------------------------------
+CSC = namedtuple("CSC", "indptr indices data shape")
+CSC.__doc__ = "Canonical CSC of a sparse matrix: int64 indptr[m+1], int32 indices (sorted, unique within a column), fp64 data, (n, m)."
+
+
+def is_sparse(A):
+    """Duck typing: anything with tocsc() (scipy sparse matrices and arrays qualify; scipy itself is never imported)."""
+    return not isinstance(A, np.ndarray) and callable(getattr(A, "tocsc", None))
+
+
+def as_csc(A):
+    """Canonical CSC of a sparse object (tocsc() yielding indptr, indices, data, shape): duplicates summed (in their stored order), row
+    indices sorted within each column.  Explicitly stored zeros are kept (they are zeros either way)."""
+    c = A.tocsc()
+    n, m = (int(v) for v in c.shape)
+    indptr = np.asarray(c.indptr, dtype=np.int64)
+    rows = np.asarray(c.indices, dtype=np.int64)
+    data = np.asarray(c.data, dtype=np.float64)
+    if indptr.shape != (m + 1,) or indptr[0] != 0 or np.any(np.diff(indptr) < 0) or indptr[-1] != rows.size or rows.size != data.size:
+        raise NnlmStop("A sparse matrix must have a valid CSC structure (indptr of length ncol + 1, non-decreasing, ending at nnz).")
+    if rows.size and (rows.min() < 0 or rows.max() >= n):
+        raise NnlmStop("A sparse matrix has a row index out of range.")
+    cols = np.repeat(np.arange(m, dtype=np.int64), np.diff(indptr))
+    order = np.lexsort((rows, cols))  # (stable: duplicates keep their stored order)
+    rows, cols, data = rows[order], cols[order], data[order]
+    if rows.size:
+        first = np.ones(rows.size, dtype=bool)
+        first[1:] = (rows[1:] != rows[:-1]) | (cols[1:] != cols[:-1])
+        starts = np.flatnonzero(first)
+        data = np.add.reduceat(data, starts)
+        rows, cols = rows[starts], cols[starts]
+    indptr = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols, minlength=m), out=indptr[1:])
+    return CSC(indptr, rows.astype(np.int32), np.ascontiguousarray(data), (n, m))
+
+
+def csc_toarray(c):
+    """Dense n x m array of a CSC (host side: small matrices and the error summary of nnlm())."""
+    n, m = c.shape
+    out = np.zeros((n, m))
+    cols = np.repeat(np.arange(m), np.diff(c.indptr))
+    out[np.asarray(c.indices, dtype=np.int64), cols] = c.data
+    return out
+
+
+def _sparse_input(A, name, loss):
+    """Sparse argument of nnmf() / nnlm(): canonical CSC; square loss only; no missing entries."""
+    if loss == "mkl":
+        raise NnlmStop("Sparse %s is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'." % name)
+    c = as_csc(A)
+    if not np.all(np.isfinite(c.data)):
+        raise NnlmStop("Sparse %s must not contain NA / non-finite values: absent entries are zeros, not missing; use a dense matrix for "
+                       "missing values." % name)
+    return c
 
 
 # ------------------------------------------------------------------------------------------------
@@ -196,20 +255,25 @@ def prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="ms
         inner_max_iter = 50 if loss == "mse" else 1  # R/nnmf.R:139
     if trace is None:
         trace = 100 / inner_max_iter  # R/nnmf.R:138
-    A = np.asarray(A)
-    if A.ndim != 2:
-        raise NnlmStop("A must be a matrix")
-    check_matrix(A, input_name="A")
-    A = np.asarray(A, dtype=np.float64)
-    n, m = A.shape
+    sparse = is_sparse(A)
+    if sparse:  # canonical CSC (args[0]); absent entries are zeros, so there is nothing missing
+        A = _sparse_input(A, "A", loss)
+        n, m = A.shape
+    else:
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise NnlmStop("A must be a matrix")
+        check_matrix(A, input_name="A")
+        A = np.asarray(A, dtype=np.float64)
+        n, m = A.shape
     im = reformat_input(init, mask, n, m, int(k), rng=rng)
     K = im["K"]
     alpha = np.concatenate([np.atleast_1d(np.asarray(alpha, dtype=np.float64)), np.zeros(3)])[:3]
     beta = np.concatenate([np.atleast_1d(np.asarray(beta, dtype=np.float64)), np.zeros(3)])[:3]
     code = get_method_code(method, loss)
-    min_k = min(A.shape)
-    isna = np.isnan(A)
-    if isna.any():
+    min_k = min(n, m)
+    isna = None if sparse else np.isnan(A)
+    if isna is not None and isna.any():
         min_k = min(min_k, int((m - isna.sum(axis=1)).min()), int((n - isna.sum(axis=0)).min()))
     if check_k and K > min_k and np.all(np.concatenate([alpha, beta]) == 0):
         raise NnlmStop("k larger than %d is not recommended, unless properly masked or regularized.\n"
@@ -260,7 +324,10 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random(), print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    out = _lib.c_nnmf(*args, callbacks=cb)
+    if isinstance(args[0], CSC):
+        out = _lib.c_nnmf_csc(*args[0], *args[1:], callbacks=cb)
+    else:
+        out = _lib.c_nnmf(*args, callbacks=cb)
     return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
 
 
@@ -286,20 +353,23 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
     x = np.asarray(x)
-    yv = np.asarray(y)
+    y_sparse = is_sparse(y)
+    yv = _sparse_input(y, "y", loss) if y_sparse else np.asarray(y)
     with np.errstate(invalid="ignore"):
         if show_warning and loss == "mkl" and (np.any(x < 0) or np.any(yv < 0)):
             warnings.warn("x or y have negative values. One should instead use method == 'mse'.", RuntimeWarning, stacklevel=3)
-    is_y_vector = yv.ndim == 1
-    ym = _as_matrix(yv)
-    check_matrix(ym, check_na=False)
+    is_y_vector = (not y_sparse) and yv.ndim == 1
+    ym = yv if y_sparse else _as_matrix(yv)  # (sparse y: canonical CSC, args[1])
+    if not y_sparse:
+        check_matrix(ym, check_na=False)
     check_matrix(x, check_na=True)
     if x.ndim != 2:
         raise NnlmStop("x must be a matrix")
     if x.shape[0] != ym.shape[0]:
         raise NnlmStop("Dimensions of x and y do not match.")
     x = np.asarray(x, dtype=np.float64)
-    ym = np.asarray(ym, dtype=np.float64)
+    if not y_sparse:
+        ym = np.asarray(ym, dtype=np.float64)
     if max_iter <= 0:
         raise NnlmStop("max.iter must be positive.")
     if n_threads < 0:
@@ -329,6 +399,8 @@ def finish_nnlm(sol, ctx):
     """R/nnlm.R:122-144."""
     coef = np.array(sol["coefficient"])
     x, y, alpha, loss = ctx["x"], ctx["y"], ctx["alpha"], ctx["loss"]
+    if isinstance(y, CSC):  # (the summary compares y with the dense x beta: n x q either way)
+        y = csc_toarray(y)
     err = mse_mkl(y, x @ coef, na_rm=True, show_warning=False)
     target = 0.5 * err["MSE"] if loss == "mse" else err["MKL"]
     target = target + (alpha[0] - alpha[1]) * float(np.sum(coef ** 2)) + alpha[1] * float(np.sum(coef.sum(axis=0) ** 2)) \
@@ -345,6 +417,8 @@ def nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, 
     args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random())
+    if isinstance(args[1], CSC):
+        return finish_nnlm(_lib.c_nnlm_csc(args[0], *args[1], *args[2:], callbacks=cb), ctx)
     return finish_nnlm(_lib.c_nnlm(*args, callbacks=cb), ctx)
 
 
@@ -354,7 +428,13 @@ def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=
     method = method or object["options"]["method"]
     loss = loss or object["options"]["loss"]
     solver = _nnlm or nnlm
-    if which != "A":
+    if which != "A" and is_sparse(newdata):  # (passed on to nnlm() as it is: duck-typed there)
+        nd = newdata
+        want = object["H"].shape[1] if which == "W" else object["W"].shape[0]
+        got = nd.shape[1] if which == "W" else nd.shape[0]
+        if int(got) != int(want):
+            raise NnlmStop("Dimension of newdata does not match the %s factor of the model." % ("H" if which == "W" else "W"))
+    elif which != "A":
         nd = np.asarray(newdata)
         if which == "W":
             check_matrix(nd, dm=(None, object["H"].shape[1]))

@@ -73,3 +73,36 @@ __device__ static inline long long wave_sum_ll(long long v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// ln x for a positive, finite, NORMAL double (the error sums take ln(ahat + 1e-16): never zero, never denormal) in ~28 fp64
+// instructions: x = m 2^e with m in [sqrt(1/2), sqrt 2), ln m = 2 atanh(s), s = (m - 1) / (m + 1) (|s| <= 0.1716: ten terms of the
+// odd series leave 6e-19), the quotient correctly rounded (reciprocal, two Newton steps, one residual correction).  libm's log()
+// compiles to ~55 instructions here and was two thirds of errors_kernel<double>'s arithmetic.  Error < 2 ulp of the result.
+// (The series coefficients live in constant memory, NOT as literals: gfx950's VOP3 encoding has no 64-bit literal operand, so each
+// literal costs a VGPR pair -- 30 registers of a kernel that needs them for occupancy; loaded from a non-const __constant__ array
+// they arrive by s_load and stay in SGPR pairs, one scalar source per fma.)
+static __constant__ double NNLM_LOGC[19] = {1.0 / 21.0, 1.0 / 19.0, 1.0 / 17.0, 1.0 / 15.0, 1.0 / 13.0, 1.0 / 11.0, 1.0 / 9.0, 1.0 / 7.0,
+                                            1.0 / 5.0,  1.0 / 3.0,  1.9082149292705877e-10, 0.693147180369123816490,
+                                            1.0 / 7.0, -1.0 / 6.0, 1.0 / 5.0, -1.0 / 4.0, 1.0 / 3.0, -0.5, 0.69314718055994530942}; // [12..18]: nnlm_log_tab
+__device__ static inline double nnlm_log_pos(double x)
+{
+    double m = __builtin_amdgcn_frexp_mant(x); // [0.5, 1)
+    int e = __builtin_amdgcn_frexp_exp(x);
+    const bool lo = m < 0.70710678118654752;
+    m = lo ? 2.0 * m : m;
+    e = lo ? e - 1 : e;
+    const double num = m - 1.0, den = m + 1.0;
+    double r = __builtin_amdgcn_rcp(den);
+    r = __builtin_fma(__builtin_fma(-den, r, 1.0), r, r);
+    r = __builtin_fma(__builtin_fma(-den, r, 1.0), r, r);
+    double sq = num * r;
+    sq = __builtin_fma(__builtin_fma(-den, sq, num), r, sq);
+    const double z = sq * sq;
+    double p = NNLM_LOGC[0];
+#pragma unroll
+    for (int c = 1; c < 10; c++) p = __builtin_fma(p, z, NNLM_LOGC[c]);
+    // ln m = 2 s + 2 s z p;  e ln 2 in two pieces (the high one has 11 trailing zero bits: e * LN2_HI is exact for |e| < 2048)
+    const double ed = (double)e;
+    const double t = __builtin_fma(2.0 * sq * z, p, ed * NNLM_LOGC[10]);
+    return __builtin_fma(ed, NNLM_LOGC[11], 2.0 * sq + t);
+}

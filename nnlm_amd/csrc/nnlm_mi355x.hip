@@ -39,13 +39,17 @@
 
 static thread_local std::string g_last_error;
 
-enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE, P_COUNT };
+enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
 //  "errors": a separate pass over A (errors_f32_kernel / errors64_kernel + its reduction); "err_reduce": the reduction of the partial sums the
 //  fused cross product left behind -- 5 us, no HBM work: it must not be priced as a pass over A
-static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce"};
+//  "spmm_h" / "spmm_w": the cross products of a sparse A (row copy of the fixed factor + spmm_kernel + its fix-up); "sp_errors": the error
+//  block of a sparse A (sums over the non-zeros, the two Grams and the factors' sums)
+static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
+                                          "spmm_h", "spmm_w", "sp_errors"};
 
 struct ProfRec {
     int id;
@@ -114,6 +118,20 @@ struct nnlm_handle {
     double *partials = nullptr;
     size_t partials_elems = 0;
     double *scal = nullptr;              // 16 doubles of reduction results
+    // sparse A (nnlm_set_matrix_csc, k_sparse.h): CSC and the CSR of the same matrix, values in the mode's type; nothing n x m sized exists
+    // on such a handle (A, miss, A16, AT, What stay NULL) and x16 is off
+    bool sparse = false;
+    long long nnz = 0;
+    long long *sp_cptr = nullptr, *sp_rptr = nullptr; // [m + 1], [n + 1]
+    int *sp_ridx = nullptr, *sp_cidx = nullptr;       // row of each CSC entry, column of each CSR entry (ascending within a column / row)
+    void *sp_cval = nullptr, *sp_rval = nullptr;      // values, fp32 (F32 mode) or fp64
+    size_t sp_bytes = 0;                              // device bytes of the six arrays
+    void *sp_Y = nullptr;                             // [max(npad, mpad)][KP] row copy of the fixed factor (mode's type)
+    double *sp_carry = nullptr;                       // [spmm workers][64] heads of the columns that straddle a worker boundary
+    double *sp_Wrow = nullptr;                        // error block: [npad][KP] fp64 rows of W
+    double *sp_eslabs = nullptr;                      // error block: Gram partial sums
+    double *sp_eG = nullptr;                          // error block: W^T W, H H^T [KP][KP] each, W's and H's sums over i / j [KP] each, S1..S3
+    double *sp_epart = nullptr;                       // error block: per-workgroup partial sums
     unsigned long long *sweeps = nullptr; // [2] device counters; sw_active = the one the current trace window sums into
     int sw_active = 0;
     double *host_res = nullptr;           // pinned: 8 reduction results + sweep counter of the asynchronous error block
@@ -590,6 +608,14 @@ static void free_factors(nnlm_handle *h)
     hipFree(h->Yrow);
     hipFree(h->Gcols);
     h->red = h->Yrow = h->Gcols = nullptr;
+    hipFree(h->sp_Y);
+    hipFree(h->sp_carry);
+    hipFree(h->sp_Wrow);
+    hipFree(h->sp_eslabs);
+    hipFree(h->sp_eG);
+    hipFree(h->sp_epart);
+    h->sp_Y = nullptr;
+    h->sp_carry = h->sp_Wrow = h->sp_eslabs = h->sp_eG = h->sp_epart = nullptr;
     h->W64 = h->H64 = nullptr;
     h->Wop = nullptr;
     h->Wmask = h->Hmask = nullptr;
@@ -620,7 +646,37 @@ static void free_matrix(nnlm_handle *h)
     h->miss = nullptr;
     h->missT = nullptr;
     h->partials = nullptr;
+    hipFree(h->sp_cptr);
+    hipFree(h->sp_rptr);
+    hipFree(h->sp_ridx);
+    hipFree(h->sp_cidx);
+    hipFree(h->sp_cval);
+    hipFree(h->sp_rval);
+    h->sp_cptr = h->sp_rptr = nullptr;
+    h->sp_ridx = h->sp_cidx = nullptr;
+    h->sp_cval = h->sp_rval = nullptr;
+    h->sp_bytes = 0;
+    h->sparse = false;
+    h->nnz = 0;
+    h->x16 = x16_enabled(h->prec); // (a sparse matrix turned it off)
     h->n = h->m = 0;
+}
+
+// a matrix is set: the dense resident layout or the sparse one
+static bool has_matrix(const nnlm_handle *h) { return h && (h->A || h->sparse); }
+
+// device bytes of the resident matrix: dense A, its missing-entry bitmaps and split-fp16 / transposed copies; or the CSC + CSR arrays
+static double matrix_bytes(const nnlm_handle *h)
+{
+    if (h->sparse) return (double)h->sp_bytes;
+    if (!h->A) return 0.0;
+    const double cnt = (double)h->npad * h->mpad;
+    double b = cnt * esize(h) + 4096 + (double)h->mpad * (h->npad / 32) * 4 + 64;
+    if (h->missT) b += (double)h->npad * (h->mpad / 32) * 4 + 64;
+    if (h->A16) b += cnt * 4 + 4096;
+    if (h->A16T) b += cnt * 4 + 4096;
+    if (h->AT) b += cnt * esize(h) + 4096;
+    return b;
 }
 
 extern "C" void nnlm_destroy(nnlm_handle *h)
@@ -826,9 +882,118 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
     return NNLM_OK;
 }
 
+// Sparse A (include/nnlm_mi355x.h): canonical CSC, absent entries are zeros.  Validated on the host, the CSR of the same matrix is built
+// there too (counting sort by row: the columns of a row come out ascending), both are uploaded once in the mode's value type.
+template <typename T>
+static int sp_upload(nnlm_handle *h, const long long *colptr, const int *rowidx, const double *x, const std::vector<long long> &rptr,
+                     const std::vector<int> &cidx, const std::vector<double> &rval)
+{
+    const int n = h->n, m = h->m;
+    const long long nnz = h->nnz;
+    const size_t vb = (size_t)nnz * sizeof(T) + 64, ib = (size_t)nnz * 4 + 64;
+    HIPCHK(h, hipMalloc(&h->sp_cptr, (size_t)(m + 1) * 8));
+    HIPCHK(h, hipMalloc(&h->sp_rptr, (size_t)(n + 1) * 8));
+    HIPCHK(h, hipMalloc(&h->sp_ridx, ib));
+    HIPCHK(h, hipMalloc(&h->sp_cidx, ib));
+    HIPCHK(h, hipMalloc(&h->sp_cval, vb));
+    HIPCHK(h, hipMalloc(&h->sp_rval, vb));
+    h->sp_bytes = (size_t)(m + 1) * 8 + (size_t)(n + 1) * 8 + 2 * ib + 2 * vb;
+    HIPCHK(h, hipMemcpy(h->sp_cptr, colptr, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMemcpy(h->sp_rptr, rptr.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz > 0) {
+        HIPCHK(h, hipMemcpy(h->sp_ridx, rowidx, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        HIPCHK(h, hipMemcpy(h->sp_cidx, cidx.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+        std::vector<T> v((size_t)nnz);
+        for (long long e = 0; e < nnz; e++) v[e] = (T)x[e];
+        HIPCHK(h, hipMemcpy(h->sp_cval, v.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+        for (long long e = 0; e < nnz; e++) v[e] = (T)rval[e];
+        HIPCHK(h, hipMemcpy(h->sp_rval, v.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+    }
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_set_matrix_csc: handle is NULL");
+    if (n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: A must be a non-empty n x m matrix with colptr[m + 1] (n=%d, m=%d)", n, m);
+    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_matrix_csc: a sparse matrix is single-GPU only (this handle has a communicator)");
+    if (colptr[0] != 0) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: colptr[0] = %lld, must be 0", colptr[0]);
+    for (int j = 0; j < m; j++)
+        if (colptr[j + 1] < colptr[j]) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: colptr decreases at column %d", j);
+    const long long nnz = colptr[m];
+    if (nnz > 0 && (!rowidx || !x)) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: rowidx / x is NULL with nnz = %lld", nnz);
+    if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: nnz = %lld exceeds n * m", nnz);
+    std::vector<long long> rptr((size_t)n + 1, 0);
+    double over = 0.0, mx = 0.0, klc = 0.0;
+    for (int j = 0; j < m; j++)
+        for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
+            const int i = rowidx[e];
+            if (i < 0 || i >= n) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: row index %d out of range at entry %lld (column %d)", i, e, j);
+            if (e > colptr[j] && i <= rowidx[e - 1])
+                return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: row indices of column %d are not strictly increasing (entry %lld)", j, e);
+            const double v = x[e];
+            if (!std::isfinite(v))
+                return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: entry %lld (row %d, column %d) is not finite; a sparse matrix has no missing entries "
+                                             "(use nnlm_set_matrix for NA data)", e, i, j);
+            rptr[(size_t)i + 1]++;
+            if (std::fabs(v) > 3.4028234663852886e38) over += 1.0;
+            const double fv = std::fabs((double)(float)v);
+            if (fv > mx) mx = fv;
+            klc += (v + NNLM_TINY) * std::log(v + NNLM_TINY) - v; // src/nnmf.cpp:70,73 over the non-zeros
+        }
+    if (h->prec == NNLM_PREC_F32 && over > 0.0)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
+                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of nnlm_c_nnmf_csc / nnlm_c_nnlm_csc)", over);
+    if (h->prec == NNLM_PREC_F32 && mx > 0.0 && mx < 7.8886090522101181e-31)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "max |A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale A or use "
+                                             "the strict fp64 mode", mx);
+    for (int i = 0; i < n; i++) rptr[(size_t)i + 1] += rptr[i];
+    std::vector<int> cidx((size_t)nnz);
+    std::vector<double> rval((size_t)nnz);
+    {
+        std::vector<long long> next(rptr.begin(), rptr.end() - 1);
+        for (int j = 0; j < m; j++)
+            for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
+                const long long d = next[rowidx[e]]++;
+                cidx[d] = j;
+                rval[d] = x[e];
+            }
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    sync_all(h);
+    free_factors(h);
+    free_matrix(h);
+    h->n = n;
+    h->m = m;
+    h->npad = round_up_i(n, NNLM_PAD_N); // (the factors keep their padded layouts)
+    h->mpad = round_up_i(m, NNLM_PAD_M);
+    h->sparse = true;
+    h->x16 = false;
+    h->nnz = nnz;
+    const int rc = h->prec == NNLM_PREC_F64 ? sp_upload<double>(h, colptr, rowidx, x, rptr, cidx, rval) : sp_upload<float>(h, colptr, rowidx, x, rptr, cidx, rval);
+    if (rc != NNLM_OK) {
+        free_matrix(h);
+        return rc;
+    }
+    // partial sums of the error block (three per workgroup of sp_errors_kernel) and of the penalty sums (three per 256 columns)
+    const int nw = nnlm_sp_workers(nnz, 64, h->cus_device); // (the most workgroups any rank asks for: one worker per wavefront)
+    const size_t eb = (size_t)(nw + 3) / 4, pb = (size_t)((n > m ? n : m) + 255) / 256;
+    h->partials_elems = 3 * (eb > pb ? eb : pb) + 64;
+    if (hipMalloc(&h->partials, h->partials_elems * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        free_matrix(h);
+        return fail(h, NNLM_ERR_HIP, "nnlm_set_matrix_csc: hipMalloc of %zu partial sums failed", h->partials_elems);
+    }
+    h->n_non_missing = (double)n * (double)m;
+    h->any_missing = false;
+    // the zeros add (n m - nnz) eps log eps
+    h->kl_const = (klc + ((double)n * (double)m - (double)nnz) * (NNLM_TINY * std::log(NNLM_TINY))) / h->n_non_missing;
+    return NNLM_OK;
+}
+
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
 {
-    if (!h || !h->A) return fail(h, NNLM_ERR_ARG, "nnlm_matrix_info: no matrix set");
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_matrix_info: no matrix set");
     if (n_non_missing) *n_non_missing = h->n_non_missing;
     if (any_missing) *any_missing = h->any_missing ? 1 : 0;
     if (kl_const) *kl_const = h->kl_const;
@@ -925,7 +1090,7 @@ static void pack_mask_cols(const int *mask, int k, int ncols, bool transposed_in
 
 extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, const double *H, const int *Wm, const int *Hm)
 {
-    if (!h || !h->A) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
     const int k = (int)k_;
     if (k < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: rank k must be >= 1");
     HIPCHK(h, hipSetDevice(h->device));
@@ -962,12 +1127,26 @@ extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, co
             HIPCHK(h, hipMalloc(&h->H16c, (size_t)h->mpad * 64 * 4 + 4096));
         }
         h->Cx_elems = eh > ew ? eh : ew;
+        const size_t big = (size_t)(h->npad > h->mpad ? h->npad : h->mpad);
+        if (h->sparse) h->Cx_elems = (size_t)h->KP * big; // (one slab: the SpMM has no split-K)
         HIPCHK(h, hipMalloc(&h->Cx, h->Cx_elems * 8));
         HIPCHK(h, hipMemset(h->Cx, 0, h->Cx_elems * 8)); // rows >= k of a slab are never written: keep them finite
         const int gb = (h->npad > h->mpad ? h->npad : h->mpad) / GRAM_COLS_PER_BLOCK + 1;
         HIPCHK(h, hipMalloc(&h->gslabs, (size_t)gb * h->KP * h->KP * 8));
-        HIPCHK(h, hipMalloc(&h->red, ((size_t)h->KP * h->KP + (size_t)h->KP * (h->npad > h->mpad ? h->npad : h->mpad)) * 8));
+        // (a sparse handle uses the head only: Graw; the [G | C] buffer of the multi-GPU all-reduce is dense-only)
+        HIPCHK(h, hipMalloc(&h->red, ((size_t)h->KP * h->KP + (h->sparse ? 0 : (size_t)h->KP * big)) * 8));
         h->Graw = h->red;
+        if (h->sparse) { // row copy of the fixed factor, SpMM carries, error block workspaces (k_sparse.h)
+            const int KP = h->KP;
+            HIPCHK(h, hipMalloc(&h->sp_Y, big * KP * es + 4096));
+            HIPCHK(h, hipMalloc(&h->sp_carry, (size_t)nnlm_sp_workers(h->nnz, KP, h->cus_device) * 64 * 8));
+            HIPCHK(h, hipMalloc(&h->sp_Wrow, (size_t)h->npad * KP * 8));
+            HIPCHK(h, hipMalloc(&h->sp_eslabs, (size_t)gb * KP * KP * 8));
+            HIPCHK(h, hipMalloc(&h->sp_eG, ((size_t)2 * KP * KP + 2 * KP + 8) * 8));
+            const size_t eb = (size_t)(nnlm_sp_workers(h->nnz, KP, h->cus_device) / (64 / nnlm_sp_lanes(KP)) + 3) / 4;
+            const size_t rb = (big + 2047) / 2048;
+            HIPCHK(h, hipMalloc(&h->sp_epart, (3 * eb > KP * rb ? 3 * eb : KP * rb) * 8 + 64));
+        }
     }
     h->wcur = 0;
     h->W64 = h->W64b[0];
@@ -1988,12 +2167,55 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
 }
 
 static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int fused_nb, bool need_pen);
+
+// Square-loss half-step on a sparse A (k_sparse.h): the Gram of the fixed factor (launch_gram), a row copy of the fixed factor and the
+// SpMM -- W^T A over the CSC for the H half-step, A H^T over the CSR for the W half-step -- into ONE slab of Cx, then the solvers of the
+// dense path unchanged (half_step_solve).  Rank > 64: one SpMM launch per 64 coordinates, the generic Gram and sweep.
+static int half_step_sparse(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
+{
+    if (method >= 3)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
+    const double *Ym = (which == 1) ? h->W64 : h->H64;
+    const int ldm = (which == 1) ? h->npad : h->mpad, p = (which == 1) ? h->n : h->m;
+    {
+        ProfScope ps(h, P_GRAM, h->stream);
+        int nsl = 0;
+        launch_gram(h, Ym, ldm, 0, p, &nsl);
+    }
+    {
+        ProfScope ps(h, which == 1 ? P_SPMM_H : P_SPMM_W);
+        const bool f64 = h->prec == NNLM_PREC_F64;
+        if (f64) factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(Ym, ldm, p, h->KP, (double *)h->sp_Y);
+        else factor_rows_kernel<float><<<(p + 255) / 256, 256, 0, h->stream>>>(Ym, ldm, p, h->KP, (float *)h->sp_Y);
+        SpmmArgs a;
+        a.ptr = (which == 1) ? h->sp_cptr : h->sp_rptr;
+        a.idx = (which == 1) ? h->sp_ridx : h->sp_cidx;
+        a.val = (which == 1) ? h->sp_cval : h->sp_rval;
+        a.Y = h->sp_Y;
+        a.nnz = h->nnz;
+        a.ncols = (which == 1) ? h->m : h->n;
+        a.KP = h->KP;
+        a.nworkers = nnlm_sp_workers(h->nnz, h->KP, h->cus_device);
+        a.chunk = (h->nnz + a.nworkers - 1) / a.nworkers;
+        if (a.chunk < 1) a.chunk = 1;
+        a.C = h->Cx;
+        a.ldc = (which == 1) ? h->mpad : h->npad;
+        a.carry = h->sp_carry;
+        for (int q0 = 0; q0 < h->KP; q0 += 64) {
+            a.q0 = q0;
+            nnlm_tu_spmm(a, f64, h->stream);
+        }
+    }
+    if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
+    return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, 1, speculative, PH_ALL, false);
+}
+
 // speculative (W half-step only): the result goes to the alternate W buffers and the alternate sweep counter and is
 // NOT made current; the caller accepts it later with swap_w() / sw_active ^= 1, or simply drops it.
 static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
                      bool partial_only = false, bool speculative = false, int phase = PH_ALL)
 {
-    if (!h || !h->A || !h->W64) return fail(h, NNLM_ERR_ARG, "half_step: matrix and factors must be set first");
+    if (!has_matrix(h) || !h->W64) return fail(h, NNLM_ERR_ARG, "half_step: matrix and factors must be set first");
     if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
     HIPCHK(h, hipSetDevice(h->device));
     g_attr_err = hipSuccess; // (a refusal latched by an earlier call on this thread that returned before its LAUNCHCHK is not this call's)
@@ -2002,6 +2224,7 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     h->sg_prev = sg_which;
     h->sg_which = h->sg_other = -1;
     h->sg_request = false;
+    if (h->sparse) return half_step_sparse(h, which, reg, inner_max_iter, inner_rel_tol, method, speculative);
     if (generic_rank(h) && h->sharded && method < 3 && !h->any_missing && !h->dense_cols)
         return fail(h, NNLM_ERR_UNSUPPORTED, "rank > %d across GPUs: only the column-sharded form (nnlm_comm_set_form(h, NNLM_FORM_COLS))", NNLM_KQ_MAX);
     if (partial_only) phase = PH_A;
@@ -2420,6 +2643,7 @@ extern "C" int nnlm_half_step(nnlm_handle *h, int which, const double reg[3], un
 extern "C" int nnlm_debug_partial(nnlm_handle *h, int which, double *G_out, double *C_out)
 {
     if (!h || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_debug_partial: matrix and factors must be set first");
+    if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_debug_partial: the handle holds a sparse matrix (the hook reads the dense split-K slabs)");
     if (which != 0 && which != 1) return fail(h, NNLM_ERR_ARG, "nnlm_debug_partial: which must be 0 or 1");
     const double z[3] = {0, 0, 0};
     // sharded handles return right after the slab fold; a 1-rank handle runs a zero-sweep solve (a no-op on the
@@ -2548,6 +2772,40 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
             ncclResult_t r = g_rccl.AllReduce(h->scal, h->scal, 2, ncclDouble, ncclSum, (ncclComm_t)h->comm, st);
             if (r != ncclSuccess) return fail(h, NNLM_ERR_COMM, "ncclAllReduce (fused error sums) failed");
         }
+    } else if (h->sparse) {
+        // Sparse A: sums over the non-zeros (sp_errors_kernel), then the zeros' share from the Grams -- sum over all entries of (WH)^2 =
+        // <W^T W, H H^T> -- and the sum of all entries of WH from the factors' sums (sp_err_final_kernel).  All reductions fp64, fixed order.
+        ProfScope ps(h, P_SP_ERRORS, st);
+        const int KP = h->KP, n = h->n, m = h->m;
+        double *G = h->sp_eG, *sums = G + (size_t)2 * KP * KP, *S = sums + 2 * KP;
+        factor_rows_kernel<double><<<(n + 255) / 256, 256, 0, st>>>(h->W64, h->npad, n, KP, h->sp_Wrow);
+        for (int f = 0; f < 2; f++) {
+            const double *X = f == 0 ? h->W64 : h->H64;
+            const int ld = f == 0 ? h->npad : h->mpad, cols = f == 0 ? n : m;
+            const int nb = (cols + GRAM_COLS_PER_BLOCK - 1) / GRAM_COLS_PER_BLOCK;
+            if (generic_rank(h)) {
+                dim3 grid(nb, h->NKQ * (h->NKQ + 1) / 2);
+                gram_partial_generic_kernel<<<grid, 256, 0, st>>>(X, ld, 0, cols, h->NKQ, h->sp_eslabs);
+            } else
+                switch (h->NKQ) {
+                case 1: gram_partial_kernel<1><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
+                case 2: gram_partial_kernel<2><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
+                case 3: gram_partial_kernel<3><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
+                default: gram_partial_kernel<4><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
+                }
+            gram_reduce_kernel<<<(KP * KP + 255) / 256, 256, 0, st>>>(h->sp_eslabs, nb, KP, G + (size_t)f * KP * KP);
+            const int rb = (cols + 2047) / 2048;
+            nnlm_tu_sp_rowsums(X, ld, cols, KP, h->sp_epart, rb, st);
+            reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)rb, KP, sums + (size_t)f * KP);
+        }
+        const int nw = nnlm_sp_workers(h->nnz, KP, h->cus_device);
+        long long chunk = (h->nnz + nw - 1) / nw;
+        if (chunk < 1) chunk = 1;
+        const int eb = (nw / (64 / nnlm_sp_lanes(KP)) + 3) / 4;
+        nnlm_tu_sp_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, chunk, nw, h->sp_Wrow, KP, h->k, h->H64, h->mpad,
+                          h->sp_epart, eb, st);
+        reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)eb, 3, S);
+        nnlm_tu_sp_err_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->scal, st);
     } else {
         ProfScope ps(h, P_ERRORS, st);
         const uint32_t *miss = h->any_missing ? h->miss : nullptr;
@@ -2653,7 +2911,7 @@ static int errors_collect(nnlm_handle *h, double *mse, double *mkl_var, double p
 
 extern "C" int nnlm_errors(nnlm_handle *h, double *mse, double *mkl_var, double pen[6])
 {
-    if (!h || !h->A || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_errors: matrix and factors must be set first");
+    if (!has_matrix(h) || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_errors: matrix and factors must be set first");
     HIPCHK(h, hipSetDevice(h->device));
     int rc = errors_launch(h, h->stream, false, 0, true);
     if (rc != NNLM_OK) return rc;
@@ -2715,6 +2973,7 @@ extern "C" int nnlm_comm_init(nnlm_handle *h, const char id[NNLM_COMM_ID_BYTES],
 {
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_comm_init: handle is NULL");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, NNLM_ERR_ARG, "nnlm_comm_init: bad rank %d of %d", rank, nranks);
+    if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a sparse matrix; the sparse path is single-GPU only");
     HIPCHK(h, hipSetDevice(h->device));
     if (h->comm) {
         g_rccl.CommDestroy((ncclComm_t)h->comm);
@@ -2762,6 +3021,8 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sweep_groups_h") == 0) *value = h->sweep_groups[1];
     else if (strcmp(key, "kl_form_w") == 0) *value = h->kl_form[0];
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
+    else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
+    else if (strcmp(key, "matrix_bytes") == 0) *value = matrix_bytes(h);
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
 }
@@ -2876,10 +3137,12 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                         double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
                         unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
 {
-    if (!h || !h->A || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_run: matrix and factors must be set first");
+    if (!has_matrix(h) || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_run: matrix and factors must be set first");
     if (!alpha || !beta || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace || !n_iteration || !warned)
         return fail(h, NNLM_ERR_ARG, "nnlm_run: NULL argument");
     if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
+    if (h->sparse && method >= 3)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     HIPCHK(h, hipSetDevice(h->device));
     int rc;
 #define CHK(x)                  \
@@ -3022,18 +3285,14 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
     return NNLM_OK;
 }
 
-extern "C" int nnlm_c_nnmf(const double *A, int n, int m, unsigned k, const double *W_init, const double *H_init, const int *Wm,
-                           const int *Hm, const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol,
-                           int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
-                           int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
-                           double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
-                           const nnlm_callbacks *cb)
+// The one-shot entries share these bodies; the dense and the sparse entries differ only in how the matrix is set (set_matrix(h)).
+template <typename SetMatrix>
+static int c_nnmf_body(SetMatrix set_matrix, int n, int m, unsigned k, const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                       const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int verbose, int show_warning,
+                       unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out, double *H_out, double *mse_error,
+                       double *mkl_error, double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                       const nnlm_callbacks *cb)
 {
-    (void)n_threads;
-    if (!A || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
-        !n_iteration || !warned)
-        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: NULL argument");
-    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: k must be >= 1");
     nnlm_handle *h = nullptr;
     int rc = nnlm_create(&h, env_device(), env_precision());
     if (rc != NNLM_OK) return rc;
@@ -3041,7 +3300,7 @@ extern "C" int nnlm_c_nnmf(const double *A, int n, int m, unsigned k, const doub
         nnlm_handle *h;
         ~Guard() { nnlm_destroy(h); }
     } guard{h};
-    CHK(nnlm_set_matrix(h, A, n, m));
+    CHK(set_matrix(h));
 
     // default init, src/nnmf.cpp:82-98: W.randu(k,n)*0.01 drawn column-major, W first, masked entries zeroed
     std::vector<double> Wi, Hi;
@@ -3073,13 +3332,44 @@ extern "C" int nnlm_c_nnmf(const double *A, int n, int m, unsigned k, const doub
     return NNLM_OK;
 }
 
-extern "C" int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q, const double alpha[3], const int *mask,
-                           const double *beta0, unsigned max_iter, double rel_tol, int n_threads, int method, double *coefficient,
-                           int *n_iteration, const nnlm_callbacks *cb)
+extern "C" int nnlm_c_nnmf(const double *A, int n, int m, unsigned k, const double *W_init, const double *H_init, const int *Wm,
+                           const int *Hm, const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol,
+                           int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                           int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                           double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                           const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!x || !y || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: NULL argument");
-    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: empty x or y");
+    if (!A || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
+        !n_iteration || !warned)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: NULL argument");
+    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: k must be >= 1");
+    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix(h, A, n, m); }, n, m, k, W_init, H_init, Wm, Hm, alpha, beta, max_iter,
+                       rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out, mse_error, mkl_error,
+                       target_error, average_epoch, n_trace, n_iteration, warned, cb);
+}
+
+extern "C" int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
+                               const double *H_init, const int *Wm, const int *Hm, const double alpha[3], const double beta[3], unsigned max_iter,
+                               double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                               int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                               double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                               const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!colptr || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
+        !n_iteration || !warned)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc: NULL argument");
+    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc: k must be >= 1");
+    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, m, colptr, rowidx, x); }, n, m, k, W_init, H_init, Wm, Hm, alpha,
+                       beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+}
+
+template <typename SetMatrix>
+static int c_nnlm_body(SetMatrix set_matrix, const double *x, int n, int p, int q, const double alpha[3], const int *mask, const double *beta0,
+                       unsigned max_iter, double rel_tol, int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
+{
     nnlm_handle *h = nullptr;
     int rc = nnlm_create(&h, env_device(), env_precision());
     if (rc != NNLM_OK) return rc;
@@ -3088,7 +3378,7 @@ extern "C" int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q
         ~Guard() { nnlm_destroy(h); }
     } guard{h};
     // y plays A (n x q), x plays W (n x p), beta plays H (p x q): one H half-step, src/nnlm.cpp:44-47
-    CHK(nnlm_set_matrix(h, y, n, q));
+    CHK(set_matrix(h));
     std::vector<double> b0;
     if (!beta0) { // beta.randu(), src/nnlm.cpp:38-39
         b0.resize((size_t)p * q);
@@ -3103,5 +3393,27 @@ extern "C" int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q
     *n_iteration = (int)raw;
     CHK(nnlm_get_factors(h, nullptr, coefficient));
     return NNLM_OK;
-#undef CHK
 }
+
+extern "C" int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q, const double alpha[3], const int *mask,
+                           const double *beta0, unsigned max_iter, double rel_tol, int n_threads, int method, double *coefficient,
+                           int *n_iteration, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!x || !y || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: NULL argument");
+    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: empty x or y");
+    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix(h, y, n, q); }, x, n, p, q, alpha, mask, beta0, max_iter, rel_tol, method,
+                       coefficient, n_iteration, cb);
+}
+
+extern "C" int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                               const double alpha[3], const int *mask, const double *beta0, unsigned max_iter, double rel_tol, int n_threads,
+                               int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!x || !ycolptr || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc: NULL argument");
+    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc: empty x or y");
+    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, q, ycolptr, yrowidx, yx); }, x, n, p, q, alpha, mask, beta0,
+                       max_iter, rel_tol, method, coefficient, n_iteration, cb);
+}
+#undef CHK

@@ -1,0 +1,68 @@
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h), see tu_sweepq.h.
+#include "tu_sweepq.h"
+#include "k_sparse.h"
+
+// Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
+// launched once per 64 coordinates)
+int nnlm_sp_lanes(int KP) { return KP == 16 ? 16 : (KP == 32 ? 32 : 64); }
+
+// At least ~64 non-zeros per worker (the binary search that finds a worker's first column is then a small part of its time), at most
+// 16 wavefronts per CU (four per SIMD: enough gathers in flight to cover the latency of the Infinity Cache)
+int nnlm_sp_workers(long long nnz, int KP, int cus)
+{
+    const int ng = 64 / nnlm_sp_lanes(KP);
+    long long waves = (nnz + 64LL * ng - 1) / (64LL * ng);
+    const long long cap = 16LL * (cus > 0 ? cus : 256);
+    if (waves > cap) waves = cap;
+    if (waves < 1) waves = 1;
+    return (int)waves * ng;
+}
+
+template <typename T, int LW> static void launch_spmm(const SpmmArgs &a, hipStream_t st)
+{
+    const int waves = a.nworkers / (64 / LW);
+    spmm_kernel<T, LW><<<(waves + 3) / 4, 256, 0, st>>>(a);
+    spmm_fixup_kernel<<<(a.nworkers + 3) / 4, 256, 0, st>>>(a);
+}
+template <typename T> static void launch_spmm_t(const SpmmArgs &a, hipStream_t st)
+{
+    switch (nnlm_sp_lanes(a.KP)) {
+    case 16: launch_spmm<T, 16>(a, st); break;
+    case 32: launch_spmm<T, 32>(a, st); break;
+    default: launch_spmm<T, 64>(a, st); break;
+    }
+}
+void nnlm_tu_spmm(const SpmmArgs &a, bool f64, hipStream_t st)
+{
+    if (f64) launch_spmm_t<double>(a, st);
+    else launch_spmm_t<float>(a, st);
+}
+
+template <typename T>
+static void launch_sp_errors_t(const long long *ptr, const int *idx, const void *val, int ncols, long long nnz, long long chunk, int nworkers,
+                               const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st)
+{
+    const T *v = (const T *)val;
+    switch (nnlm_sp_lanes(KP)) {
+    case 16: sp_errors_kernel<T, 16><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    case 32: sp_errors_kernel<T, 32><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    default: sp_errors_kernel<T, 64><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    }
+}
+// nblocks = workgroups of four wavefronts covering the nworkers workers (the caller sizes `partial` from it: 3 doubles per workgroup)
+void nnlm_tu_sp_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nworkers,
+                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st)
+{
+    if (f64) launch_sp_errors_t<double>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    else launch_sp_errors_t<float>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+}
+
+void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *partial, int nblocks, hipStream_t st)
+{
+    sp_rowsum_partial_kernel<<<nblocks, 256, 0, st>>>(X, ld, ncols, KP, partial);
+}
+void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP, double *out,
+                          hipStream_t st)
+{
+    sp_err_final_kernel<<<1, 256, 0, st>>>(s, GW, GH, wsum, hsum, k, KP, out);
+}

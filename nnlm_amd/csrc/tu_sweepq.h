@@ -16,3 +16,29 @@ void nnlm_tu_colsolve_row(const SweepArgs &a, size_t g_stride, hipStream_t st);
 // fp32-operand mode, row form (k_sweep_r.h, tu_sweepr.hip): nb workgroups of NW = 4 or 8 wavefronts of FOUR columns; a.k <= SWEEPR_KMAX; reads a.Graw
 #define SWEEPR_KMAX 50
 void nnlm_tu_sweep_r(const SweepArgs &a, int nb, int NW, hipStream_t st);
+
+// Sparse A (k_sparse.h, tu_sparse.hip): the cross product of a half-step as an SpMM over the non-zeros, and the error sums over them
+struct SpmmArgs {
+    const long long *ptr; // [ncols + 1]
+    const int *idx;       // [nnz] contraction index (row of A for CSC, column for CSR)
+    const void *val;      // [nnz] T
+    const void *Y;        // [rows][KP] T, row-major fixed factor
+    long long nnz, chunk; // non-zeros per worker
+    int ncols, KP, q0;    // columns of the output; coordinates q0 .. q0 + 63 (rank > 64: one launch per 64 coordinates)
+    int nworkers;
+    double *C;            // C[q * ldc + c]
+    int ldc;
+    double *carry;        // [nworkers][64]
+};
+// launch entries (tu_sparse.hip); f64 selects T = double, else float
+void nnlm_tu_spmm(const SpmmArgs &a, bool f64, hipStream_t st);
+void nnlm_tu_sp_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nworkers,
+                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st);
+// workers of one launch: a multiple of the workers per wavefront; nnz / workers non-zeros each, at least ~64, at most 16 wavefronts per CU
+int nnlm_sp_workers(long long nnz, int KP, int cus);
+int nnlm_sp_lanes(int KP);
+// partial[b][q] = sum of X[q][c] (X [KP][ld] fp64) over columns [2048 b, 2048 (b + 1)) of ncols
+void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *partial, int nblocks, hipStream_t st);
+// out[0] = sum of squares, out[1] = KL sum over all n x m entries from s = {S1, S2, S3}, the Grams and the factors' sums (k_sparse.h)
+void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP, double *out,
+                          hipStream_t st);
