@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256) void colsolve_ls_kernel(const SweepArgs a, siz
             const int q = 8 * c + e;
             double v = 0.0;
             if (q < k && lv) {
-                v = G[(a.g_upper && q > lane) ? (size_t)lane * a.KPg + q : (size_t)q * a.KPg + lane];
+                v = G[q > lane ? (size_t)lane * a.KPg + q : (size_t)q * a.KPg + lane];
                 if (q == lane && a.r0 != a.r1) v += a.r0 - a.r1; // :98-99
                 if (a.r1 != 0) v += a.r1;                          // :100-101
                 if (q == lane) v += NNLM_TINY;                     // :103
@@ -239,7 +239,7 @@ __device__ static inline double na_fma(double a, double b, double c) { return __
 template <typename T, int NT, bool TAIL>
 __global__ __launch_bounds__(256) void na_gram_lds_kernel(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ meta, const int *__restrict__ idx,
                                                           const T *__restrict__ Yrow, const double *__restrict__ Gfull, double *__restrict__ Gcols,
-                                                          int ncols, int col0, int k, int upper_only)
+                                                          int ncols, int col0, int k)
 {
     using M = Mfma<T>;
     using acc_t = typename M::acc_t;
@@ -400,10 +400,10 @@ __global__ __launch_bounds__(256) void na_gram_lds_kernel(const uint32_t *__rest
         }
     }
     double *out = Gcols + (size_t)col * KP * KP;
-    auto put = [&](int i, int j, double sum) { // both triangles, or (upper_only: the solvers read G[min][max]) the upper one
+    auto put = [&](int i, int j, double sum) { // upper triangle: G[min][max]
         const double v = complement ? Gfull[i * KP + j] - sum : sum;
-        if (!upper_only || i <= j) out[i * KP + j] = v;
-        if (i != j && (!upper_only || j < i)) out[j * KP + i] = v;
+        if (i <= j) out[i * KP + j] = v;
+        else out[j * KP + i] = v;
     };
     int pi = 0;
 #pragma unroll
@@ -416,10 +416,7 @@ __global__ __launch_bounds__(256) void na_gram_lds_kernel(const uint32_t *__rest
                 double sum = (double)acc[pi][r];
                 if (F32) sum += acc64[F32 ? pi : 0][r];
                 const double v = complement ? Gfull[i * KP + j] - sum : sum;
-                if ((TAIL || (i < k && j < k)) && !(upper_only && i > j)) { // (entries beyond k are never read by the solvers)
-                    out[i * KP + j] = v;
-                    if (a != b && !upper_only) out[j * KP + i] = v;
-                }
+                if ((TAIL || (i < k && j < k)) && i <= j) out[i * KP + j] = v; // (entries beyond k are never read by the solvers)
             }
     if (TAIL) {
         // tail rows: add the four lane groups (each summed its own row of every group of four); lane group 0 stores row C0, lane
@@ -474,7 +471,7 @@ typedef _Float16 gh4 __attribute__((ext_vector_type(4)));
 template <int NKQ>
 __global__ __launch_bounds__(256) void na_gram_f16_kernel(const uint32_t *__restrict__ ptr, const uint32_t *__restrict__ meta, const int *__restrict__ idx,
                                                           const uint32_t *__restrict__ Y16rows, int zero_row, const int *__restrict__ exp_in,
-                                                          const double *__restrict__ Gfull, double *__restrict__ Gcols, int ncols, int col0, int k, int upper_only)
+                                                          const double *__restrict__ Gfull, double *__restrict__ Gcols, int ncols, int col0, int k)
 {
     constexpr int KP = 16 * NKQ;          // row stride of Gfull / Gcols
     constexpr int NP = NKQ * (NKQ + 1) / 2;
@@ -601,16 +598,13 @@ __global__ __launch_bounds__(256) void na_gram_f16_kernel(const uint32_t *__rest
                 const double sum = (acc64[pi][r] + (double)accm[pi][r] + (double)accx[pi][r] * (1.0 / 2048.0)) * unscale;
                 v4[r] = complement ? Gfull[(i0 + r) * KP + j] - sum : sum;
             }
-            // upper_only (the one-column-per-wavefront solvers read G[min][max]): nothing below the diagonal is written.  Otherwise
-            // (colsolve_row_kernel reads whole rows) the mirrored tile goes out as ONE 32-byte store per lane -- the lane's four rows i are
-            // four consecutive entries of row j, the four lane groups fill a 128-byte line -- not as four 8-byte stores 512 bytes apart
-            // (those were 2.4 % of a config-5 iteration).  Entries beyond k are never read by the solvers (the buffer has KP x KP of them).
+            // upper triangle only (the solvers read G[min][max]): nothing below the diagonal is written.  Entries beyond k are never
+            // read by the solvers (the buffer has KP x KP of them).
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const int i = i0 + r;
-                if (i < k && j < k && !(upper_only && i > j)) out[i * KP + j] = v4[r];
+                if (i < k && j < k && i <= j) out[i * KP + j] = v4[r];
             }
-            if (a != b && !upper_only && j < k) *(f64x4 *)(out + j * KP + i0) = v4;
         }
 }
 
@@ -650,7 +644,7 @@ __global__ __launch_bounds__(256) void colsolve_strict_kernel(const SweepArgs a,
     for (int q = 0; q < KR; q++) {
         double v = 0.0;
         if (q < k && lv) {
-            v = G[(a.g_upper && q > lane) ? (size_t)lane * a.KPg + q : (size_t)q * a.KPg + lane];
+            v = G[q > lane ? (size_t)lane * a.KPg + q : (size_t)q * a.KPg + lane];
             if (q == lane && a.r0 != a.r1) v += a.r0 - a.r1;
             if (a.r1 != 0) v += a.r1;
             if (q == lane) v += NNLM_TINY;

@@ -35,6 +35,7 @@
 #include <string>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 static thread_local std::string g_last_error;
@@ -114,7 +115,9 @@ struct nnlm_handle {
     uint32_t *na_ptr[2] = {nullptr, nullptr}, *na_meta[2] = {nullptr, nullptr};
     int *na_idx[2] = {nullptr, nullptr};
     double *Yrow = nullptr;              // [max(npad,mpad)][KP] row-major copy of the fixed factor (NA path)
-    double *Gcols = nullptr;             // [max(n,m)][KP][KP] per-column Grams (NA path)
+    double *Gcols = nullptr;             // [max(n,m)][KP][KP] per-column Grams (NA path): upper triangle only at rank <= 64 (na_gram_f16 /
+                                         // na_gram_lds write it, the colsolve kernels read G[min][max]); the full matrix for the generic
+                                         // rank > 64 kernels (na_gram_generic_kernel, sweep_generic_kernel)
     double *partials = nullptr;
     size_t partials_elems = 0;
     double *scal = nullptr;              // 16 doubles of reduction results
@@ -1037,24 +1040,73 @@ struct HalfPlan {
     int col_off = 0; // first column of the factor being solved that this launch covers (column shards of the multi-GPU NA path)
 };
 
-// which = 1: H half-step (contraction over i, A as stored); which = 0: W half-step (contraction over j: the same "TN" kernels on
-// the transposed copy of A -- A16T in the split-fp16 mode, AT otherwise -- made once per matrix; the reference transposes A in
-// EVERY iteration, src/nnmf.cpp:131)
+// What the orientation of half-step `which` decides.  which = 1: the H half-step, contraction over the rows i of A (A as stored), W
+// fixed; which = 0: the W half-step, contraction over the columns j -- the same "TN" kernels on the transposed copy of A (A16T in the
+// split-fp16 mode, AT otherwise), made once per matrix; the reference transposes A in EVERY iteration, src/nnmf.cpp:131.  H fixed.
+// The view holds no pointer that changes inside a half-step: AT is made on first use (a_contig) and the W buffers flip in swap_w.
+struct Side {
+    int which;
+    const double *Y;          // master of the fixed factor [KP][ldy]
+    int ldy, p;               // contraction length: padded (= ld of the fixed factor) and true
+    int ncols, ldc;           // columns solved: true and padded (= ld of the solved factor and of the Cx slabs)
+    size_t slab_stride;       // KP * ldc
+    const double *X;          // master of the factor solved
+    double *Xout;             // where the half-step writes it: H in place, W into the alternate buffer W64b[wcur ^ 1]
+    void *op;                 // GEMM-operand copy written next to it (SweepArgs::op): W only
+    int op_mode, op_ld;
+    const unsigned long long *mask;
+    const uint32_t *bits;     // missing-value bits of each solved column over the contraction (miss / missT), NULL without missing values
+    int words;                // 32-bit words of `bits` per column
+    const uint32_t *A16;      // split-fp16 copy of A, contraction contiguous (A16 / A16T)
+    const long long *sp_ptr;  // sparse A: CSC (H half-step) or CSR (W half-step)
+    const int *sp_idx;
+    const void *sp_val;
+    int prof_xprod, prof_sweep, prof_spmm;
+};
+
+static Side side_of(const nnlm_handle *h, int which)
+{
+    Side s;
+    s.which = which;
+    if (which == 1) {
+        s.Y = h->W64; s.ldy = h->npad; s.p = h->n;
+        s.ncols = h->m; s.ldc = h->mpad;
+        s.X = s.Xout = h->H64;
+        s.op = nullptr; s.op_mode = 0; s.op_ld = 0; // (H has no GEMM-operand copy: every consumer reads the master or makes its own split / fp32 copy)
+        s.mask = h->has_hmask ? h->Hmask : nullptr;
+        s.bits = h->miss;
+        s.A16 = h->A16;
+        s.sp_ptr = h->sp_cptr; s.sp_idx = h->sp_ridx; s.sp_val = h->sp_cval;
+        s.prof_xprod = P_XPROD_H; s.prof_sweep = P_SWEEP_H; s.prof_spmm = P_SPMM_H;
+    } else {
+        s.Y = h->H64; s.ldy = h->mpad; s.p = h->m;
+        s.ncols = h->n; s.ldc = h->npad;
+        s.X = h->W64; s.Xout = h->W64b[h->wcur ^ 1];
+        s.op = h->Wopb[h->wcur ^ 1]; s.op_mode = (h->prec == NNLM_PREC_F64) ? 0 : 1; s.op_ld = h->npad;
+        s.mask = h->has_wmask ? h->Wmask : nullptr;
+        s.bits = h->missT;
+        s.A16 = h->A16T;
+        s.sp_ptr = h->sp_rptr; s.sp_idx = h->sp_cidx; s.sp_val = h->sp_rval;
+        s.prof_xprod = h->fuse_err ? P_XPROD_W_ERR : P_XPROD_W; s.prof_sweep = P_SWEEP_W; s.prof_spmm = P_SPMM_W;
+    }
+    if (!h->any_missing) s.bits = nullptr;
+    s.words = s.ldy / 32;
+    s.slab_stride = (size_t)h->KP * s.ldc;
+    return s;
+}
+
+// A with the contraction contiguous, [ncols][ldy] in the mode's element type (the W half-step's copy AT: ensure_AT first)
+static const void *a_contig(const nnlm_handle *h, const Side &s) { return s.which == 1 ? h->A : h->AT; }
+
+// contraction elements one stage of a cross product covers (the granularity of the multi-GPU split): 256 bytes of A in the mode's type
+// (the split-fp16 kernels' stages of 64 elements are the same in the fp32-operand mode, the only mode that has them)
+static int stage_elems(const nnlm_handle *h) { return XPROD_ROWB / (int)esize(h); }
+
 static HalfPlan plan_half(const nnlm_handle *h, int which, int rank, int nranks)
 {
+    const Side s = side_of(h, which);
     HalfPlan p;
-    int stages_total, tiles_x;
-    if (which == 1) {
-        const int CE = XPROD_ROWB / (int)esize(h);
-        stages_total = h->npad / CE;
-        tiles_x = h->mpad / XPROD_TN_BJ;
-    } else if (h->x16) { // split-fp16: the TN kernel on the transposed copy, tiles of 128 rows of A, stages of 64 columns
-        stages_total = h->mpad / 64;
-        tiles_x = h->npad / XPROD_TN_BJ;
-    } else { // strict mode (and rank > 64 without split copies): the TN kernel on the transposed copy AT
-        stages_total = h->mpad / (XPROD_ROWB / (int)esize(h));
-        tiles_x = h->npad / XPROD_TN_BJ;
-    }
+    const int stages_total = s.ldy / stage_elems(h), tiles_x = s.ldc / XPROD_TN_BJ;
     // this rank's slab of the contraction
     const int per_rank = (stages_total + nranks - 1) / nranks;
     p.stage_begin = rank * per_rank;
@@ -1066,14 +1118,6 @@ static HalfPlan plan_half(const nnlm_handle *h, int which, int rank, int nranks)
     split_plan(tiles_x, len, &p.S, &p.sps);
     p.tiles_x = tiles_x;
     return p;
-}
-
-// contraction elements one stage of the cross product of half-step `which` covers (the granularity of the multi-GPU split)
-static int stage_elems(const nnlm_handle *h, int which)
-{
-    if (which == 1) return XPROD_ROWB / (int)esize(h);
-    if (h->x16) return 64;
-    return XPROD_ROWB / (int)esize(h);
 }
 
 static void pack_mask_cols(const int *mask, int k, int ncols, bool transposed_input, int ld_in, std::vector<unsigned long long> &out, int npadded,
@@ -1207,62 +1251,60 @@ extern "C" int nnlm_get_factors(nnlm_handle *h, double *W, double *H)
 // ---------------------------------------------------------------------------------------------
 // half-step
 // ---------------------------------------------------------------------------------------------
-template <typename T, int NKQ, int KT>
-static void launch_xprod(nnlm_handle *h, int which, const HalfPlan &p)
+// Calls f(std::integral_constant<int, N>{}) for the number N of 16-row blocks of a factor a kernel instantiation covers: nkq = 1, 2, 3
+// as they are; anything >= 4 -> 4 (rank <= 64, or one 64-row slice of the rank > 64 loops)
+template <typename F>
+static void with_nkq(int nkq, F &&f)
 {
-    const int KP = 16 * (NKQ + (KT > 0 ? 1 : 0)); // = h->KP
-    dim3 grid(p.tiles_x, p.S);
-    const int lds = xprod_tn_lds_bytes(KP);
-    set_dyn_lds((const void *)xprod_tn_kernel<T, NKQ, KT>, lds, "xprod_tn_kernel");
-    if (which == 1)
-        xprod_tn_kernel<T, NKQ, KT><<<grid, XPROD_THREADS, lds, h->stream>>>((const T *)h->A + (size_t)p.col_off * h->npad, h->npad, (const T *)h->Wop,
-                                                                              h->npad, h->Cx + p.col_off, h->mpad, (size_t)KP * h->mpad, p.stage_begin,
-                                                                              p.stage_end, p.sps);
-    else // roles swapped on the transposed copy (ensure_AT ran): rows of A are the columns solved, H (master, [KP][mpad]) the fixed factor
-        xprod_tn_kernel<T, NKQ, KT><<<grid, XPROD_THREADS, lds, h->stream>>>((const T *)h->AT + (size_t)p.col_off * h->mpad, h->mpad, (const T *)h->H64,
-                                                                              h->mpad, h->Cx + p.col_off, h->npad, (size_t)KP * h->npad, p.stage_begin,
-                                                                              p.stage_end, p.sps);
+    switch (nkq) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
 }
 
-// MFMA tiles / VALU tail rows for rank k: k = 16*NKQ + rem; a remainder of 1..4 rows (with at least one full tile) is
-// not padded to a whole 16-wide MFMA tile but handled as 2 or 4 tail rows (k_xprod.h).
-template <typename T>
-static void launch_xprod_nkq(nnlm_handle *h, int which, const HalfPlan &p)
+// xprod_tn_kernel (k_xprod.h) over rows [0, 16 NKQ (+ KT tail rows)) of the fixed factor Y into the slabs at C (the rank > 64 loops:
+// one launch per 64 rows of Y and C)
+template <typename T, int NKQ, int KT = 0>
+static void launch_xprod_tn(nnlm_handle *h, const T *Amat, int lda, const T *Y, int ldy, double *C, int ldc, size_t slab_stride, const HalfPlan &p)
 {
+    dim3 grid(p.tiles_x, p.S);
+    const int lds = xprod_tn_lds_bytes(16 * (NKQ + (KT > 0 ? 1 : 0)));
+    set_dyn_lds((const void *)xprod_tn_kernel<T, NKQ, KT>, lds, "xprod_tn_kernel");
+    xprod_tn_kernel<T, NKQ, KT><<<grid, XPROD_THREADS, lds, h->stream>>>(Amat + (size_t)p.col_off * lda, lda, Y, ldy, C + p.col_off, ldc, slab_stride,
+                                                                          p.stage_begin, p.stage_end, p.sps);
+}
+
+// Strict mode, rank <= 64 (the masters are the operands: Wop aliases W64).  MFMA tiles / VALU tail rows for rank k: k = 16*NKQ + rem;
+// a remainder of 1..4 rows (with at least one full tile) is not padded to a whole 16-wide MFMA tile but handled as 2 or 4 tail rows (k_xprod.h).
+static void launch_xprod_nkq(nnlm_handle *h, const Side &s, const HalfPlan &p)
+{
+    const double *Amat = (const double *)a_contig(h, s);
+    auto go = [&](auto nkq, auto kt) { launch_xprod_tn<double, nkq, kt>(h, Amat, s.ldy, s.Y, s.ldy, h->Cx, s.ldc, s.slab_stride, p); };
     const int full = h->k / 16, rem = h->k % 16;
-    if (full >= 1 && rem >= 1 && rem <= 4) {
-        const int kt = rem <= 2 ? 2 : 4;
-        switch (full * 10 + kt) {
-        case 12: launch_xprod<T, 1, 2>(h, which, p); return;
-        case 14: launch_xprod<T, 1, 4>(h, which, p); return;
-        case 22: launch_xprod<T, 2, 2>(h, which, p); return;
-        case 24: launch_xprod<T, 2, 4>(h, which, p); return;
-        case 32: launch_xprod<T, 3, 2>(h, which, p); return;
-        default: launch_xprod<T, 3, 4>(h, which, p); return;
-        }
-    }
-    switch (h->NKQ) {
-    case 1: launch_xprod<T, 1, 0>(h, which, p); break;
-    case 2: launch_xprod<T, 2, 0>(h, which, p); break;
-    case 3: launch_xprod<T, 3, 0>(h, which, p); break;
-    default: launch_xprod<T, 4, 0>(h, which, p); break;
-    }
+    if (full >= 1 && rem >= 1 && rem <= 4)
+        with_nkq(full, [&](auto N) {
+            constexpr int F = N < 4 ? N : 3; // (full <= 3: k <= 64)
+            if (rem <= 2) go(std::integral_constant<int, F>{}, std::integral_constant<int, 2>{});
+            else go(std::integral_constant<int, F>{}, std::integral_constant<int, 4>{});
+        });
+    else
+        with_nkq(h->NKQ, [&](auto N) { go(N, std::integral_constant<int, 0>{}); });
 }
 
 // Split-fp16 cross product (k_xprod16.h): split copy of the fixed factor scaled by its own power of two, then the
 // A-streaming kernel on A16 (H half-step) or A16T (W half-step: the transposed copy makes it the same "TN" kernel).
-// Y16 / Cx / slab_stride: rows [q0, q0 + 16 NKQ) of the split copy and of the slabs when the rank exceeds 64 (NULL / 0: all of them)
+// q0: first of the 16 NKQ rows of the split copy and of the slabs this launch covers (rank > 64: one launch per 64 rows)
 template <int NKQ>
-static void launch_xprod16_m(nnlm_handle *h, const uint32_t *A16, int lda, int ldy, int ldc, const HalfPlan &p, const uint32_t *Y16 = nullptr,
-                             double *Cx = nullptr, size_t slab_stride = 0)
+static void launch_xprod16_m(nnlm_handle *h, const Side &s, const HalfPlan &p, int q0 = 0)
 {
-    const int KP = 16 * NKQ;
     dim3 grid(p.tiles_x, p.S);
-    const int lds = xprod_tn_lds_bytes(KP);
+    const int lds = xprod_tn_lds_bytes(16 * NKQ);
     set_dyn_lds((const void *)xprod16_tn_kernel<NKQ>, lds, "xprod16_tn_kernel");
-    xprod16_tn_kernel<NKQ><<<grid, XPROD_THREADS, lds, h->stream>>>(A16 + (size_t)p.col_off * lda, lda, Y16 ? Y16 : h->Y16, ldy,
-                                                                    (Cx ? Cx : h->Cx) + p.col_off, ldc, slab_stride ? slab_stride : (size_t)KP * ldc,
-                                                                    p.stage_begin, p.stage_end, p.sps, h->scal_exp);
+    xprod16_tn_kernel<NKQ><<<grid, XPROD_THREADS, lds, h->stream>>>(s.A16 + (size_t)p.col_off * s.ldy, s.ldy, h->Y16 + (size_t)q0 * s.ldy, s.ldy,
+                                                                    h->Cx + (size_t)q0 * s.ldc + p.col_off, s.ldc, s.slab_stride, p.stage_begin,
+                                                                    p.stage_end, p.sps, h->scal_exp);
 }
 // split copy of the fixed factor, scaled by its own power of two (two small kernels, outside the cross product's timing
 // scope).  Measured: making these faster (2-D absmax grid, no memset) or moving sweep_consts_kernel to the Gram stream
@@ -1270,11 +1312,10 @@ static void launch_xprod16_m(nnlm_handle *h, const uint32_t *A16, int lda, int l
 // mb: device word that already holds max|factor| (from gram_partial_kernel), or NULL: compute it here
 // w_max_in_zero_word: zero_word (about to be cleared for this half-step's sweep) still holds max|W| of the current W, left by
 // the sweep that solved it -- the fused error block's split copy of W then needs no absmax pass (24 us) of its own.
-static void prepare_factor16(nnlm_handle *h, int which, unsigned *mb = nullptr, unsigned *zero_word = nullptr, bool w_max_in_zero_word = false)
+static void prepare_factor16(nnlm_handle *h, const Side &s, unsigned *mb = nullptr, unsigned *zero_word = nullptr, bool w_max_in_zero_word = false)
 {
-    const double *Ym = (which == 1) ? h->W64 : h->H64;
-    const int ldm = (which == 1) ? h->npad : h->mpad; // leading dimension of the master = padded contraction length
-    const int plen_true = (which == 1) ? h->n : h->m;
+    const double *Ym = s.Y;
+    const int ldm = s.ldy, plen_true = s.p;
     h->y16_for = -1; // (Y16 is rewritten)
     if (!mb) {
         mb = h->maxbits;
@@ -1282,7 +1323,7 @@ static void prepare_factor16(nnlm_handle *h, int which, unsigned *mb = nullptr, 
         absmax_f64_kernel<<<(plen_true + 255) / 256, 256, 0, h->stream>>>(Ym, ldm, plen_true, h->k, mb);
     }
     const size_t cnt = (size_t)h->KP * ldm;
-    const bool fuse = which == 0 && h->fuse_err; // the fused error block also needs H and W with kq contiguous (same exponent for H)
+    const bool fuse = s.which == 0 && h->fuse_err; // the fused error block also needs H and W with kq contiguous (same exponent for H)
     if (fuse && w_max_in_zero_word && zero_word) // (before factor16_kernel clears that word)
         factor16c_kernel<<<h->npad / 64, 256, 0, h->stream>>>(h->W64, h->npad, h->n, h->k, zero_word, h->scal_exp + 2, h->W16c);
     factor16_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(Ym, ldm, plen_true, h->k, h->KP, ldm, mb, h->scal_exp + 1, h->Y16, zero_word);
@@ -1318,26 +1359,10 @@ static void launch_xprod16_err_m(nnlm_handle *h, const HalfPlan &p)
     h->err_zero_word = nullptr;
     h->fused_nb = p.tiles_x * p.S;
 }
-static void launch_xprod16(nnlm_handle *h, int which, const HalfPlan &p)
+static void launch_xprod16(nnlm_handle *h, const Side &s, const HalfPlan &p)
 {
-    if (which == 0 && h->fuse_err) {
-        switch (h->NKQ) {
-        case 1: launch_xprod16_err_m<1>(h, p); break;
-        case 2: launch_xprod16_err_m<2>(h, p); break;
-        case 3: launch_xprod16_err_m<3>(h, p); break;
-        default: launch_xprod16_err_m<4>(h, p); break;
-        }
-        return;
-    }
-    const int ldm = (which == 1) ? h->npad : h->mpad;
-    const uint32_t *A16 = (which == 1) ? h->A16 : h->A16T;
-    const int ldc = (which == 1) ? h->mpad : h->npad;
-    switch (h->NKQ) {
-    case 1: launch_xprod16_m<1>(h, A16, ldm, ldm, ldc, p); break;
-    case 2: launch_xprod16_m<2>(h, A16, ldm, ldm, ldc, p); break;
-    case 3: launch_xprod16_m<3>(h, A16, ldm, ldm, ldc, p); break;
-    default: launch_xprod16_m<4>(h, A16, ldm, ldm, ldc, p); break;
-    }
+    if (s.which == 0 && h->fuse_err) with_nkq(h->NKQ, [&](auto N) { launch_xprod16_err_m<N>(h, p); });
+    else with_nkq(h->NKQ, [&](auto N) { launch_xprod16_m<N>(h, s, p); });
 }
 
 // ---- rank > 64 (k_generic.h): the same A-streaming kernels, launched once per 64 rows of the fixed factor --------------
@@ -1360,97 +1385,60 @@ static int ensure_AT(nnlm_handle *h, bool soft = false)
     return NNLM_OK;
 }
 
-template <typename T, int NKQ>
-static void launch_xprod_tn_rows(nnlm_handle *h, const T *Amat, int lda, const T *Y, int ldy, double *C, int ldc, size_t slab_stride, const HalfPlan &p)
-{
-    dim3 grid(p.tiles_x, p.S);
-    const int lds = xprod_tn_lds_bytes(16 * NKQ);
-    set_dyn_lds((const void *)xprod_tn_kernel<T, NKQ, 0>, lds, "xprod_tn_kernel");
-    xprod_tn_kernel<T, NKQ, 0><<<grid, XPROD_THREADS, lds, h->stream>>>(Amat + (size_t)p.col_off * lda, lda, Y, ldy, C + p.col_off, ldc, slab_stride,
-                                                                         p.stage_begin, p.stage_end, p.sps);
-}
-
 template <typename T>
-static int launch_xprod_generic_t(nnlm_handle *h, int which, const HalfPlan &p)
+static int launch_xprod_generic_t(nnlm_handle *h, const Side &s, const HalfPlan &p)
 {
-    const int KP = h->KP;
-    const T *Amat;
-    const T *Y;
-    int lda, ldy, ldc;
-    if (which == 1) {
-        Amat = (const T *)h->A; lda = h->npad; Y = (const T *)h->Wop; ldy = h->npad; ldc = h->mpad;
-    } else {
+    const T *Y = (const T *)h->Wop;
+    if (s.which == 0) {
         int rc = ensure_AT(h);
         if (rc != NNLM_OK) return rc;
-        Amat = (const T *)h->AT; lda = h->mpad; ldy = h->mpad; ldc = h->npad;
         if (h->prec == NNLM_PREC_F64) Y = (const T *)h->H64;
         else { // fp32 [KP][mpad] copy of H
-            const size_t cnt = (size_t)KP * h->mpad;
+            const size_t cnt = (size_t)h->KP * h->mpad;
             factor_to_f32_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(h->H64, cnt, h->Hkq);
             Y = (const T *)h->Hkq;
         }
     }
-    const size_t slab = (size_t)KP * ldc;
-    for (int q0 = 0; q0 < KP; q0 += 64) {
-        const int nk = (KP - q0 >= 64) ? 4 : (KP - q0) / 16;
-        const T *Yq = Y + (size_t)q0 * ldy;
-        double *Cq = h->Cx + (size_t)q0 * ldc;
-        switch (nk) {
-        case 1: launch_xprod_tn_rows<T, 1>(h, Amat, lda, Yq, ldy, Cq, ldc, slab, p); break;
-        case 2: launch_xprod_tn_rows<T, 2>(h, Amat, lda, Yq, ldy, Cq, ldc, slab, p); break;
-        case 3: launch_xprod_tn_rows<T, 3>(h, Amat, lda, Yq, ldy, Cq, ldc, slab, p); break;
-        default: launch_xprod_tn_rows<T, 4>(h, Amat, lda, Yq, ldy, Cq, ldc, slab, p); break;
-        }
-    }
+    const T *Amat = (const T *)a_contig(h, s);
+    for (int q0 = 0; q0 < h->KP; q0 += 64)
+        with_nkq((h->KP - q0) / 16, [&](auto N) {
+            launch_xprod_tn<T, N>(h, Amat, s.ldy, Y + (size_t)q0 * s.ldy, s.ldy, h->Cx + (size_t)q0 * s.ldc, s.ldc, s.slab_stride, p);
+        });
     return NNLM_OK;
 }
 
-static int launch_xprod_generic(nnlm_handle *h, int which, const HalfPlan &p)
+static int launch_xprod_generic(nnlm_handle *h, const Side &s, const HalfPlan &p)
 {
     if (h->x16) { // split-fp16 copies A16 / A16T exist: the split copy of the factor (prepare_factor16) covers all KP rows
-        const int KP = h->KP;
-        const int ldm = (which == 1) ? h->npad : h->mpad, ldc = (which == 1) ? h->mpad : h->npad;
-        const uint32_t *A16 = (which == 1) ? h->A16 : h->A16T;
-        const size_t slab = (size_t)KP * ldc;
-        for (int q0 = 0; q0 < KP; q0 += 64) {
-            const int nk = (KP - q0 >= 64) ? 4 : (KP - q0) / 16;
-            const uint32_t *Yq = h->Y16 + (size_t)q0 * ldm;
-            double *Cq = h->Cx + (size_t)q0 * ldc;
-            switch (nk) {
-            case 1: launch_xprod16_m<1>(h, A16, ldm, ldm, ldc, p, Yq, Cq, slab); break;
-            case 2: launch_xprod16_m<2>(h, A16, ldm, ldm, ldc, p, Yq, Cq, slab); break;
-            case 3: launch_xprod16_m<3>(h, A16, ldm, ldm, ldc, p, Yq, Cq, slab); break;
-            default: launch_xprod16_m<4>(h, A16, ldm, ldm, ldc, p, Yq, Cq, slab); break;
-            }
-        }
+        for (int q0 = 0; q0 < h->KP; q0 += 64) with_nkq((h->KP - q0) / 16, [&](auto N) { launch_xprod16_m<N>(h, s, p, q0); });
         return NNLM_OK;
     }
-    if (h->prec == NNLM_PREC_F64) return launch_xprod_generic_t<double>(h, which, p);
-    return launch_xprod_generic_t<float>(h, which, p);
+    if (h->prec == NNLM_PREC_F64) return launch_xprod_generic_t<double>(h, s, p);
+    return launch_xprod_generic_t<float>(h, s, p);
 }
 
-// mb (optional): zeroed word that receives the bit pattern of max|Y| over the range (the split-fp16 copy's scale: no absmax pass)
-static void launch_gram(nnlm_handle *h, const double *Y, int ld, int c_begin, int c_end, int *nslabs, unsigned *mb = nullptr)
+// Gram partial sums of columns [c_begin, c_end) of Y into `slabs`, one per block of GRAM_COLS_PER_BLOCK columns: returns their number.
+// mb (optional, rank <= 64): zeroed word that receives the bit pattern of max|Y| over the range (the split-fp16 copy's scale: no absmax pass)
+static int launch_gram_partial(const nnlm_handle *h, const double *Y, int ld, int c_begin, int c_end, double *slabs, unsigned *mb, hipStream_t st)
 {
     int nb = (c_end - c_begin + GRAM_COLS_PER_BLOCK - 1) / GRAM_COLS_PER_BLOCK;
     if (nb < 1) nb = 1;
     if (generic_rank(h)) {
         dim3 grid(nb, h->NKQ * (h->NKQ + 1) / 2);
-        gram_partial_generic_kernel<<<grid, 256, 0, h->stream>>>(Y, ld, c_begin, c_end, h->NKQ, h->gslabs);
-        gram_reduce_kernel<<<(h->KP * h->KP + 255) / 256, 256, 0, h->stream>>>(h->gslabs, nb, h->KP, h->Graw);
-        *nslabs = nb;
-        return;
-    }
-    switch (h->NKQ) {
-    case 1: gram_partial_kernel<1><<<nb, 256, 0, h->stream>>>(Y, ld, c_begin, c_end, h->gslabs, mb); break;
-    case 2: gram_partial_kernel<2><<<nb, 256, 0, h->stream>>>(Y, ld, c_begin, c_end, h->gslabs, mb); break;
-    case 3: gram_partial_kernel<3><<<nb, 256, 0, h->stream>>>(Y, ld, c_begin, c_end, h->gslabs, mb); break;
-    default: gram_partial_kernel<4><<<nb, 256, 0, h->stream>>>(Y, ld, c_begin, c_end, h->gslabs, mb); break;
-    }
+        gram_partial_generic_kernel<<<grid, 256, 0, st>>>(Y, ld, c_begin, c_end, h->NKQ, slabs);
+    } else
+        with_nkq(h->NKQ, [&](auto N) { gram_partial_kernel<N><<<nb, 256, 0, st>>>(Y, ld, c_begin, c_end, slabs, mb); });
+    return nb;
+}
+
+// Gram of the fixed factor over its columns [c_begin, c_end) into Graw
+static void launch_gram(nnlm_handle *h, const Side &s, int c_begin, int c_end, unsigned *mb = nullptr)
+{
     const int KP = h->KP;
-    // (16 wavefronts per 64 entries, every 16th slab each: 5 us where the one-thread-per-entry sum over ~80 slabs took 20-25)
-    gram_fold_kernel<<<KP * KP / 64, 1024, 0, h->stream>>>(h->gslabs, nb, KP, h->Graw, SweepImg{});
-    *nslabs = nb;
+    const int nb = launch_gram_partial(h, s.Y, s.ldy, c_begin, c_end, h->gslabs, mb, h->stream);
+    if (generic_rank(h)) gram_reduce_kernel<<<(KP * KP + 255) / 256, 256, 0, h->stream>>>(h->gslabs, nb, KP, h->Graw);
+    else // (16 wavefronts per 64 entries, every 16th slab each: 5 us where the one-thread-per-entry sum over ~80 slabs took 20-25)
+        gram_fold_kernel<<<KP * KP / 64, 1024, 0, h->stream>>>(h->gslabs, nb, KP, h->Graw, SweepImg{});
 }
 
 template <int R, int L>
@@ -1753,26 +1741,17 @@ static void launch_colsolve(nnlm_handle *h, int method, const SweepArgs &a, size
         return;
     }
     // SCD in the reference's arithmetic (strict mode): the unrolled lane-local form; Lee's updates: colsolve_lee_kernel
-    if (method == 1) {
-        switch (h->NKQ) {
-        case 1: launch_colsolve_strict_m<1>(a, g_stride, h->stream); break;
-        case 2: launch_colsolve_strict_m<2>(a, g_stride, h->stream); break;
-        case 3: launch_colsolve_strict_m<3>(a, g_stride, h->stream); break;
-        default: launch_colsolve_strict_m<4>(a, g_stride, h->stream); break;
-        }
-        return;
-    }
-    switch (h->NKQ) {
-    case 1: launch_colsolve_m<1>(a, g_stride, h->stream); break;
-    case 2: launch_colsolve_m<2>(a, g_stride, h->stream); break;
-    case 3: launch_colsolve_m<3>(a, g_stride, h->stream); break;
-    default: launch_colsolve_m<4>(a, g_stride, h->stream); break;
-    }
+    with_nkq(h->NKQ, [&](auto N) {
+        if (method == 1) launch_colsolve_strict_m<N>(a, g_stride, h->stream);
+        else launch_colsolve_m<N>(a, g_stride, h->stream);
+    });
 }
 
 // CSR row lists of orientation `which` (see nnlm_handle::na_ptr): count, prefix sum on the host (once), fill
-static int ensure_na_lists(nnlm_handle *h, int which, const uint32_t *bits, int words, int p, int ncols)
+static int ensure_na_lists(nnlm_handle *h, const Side &s)
 {
+    const int which = s.which, words = s.words, p = s.p, ncols = s.ncols;
+    const uint32_t *bits = s.bits;
     if (h->na_ptr[which]) return NNLM_OK;
     uint32_t *cnt = nullptr;
     HIPCHK(h, hipMalloc(&cnt, (size_t)ncols * 4));
@@ -1811,49 +1790,72 @@ static size_t yrow_bytes(const nnlm_handle *h)
     return a > b ? a : b;
 }
 
-// Per-column Grams of columns [c0, c1) (row lists exist for all ncols columns)
-static int launch_na_gram(nnlm_handle *h, int which, const uint32_t *bits, int words, int p, int ncols, int c0, int c1, bool upper_only = false)
+// workspaces made on first use (freed with the factors)
+static int ensure_yrow(nnlm_handle *h)
 {
-    const int nc = c1 - c0;
+    if (!h->Yrow) HIPCHK(h, hipMalloc(&h->Yrow, yrow_bytes(h)));
+    return NNLM_OK;
+}
+static int ensure_gcols(nnlm_handle *h)
+{
+    if (!h->Gcols) HIPCHK(h, hipMalloc(&h->Gcols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * h->KP * 8));
+    return NNLM_OK;
+}
+static int ensure_sg_slabs(nnlm_handle *h)
+{
+    if (!h->sg_slabs) HIPCHK(h, hipMalloc(&h->sg_slabs, sg_slab_count(h) * h->KP * h->KP * 8));
+    return NNLM_OK;
+}
+static int ensure_klsw(nnlm_handle *h)
+{
+    if (!h->klsw) HIPCHK(h, hipMalloc(&h->klsw, (size_t)h->KP * 8));
+    return NNLM_OK;
+}
+static int ensure_klsw_cols(nnlm_handle *h)
+{
+    if (!h->klsw_cols) HIPCHK(h, hipMalloc(&h->klsw_cols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * 8));
+    return NNLM_OK;
+}
+
+// Per-column Grams of columns [c0, c1) into Gcols (row lists exist for all the side's columns)
+static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1)
+{
+    const int nc = c1 - c0, p = s.p;
     if (nc <= 0) return NNLM_OK;
-    const double *Ym = (which == 1) ? h->W64 : h->H64; // fixed factor [KP][ldy]; the kernels gather its ROWS: row-major copy Yrow [p][KP]
-    const int ldy = (which == 1) ? h->npad : h->mpad;
-    int rc = ensure_na_lists(h, which, bits, words, p, ncols);
+    int rc = ensure_na_lists(h, s);
     if (rc != NNLM_OK) return rc;
+    const uint32_t *ptr = h->na_ptr[s.which], *meta = h->na_meta[s.which];
+    const int *idx = h->na_idx[s.which];
+    // The kernels gather ROWS of the fixed factor [KP][ldy]: row-major copy Yrow.
     // F32 mode: the Grams on the fp16 matrix cores from the split copy of the rows (na_gram_f16_kernel).
     // max|fixed factor| is in *fixed_maxw (prepare_factor16 ran for this half-step's cross product).
     if (h->x16 && !generic_rank(h)) {
         // [p + 64 rows][64 hi | 64 lo halves]; rows p .. are zero (the kernel's "no row" index)
-        factor16c_kernel<<<p / 64 + 1, 256, 0, h->stream>>>(Ym, ldy, p, h->k, h->fixed_maxw ? h->fixed_maxw : h->maxbits, h->scal_exp + 3, (uint32_t *)h->Yrow);
+        factor16c_kernel<<<p / 64 + 1, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->k, h->fixed_maxw ? h->fixed_maxw : h->maxbits, h->scal_exp + 3, (uint32_t *)h->Yrow);
         const int nb = (nc + 3) / 4;
-#define NNLM_NAGH(N_) na_gram_f16_kernel<N_><<<nb, 256, 0, h->stream>>>(h->na_ptr[which], h->na_meta[which], h->na_idx[which], (const uint32_t *)h->Yrow, p, h->scal_exp + 3, h->Graw, h->Gcols, c1, c0, h->k, upper_only ? 1 : 0)
-        switch (h->NKQ) {
-        case 1: NNLM_NAGH(1); break;
-        case 2: NNLM_NAGH(2); break;
-        case 3: NNLM_NAGH(3); break;
-        default: NNLM_NAGH(4); break;
-        }
-#undef NNLM_NAGH
+        with_nkq(h->NKQ, [&](auto N) {
+            na_gram_f16_kernel<N><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const uint32_t *)h->Yrow, p, h->scal_exp + 3, h->Graw, h->Gcols, c1, c0, h->k);
+        });
         return NNLM_OK;
     }
-    factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(Ym, ldy, p, h->KP, h->Yrow);
+    factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->KP, h->Yrow);
     if (generic_rank(h)) { // rank > 64: k_generic.h
         const int lds = 16 * h->KP * 8;
-        na_gram_generic_kernel<<<nc, 256, lds, h->stream>>>(h->na_ptr[which], h->na_meta[which], h->na_idx[which], h->Yrow, h->KP, h->Graw, h->Gcols, c0);
+        na_gram_generic_kernel<<<nc, 256, lds, h->stream>>>(ptr, meta, idx, h->Yrow, h->KP, h->Graw, h->Gcols, c0);
         return NNLM_OK;
     }
     // strict mode: fp64 rows gathered by LDS-DMA, v_mfma_f64_16x16x4_f64 (k_missing.h, na_gram_lds_kernel); tail form for k = 16 j + 1, + 2
     const int nb = (nc + 3) / 4;
     const int ntail = h->k - 16 * (h->NKQ - 1);
     const bool tl = h->NKQ >= 2 && (ntail == 1 || ntail == 2);
-#define NNLM_NAGL(N_, TL_) na_gram_lds_kernel<double, N_, TL_><<<nb, 256, 0, h->stream>>>(h->na_ptr[which], h->na_meta[which], h->na_idx[which], (const double *)h->Yrow, h->Graw, h->Gcols, c1, c0, h->k, upper_only ? 1 : 0)
-    switch (h->NKQ) {
-    case 1: NNLM_NAGL(1, false); break;
-    case 2: if (tl) NNLM_NAGL(1, true); else NNLM_NAGL(2, false); break;
-    case 3: if (tl) NNLM_NAGL(2, true); else NNLM_NAGL(3, false); break;
-    default: if (tl) NNLM_NAGL(3, true); else NNLM_NAGL(4, false); break;
-    }
-#undef NNLM_NAGL
+    with_nkq(h->NKQ, [&](auto N) {
+        auto go = [&](auto nt, auto tail) {
+            na_gram_lds_kernel<double, nt, tail><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const double *)h->Yrow, h->Graw, h->Gcols, c1, c0, h->k);
+        };
+        if constexpr (N == 1) go(N, std::false_type{});
+        else if (tl) go(std::integral_constant<int, N - 1>{}, std::true_type{});
+        else go(N, std::false_type{});
+    });
     return NNLM_OK;
 }
 
@@ -1871,11 +1873,11 @@ static void swap_w(nnlm_handle *h)
 //   PH_B   sweep of this rank's columns into the packed slab (after the all-reduce, before the all-gather)
 //   PH_C   unpack of the all-gathered slabs into the resident layouts
 enum { PH_ALL = 0, PH_A = 1, PH_B = 2, PH_C = 3 };
-static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+static int half_step_solve(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
                            int nslabs, bool speculative, int phase, bool colshard = false);
 
 static int pack_prepare(nnlm_handle *h, int ncols, struct ShardCols *out, size_t tail);
-static int pack_gather_unpack(nnlm_handle *h, int which, int phase);
+static int pack_gather_unpack(nnlm_handle *h, const Side &s, int phase);
 
 // Columns of the factor being solved that this rank sweeps (multi-GPU): equal slabs of cpr columns (multiple of 256).
 struct ShardCols {
@@ -1890,18 +1892,75 @@ static ShardCols shard_cols(const nnlm_handle *h, int ncols)
     return c;
 }
 
-static int ensure_na_lists(nnlm_handle *h, int which, const uint32_t *bits, int words, int p, int ncols);
+// Row sums of the fixed factor (klsw) and, with missing values, per column over its non-missing entries for this launch's columns
+// (klsw_cols; src/update_with_missing.cpp:122,130): *sumw_cols = klsw_cols, or NULL
+static int kl_row_sums(nnlm_handle *h, const Side &s, const KlArgs &a, const double **sumw_cols)
+{
+    int rc = ensure_klsw(h);
+    if (rc != NNLM_OK) return rc;
+    kl_sumw_kernel<<<h->k, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->klsw);
+    *sumw_cols = nullptr;
+    if (!h->any_missing) return NNLM_OK;
+    if ((rc = ensure_yrow(h)) != NNLM_OK || (rc = ensure_klsw_cols(h)) != NNLM_OK || (rc = ensure_na_lists(h, s)) != NNLM_OK) return rc;
+    factor_rows_kernel<<<(a.p + 255) / 256, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->KP, h->Yrow);
+    if (a.ncols > a.col0) // (this rank's columns only)
+        kl_sumw_cols_kernel<<<(a.ncols - a.col0 + 3) / 4, 256, 0, h->stream>>>(h->na_ptr[s.which] + a.col0, h->na_meta[s.which] + a.col0, h->na_idx[s.which],
+                                                                              h->Yrow, h->KP, h->k, h->klsw, h->klsw_cols + (size_t)a.col0 * h->KP, h->KP,
+                                                                              a.ncols - a.col0);
+    *sumw_cols = h->klsw_cols;
+    return NNLM_OK;
+}
+
+// Column tiles of width `tile` that hold this launch's columns [a.col0, a.ncols): their number and the first one's first column
+// (multi-GPU: only the tiles of this rank's shard -- its first column is a multiple of 256)
+struct KlTiles {
+    int ny;
+    size_t cofs;
+};
+static KlTiles kl_tiles(const KlArgs &a, int tile)
+{
+    const int ct0 = a.col0 / tile, ct1 = (a.ncols + tile - 1) / tile;
+    return {ct1 > ct0 ? ct1 - ct0 : 0, (size_t)ct0 * tile};
+}
+
+// the fields KlTileArgs and Kl64Args share with KlArgs, and the row sums
+template <typename K>
+static void kl_common_args(K &o, const nnlm_handle *h, const KlArgs &a, const double *sumw_cols)
+{
+    o.p = a.p;
+    o.ncols = a.ncols;
+    o.k = a.k;
+    o.X = a.X;
+    o.Xout = a.Xout;
+    o.ldx = a.ldx;
+    o.colbase = a.col0;
+    o.ldo = a.ldo;
+    o.ocol0 = a.ocol0;
+    o.sumw = h->klsw;
+    o.sumw_cols = sumw_cols;
+    o.ldsw = h->KP;
+    o.r0 = a.r0;
+    o.r1 = a.r1;
+    o.r2 = a.r2;
+    o.mask = a.mask;
+    o.max_iter = a.max_iter;
+    o.rel_tol = a.rel_tol;
+    o.op = a.op;
+    o.op_mode = a.op_mode;
+    o.op_ld = a.op_ld;
+    o.sweeps = a.sweeps;
+}
 
 // Across GPUs the KL methods shard by columns of the factor being solved (the solvers need a column's whole contraction and
 // exchange nothing while they run): a rank solves its columns into the packed slab, ONE all-gather returns the factor.
-static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
                         bool speculative, int phase)
 {
     h->pack_tail = 0; // (the KL slabs travel alone)
     if (h->sharded && phase == PH_A) return NNLM_OK; // (test hooks: nothing to all-reduce)
     if (h->sharded && phase == PH_C) {
-        int rc = pack_gather_unpack(h, which, phase);
-        if (rc == NNLM_OK && which == 0 && !speculative) swap_w(h);
+        int rc = pack_gather_unpack(h, s, phase);
+        if (rc == NNLM_OK && s.which == 0 && !speculative) swap_w(h);
         return rc;
     }
     KlArgs a;
@@ -1914,27 +1973,16 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
     a.sweeps = h->sweeps + (speculative ? (h->sw_active ^ 1) : h->sw_active);
     a.A = h->A;
     a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
-    if (which == 1) {
-        a.X = h->H64; a.Xout = h->H64; a.ldx = h->mpad; a.Y = h->W64; a.ldy = h->npad;
-        a.a_col_stride = (size_t)h->npad; a.a_i_stride = 1;
-        a.bits = h->any_missing ? h->miss : nullptr; a.words = h->npad / 32;
-        a.p = h->n; a.ncols = h->m;
-        a.mask = h->has_hmask ? h->Hmask : nullptr;
-        a.op = nullptr; a.op_mode = 0; a.op_ld = 0;
-    } else {
-        a.X = h->W64; a.Xout = h->W64b[h->wcur ^ 1]; a.ldx = h->npad; a.Y = h->H64; a.ldy = h->mpad;
-        a.a_col_stride = 1; a.a_i_stride = (size_t)h->npad;
-        a.bits = h->any_missing ? h->missT : nullptr; a.words = h->mpad / 32;
-        a.p = h->m; a.ncols = h->n;
-        a.mask = h->has_wmask ? h->Wmask : nullptr;
-        a.op = h->Wopb[h->wcur ^ 1]; a.op_mode = (h->prec == NNLM_PREC_F64) ? 0 : 1; a.op_ld = h->npad;
-    }
-    const int ld_con = (which == 1) ? h->npad : h->mpad; // padded contraction length
-    const int ncols_all = a.ncols;
+    a.X = s.X; a.Xout = s.Xout; a.ldx = s.ldc; a.Y = s.Y; a.ldy = s.ldy;
+    a.a_col_stride = s.which == 1 ? (size_t)h->npad : 1; a.a_i_stride = s.which == 1 ? 1 : (size_t)h->npad; // (A is [mpad][npad])
+    a.bits = s.bits; a.words = s.words;
+    a.p = s.p; a.ncols = s.ncols;
+    a.mask = s.mask;
+    a.op = s.op; a.op_mode = s.op_mode; a.op_ld = s.op_ld;
     a.ldo = a.ldx;
     if (h->sharded) { // this rank's columns only, into the packed slab; the unpack writes masters and operands
         ShardCols sc;
-        int rcp = pack_prepare(h, ncols_all, &sc, 0);
+        int rcp = pack_prepare(h, s.ncols, &sc, 0);
         if (rcp != NNLM_OK) return rcp;
         a.col0 = sc.col0;
         a.ncols = sc.col1;
@@ -1945,7 +1993,7 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
         a.op_mode = 0;
     }
     {
-    ProfScope ps(h, which == 1 ? P_SWEEP_H : P_SWEEP_W);
+    ProfScope ps(h, s.prof_sweep);
     // The register-resident kernels start from the states y = Yt^T x of ALL columns (one GEMM into a matrix-sized buffer) and read
     // contraction-contiguous data (a transposed copy of A for the W half-step): one to two more copies of the matrix in HBM.  Where they
     // cannot be had, the streaming kernel takes the half-step in column chunks, with whatever scratch it can get (strided reads of A for
@@ -1969,7 +2017,7 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
         h->what_tight = true;
         reg64_path = false;
     }
-    if ((tile_path || reg64_path) && which == 0) {
+    if ((tile_path || reg64_path) && s.which == 0) {
         const int rc = h->at_tight ? NNLM_ERR_UNSUPPORTED : ensure_AT(h, true);
         if (rc == NNLM_ERR_UNSUPPORTED) {
             // the W half-step goes to the streaming kernel: the matrix-sized starting-state buffer is exactly the memory its scratch
@@ -1986,142 +2034,53 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
         KlTileArgs ta;
         const size_t cnt = (size_t)h->KP * h->mpad; // fp32 [KP][mpad] copy of H (fixed factor of the W half-step, operand of the GEMM below)
         factor_to_f32_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(h->H64, cnt, h->Hkq);
-        if (!h->klsw) HIPCHK(h, hipMalloc(&h->klsw, (size_t)h->KP * 8));
-        // starting state vectors y = Yt^T x of ALL columns as one GEMM, in the layout the solver reads: [column][contraction]
+        // starting state vectors y = Yt^T x of ALL columns as one GEMM, in the layout the solver reads: [column][contraction] (W half-step,
+        // roles swapped: What^T [row of A][column of A], next to the transposed fp32 copy of A)
         const int k2 = round_up_i(h->k, 2);
         const int lds = 2 * k2 * ERRF_TILE * (int)sizeof(float);
         set_dyn_lds((const void *)wh_store_kernel, lds, "wh_store_kernel");
-        // (multi-GPU: only the column tiles of this rank's shard -- its first column is a multiple of 256)
-        const int ct0 = a.col0 / ERRF_TILE, ct1 = (a.ncols + ERRF_TILE - 1) / ERRF_TILE;
-        const int ny = ct1 > ct0 ? ct1 - ct0 : 0;
-        const size_t cofs = (size_t)ct0 * ERRF_TILE;
-        if (which == 1) {
-            const int nx = h->npad / ERRF_TILE;
-            if (ny > 0 && !kl_own_init)
-                wh_store_kernel<<<8u * ((nx + 7) / 8) * ny, 256, lds, h->stream>>>((const float *)h->Wop, h->npad, h->Hkq + cofs, h->mpad, k2,
-                                                                                     h->What + cofs * h->npad, h->npad, nx);
-            ta.Adata = (const float *)h->A;
-            ta.Yf = (const float *)h->Wop;
-        } else { // roles swapped: What^T [row of A][column of A], next to the transposed fp32 copy of A
-            int rc = ensure_AT(h);
-            if (rc != NNLM_OK) return rc;
-            const int nx = h->mpad / ERRF_TILE;
-            if (ny > 0 && !kl_own_init)
-                wh_store_kernel<<<8u * ((nx + 7) / 8) * ny, 256, lds, h->stream>>>(h->Hkq, h->mpad, (const float *)h->Wop + cofs, h->npad, k2,
-                                                                                     h->What + cofs * h->mpad, h->mpad, nx);
-            ta.Adata = (const float *)h->AT;
-            ta.Yf = h->Hkq;
-        }
-        ta.lda = (size_t)ld_con;
+        const KlTiles ct = kl_tiles(a, ERRF_TILE);
+        const float *Yf = s.which == 1 ? (const float *)h->Wop : h->Hkq, *Xf = s.which == 1 ? h->Hkq : (const float *)h->Wop; // fixed, solved factor
+        const int nx = s.ldy / ERRF_TILE;
+        if (ct.ny > 0 && !kl_own_init)
+            wh_store_kernel<<<8u * ((nx + 7) / 8) * ct.ny, 256, lds, h->stream>>>(Yf, s.ldy, Xf + ct.cofs, s.ldc, k2, h->What + ct.cofs * s.ldy, s.ldy, nx);
+        ta.Adata = (const float *)a_contig(h, s);
+        ta.Yf = Yf;
+        ta.lda = (size_t)s.ldy;
         ta.Yinit = kl_own_init ? nullptr : h->What;
-        ta.ldyf = ld_con;
-        ta.p = a.p;
-        ta.ncols = a.ncols;
-        ta.k = h->k;
-        ta.X = a.X;
-        ta.Xout = a.Xout;
-        ta.ldx = a.ldx;
-        ta.colbase = a.col0;
-        ta.ldo = a.ldo;
-        ta.ocol0 = a.ocol0;
-        kl_sumw_kernel<<<h->k, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->klsw);
-        ta.sumw = h->klsw;
-        ta.sumw_cols = nullptr;
-        ta.ldsw = h->KP;
-        if (h->any_missing) { // row sums over each column's non-missing entries (src/update_with_missing.cpp:122,130)
-            if (!h->Yrow) HIPCHK(h, hipMalloc(&h->Yrow, yrow_bytes(h)));
-            if (!h->klsw_cols) HIPCHK(h, hipMalloc(&h->klsw_cols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * 8));
-            int rc = ensure_na_lists(h, which, a.bits, a.words, a.p, ncols_all);
-            if (rc != NNLM_OK) return rc;
-            factor_rows_kernel<<<(a.p + 255) / 256, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->KP, h->Yrow);
-            if (a.ncols > a.col0) // (this rank's columns only)
-                kl_sumw_cols_kernel<<<(a.ncols - a.col0 + 3) / 4, 256, 0, h->stream>>>(h->na_ptr[which] + a.col0, h->na_meta[which] + a.col0, h->na_idx[which],
-                                                                                      h->Yrow, h->KP, h->k, h->klsw, h->klsw_cols + (size_t)a.col0 * h->KP, h->KP,
-                                                                                      a.ncols - a.col0);
-            ta.sumw_cols = h->klsw_cols;
-        }
-        ta.r0 = reg[0];
-        ta.r1 = reg[1];
-        ta.r2 = reg[2];
-        ta.mask = a.mask;
+        ta.ldyf = s.ldy;
+        const double *sumw_cols;
+        int rc = kl_row_sums(h, s, a, &sumw_cols);
+        if (rc != NNLM_OK) return rc;
+        kl_common_args(ta, h, a, sumw_cols);
         ta.mw = h->MW;
-        ta.max_iter = inner_max_iter;
-        ta.rel_tol = inner_rel_tol;
-        ta.op = a.op;
-        ta.op_mode = a.op_mode;
-        ta.op_ld = a.op_ld;
-        ta.sweeps = a.sweeps;
         launch_kl_tile(method, ta, h->stream);
-        h->kl_form[which] = kl_own_init ? 1 : 0;
+        h->kl_form[s.which] = kl_own_init ? 1 : 0;
     } else if (reg64_path) {
         // ---- strict fp64 mode: register-resident fp64 state, the row of the fixed factor parked in LDS between the passes ----
+        // (starting states: What64[j][i], the layout of A; W half-step, roles swapped: What64^T [row of A][column of A], next to AT)
         Kl64Args ka;
-        if (!h->klsw) HIPCHK(h, hipMalloc(&h->klsw, (size_t)h->KP * 8));
         const int k4 = round_up_i(h->k, 4);
-        // (multi-GPU: only the column tiles of this rank's shard -- its first column is a multiple of 256)
-        const int ct0 = a.col0 / 64, ct1 = (a.ncols + 63) / 64;
-        const int ny = ct1 > ct0 ? ct1 - ct0 : 0;
-        const size_t cofs = (size_t)ct0 * 64;
-        if (which == 1) { // What64[j][i], the layout of A
-            dim3 grid(h->npad / 64, ny > 0 ? ny : 1);
-            if (ny > 0)
-                wh_store64_kernel<<<grid, 256, 0, h->stream>>>(h->W64, h->npad, h->H64 + cofs, h->mpad, k4, h->What64 + cofs * h->npad, (size_t)h->npad,
-                                                               h->n, h->m - (int)cofs);
-            ka.Adata = (const double *)h->A;
-        } else { // roles swapped: What64^T [row of A][column of A], next to the transposed copy of A
-            int rc = ensure_AT(h);
-            if (rc != NNLM_OK) return rc;
-            dim3 grid(h->mpad / 64, ny > 0 ? ny : 1);
-            if (ny > 0)
-                wh_store64_kernel<<<grid, 256, 0, h->stream>>>(h->H64, h->mpad, h->W64 + cofs, h->npad, k4, h->What64 + cofs * h->mpad, (size_t)h->mpad,
-                                                               h->m, h->n - (int)cofs);
-            ka.Adata = (const double *)h->AT;
-        }
-        ka.lda = (size_t)ld_con;
+        const KlTiles ct = kl_tiles(a, 64);
+        dim3 grid(s.ldy / 64, ct.ny > 0 ? ct.ny : 1);
+        if (ct.ny > 0)
+            wh_store64_kernel<<<grid, 256, 0, h->stream>>>(s.Y, s.ldy, s.X + ct.cofs, s.ldc, k4, h->What64 + ct.cofs * s.ldy, (size_t)s.ldy, s.p,
+                                                           s.ncols - (int)ct.cofs);
+        ka.Adata = (const double *)a_contig(h, s);
+        ka.lda = (size_t)s.ldy;
         ka.Yinit = h->What64;
         ka.Y = a.Y;
         ka.ldy = a.ldy;
-        ka.p = a.p;
-        ka.ncols = a.ncols;
-        ka.k = h->k;
-        ka.X = a.X;
-        ka.Xout = a.Xout;
-        ka.ldx = a.ldx;
-        ka.colbase = a.col0;
-        ka.ldo = a.ldo;
-        ka.ocol0 = a.ocol0;
-        kl_sumw_kernel<<<h->k, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->klsw);
-        ka.sumw = h->klsw;
-        ka.sumw_cols = nullptr;
-        ka.ldsw = h->KP;
-        if (h->any_missing) { // row sums over each column's non-missing entries (src/update_with_missing.cpp:122,130)
-            if (!h->Yrow) HIPCHK(h, hipMalloc(&h->Yrow, yrow_bytes(h)));
-            if (!h->klsw_cols) HIPCHK(h, hipMalloc(&h->klsw_cols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * 8));
-            int rc = ensure_na_lists(h, which, a.bits, a.words, a.p, ncols_all);
-            if (rc != NNLM_OK) return rc;
-            factor_rows_kernel<<<(a.p + 255) / 256, 256, 0, h->stream>>>(a.Y, a.ldy, a.p, h->KP, h->Yrow);
-            if (a.ncols > a.col0) // (this rank's columns only)
-                kl_sumw_cols_kernel<<<(a.ncols - a.col0 + 3) / 4, 256, 0, h->stream>>>(h->na_ptr[which] + a.col0, h->na_meta[which] + a.col0, h->na_idx[which],
-                                                                                      h->Yrow, h->KP, h->k, h->klsw, h->klsw_cols + (size_t)a.col0 * h->KP, h->KP,
-                                                                                      a.ncols - a.col0);
-            ka.sumw_cols = h->klsw_cols;
-        }
-        ka.r0 = reg[0];
-        ka.r1 = reg[1];
-        ka.r2 = reg[2];
-        ka.mask = a.mask;
-        ka.max_iter = inner_max_iter;
-        ka.rel_tol = inner_rel_tol;
-        ka.op = a.op;
-        ka.op_mode = a.op_mode;
-        ka.op_ld = a.op_ld;
-        ka.sweeps = a.sweeps;
+        const double *sumw_cols;
+        int rc = kl_row_sums(h, s, a, &sumw_cols);
+        if (rc != NNLM_OK) return rc;
+        kl_common_args(ka, h, a, sumw_cols);
         launch_kl64(method, ka, h->stream);
-        h->kl_form[which] = 2;
+        h->kl_form[s.which] = 2;
     } else {
         // ---- no size limits: state vectors and data columns streamed from a scratch buffer (kl_stream_kernel), `chunk` columns at a
         // time: the whole range when the scratch for it can be had (two vectors per column), otherwise as many as fit
-        const size_t per_col = (size_t)2 * ld_con * esize(h);
+        const size_t per_col = (size_t)2 * s.ldy * esize(h);
         const int range = a.ncols > a.col0 ? a.ncols - a.col0 : 0;
         int chunk = range;
         if (range > 0 && h->klst_bytes < (size_t)range * per_col) {
@@ -2142,7 +2101,7 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
                 h->klst_bytes = (size_t)chunk * per_col;
             }
         }
-        h->kl_form[which] = 3;
+        h->kl_form[s.which] = 3;
         const int col_end = a.ncols;
         for (int c0 = a.col0; c0 < col_end; c0 += chunk) {
             KlArgs ac = a;
@@ -2150,8 +2109,8 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
             ac.ncols = (c0 + chunk < col_end) ? c0 + chunk : col_end;
             // (the kernel addresses the scratch by absolute column: the chunk's slots start at its first column)
             char *st = (char *)h->klst - (size_t)c0 * per_col;
-            const int rcs = (h->prec == NNLM_PREC_F64) ? launch_kl_stream<double>(h, method, ac, h->MW, st, (size_t)ld_con, h->stream)
-                                                       : launch_kl_stream<float>(h, method, ac, h->MW, st, (size_t)ld_con, h->stream);
+            const int rcs = (h->prec == NNLM_PREC_F64) ? launch_kl_stream<double>(h, method, ac, h->MW, st, (size_t)s.ldy, h->stream)
+                                                       : launch_kl_stream<float>(h, method, ac, h->MW, st, (size_t)s.ldy, h->stream);
             if (rcs != NNLM_OK) return rcs;
         }
     }
@@ -2159,10 +2118,10 @@ static int half_step_kl(nnlm_handle *h, int which, const double reg[3], unsigned
     LAUNCHCHK(h);
     if (h->sharded) {
         if (phase == PH_B) return NNLM_OK; // test hooks: the caller gathers the slabs
-        int rc = pack_gather_unpack(h, which, phase);
+        int rc = pack_gather_unpack(h, s, phase);
         if (rc != NNLM_OK) return rc;
     }
-    if (which == 0 && !speculative) swap_w(h);
+    if (s.which == 0 && !speculative) swap_w(h);
     return NNLM_OK;
 }
 
@@ -2171,35 +2130,33 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
 // Square-loss half-step on a sparse A (k_sparse.h): the Gram of the fixed factor (launch_gram), a row copy of the fixed factor and the
 // SpMM -- W^T A over the CSC for the H half-step, A H^T over the CSR for the W half-step -- into ONE slab of Cx, then the solvers of the
 // dense path unchanged (half_step_solve).  Rank > 64: one SpMM launch per 64 coordinates, the generic Gram and sweep.
-static int half_step_sparse(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
+static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
 {
     if (method >= 3)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
-    const double *Ym = (which == 1) ? h->W64 : h->H64;
-    const int ldm = (which == 1) ? h->npad : h->mpad, p = (which == 1) ? h->n : h->m;
+    const int p = s.p;
     {
         ProfScope ps(h, P_GRAM, h->stream);
-        int nsl = 0;
-        launch_gram(h, Ym, ldm, 0, p, &nsl);
+        launch_gram(h, s, 0, p);
     }
     {
-        ProfScope ps(h, which == 1 ? P_SPMM_H : P_SPMM_W);
+        ProfScope ps(h, s.prof_spmm);
         const bool f64 = h->prec == NNLM_PREC_F64;
-        if (f64) factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(Ym, ldm, p, h->KP, (double *)h->sp_Y);
-        else factor_rows_kernel<float><<<(p + 255) / 256, 256, 0, h->stream>>>(Ym, ldm, p, h->KP, (float *)h->sp_Y);
+        if (f64) factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->KP, (double *)h->sp_Y);
+        else factor_rows_kernel<float><<<(p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->KP, (float *)h->sp_Y);
         SpmmArgs a;
-        a.ptr = (which == 1) ? h->sp_cptr : h->sp_rptr;
-        a.idx = (which == 1) ? h->sp_ridx : h->sp_cidx;
-        a.val = (which == 1) ? h->sp_cval : h->sp_rval;
+        a.ptr = s.sp_ptr;
+        a.idx = s.sp_idx;
+        a.val = s.sp_val;
         a.Y = h->sp_Y;
         a.nnz = h->nnz;
-        a.ncols = (which == 1) ? h->m : h->n;
+        a.ncols = s.ncols;
         a.KP = h->KP;
         a.nworkers = nnlm_sp_workers(h->nnz, h->KP, h->cus_device);
         a.chunk = (h->nnz + a.nworkers - 1) / a.nworkers;
         if (a.chunk < 1) a.chunk = 1;
         a.C = h->Cx;
-        a.ldc = (which == 1) ? h->mpad : h->npad;
+        a.ldc = s.ldc;
         a.carry = h->sp_carry;
         for (int q0 = 0; q0 < h->KP; q0 += 64) {
             a.q0 = q0;
@@ -2207,7 +2164,7 @@ static int half_step_sparse(nnlm_handle *h, int which, const double reg[3], unsi
         }
     }
     if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
-    return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, 1, speculative, PH_ALL, false);
+    return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, 1, speculative, PH_ALL, false);
 }
 
 // speculative (W half-step only): the result goes to the alternate W buffers and the alternate sweep counter and is
@@ -2224,11 +2181,13 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     h->sg_prev = sg_which;
     h->sg_which = h->sg_other = -1;
     h->sg_request = false;
-    if (h->sparse) return half_step_sparse(h, which, reg, inner_max_iter, inner_rel_tol, method, speculative);
+    const Side s = side_of(h, which);
+    const int solved_by = which ^ 1; // the half-step that solved this half-step's fixed factor
+    if (h->sparse) return half_step_sparse(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
     if (generic_rank(h) && h->sharded && method < 3 && !h->any_missing && !h->dense_cols)
         return fail(h, NNLM_ERR_UNSUPPORTED, "rank > %d across GPUs: only the column-sharded form (nnlm_comm_set_form(h, NNLM_FORM_COLS))", NNLM_KQ_MAX);
     if (partial_only) phase = PH_A;
-    if (method >= 3) return half_step_kl(h, which, reg, inner_max_iter, inner_rel_tol, method, speculative, phase);
+    if (method >= 3) return half_step_kl(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative, phase);
     // Missing values across GPUs: every column has a Gram of its own, so the column is the unit: a rank forms the
     // cross product of ITS columns over the whole contraction, their Grams, solves them, and ONE all-gather returns the factor --
     // no all-reduce.  Test hooks: phase 1 is empty, phase 2 computes and packs, phase 3 unpacks.
@@ -2242,20 +2201,21 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     if (colshard && phase == PH_A) return NNLM_OK;
     if (phase == PH_C || (phase == PH_B && !colshard)) {
         const HalfPlan pp = plan_half(h, which, h->rank, h->nranks);
-        return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, pp.S, speculative, phase, colshard);
+        return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, pp.S, speculative, phase, colshard);
     }
-    if (h->any_missing && !h->Gcols) { // NA path workspaces, on first use
-        if (!h->Yrow) HIPCHK(h, hipMalloc(&h->Yrow, yrow_bytes(h)));
-        HIPCHK(h, hipMalloc(&h->Gcols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * h->KP * 8));
+    if (h->any_missing) { // NA path workspaces, on first use
+        int rc = ensure_yrow(h);
+        if (rc == NNLM_OK) rc = ensure_gcols(h);
+        if (rc != NNLM_OK) return rc;
     }
     HalfPlan p = plan_half(h, which, colshard ? 0 : h->rank, colshard ? 1 : h->nranks);
     if (colshard) { // own columns only, whole contraction
-        const ShardCols sc = shard_cols(h, (which == 1) ? h->m : h->n);
+        const ShardCols sc = shard_cols(h, s.ncols);
         const int tile = XPROD_TN_BJ;
         p.col_off = sc.col0;
         p.tiles_x = (sc.col1 - sc.col0 + tile - 1) / tile;
         if (p.tiles_x > 0) split_plan(p.tiles_x, p.stage_end - p.stage_begin, &p.S, &p.sps);
-        const size_t need = (size_t)p.S * h->KP * ((which == 1) ? h->mpad : h->npad);
+        const size_t need = (size_t)p.S * s.slab_stride;
         if (need > h->Cx_elems) { // (fewer tiles -> deeper split-K than the single-GPU plan the slabs were sized for)
             sync_all(h);
             hipFree(h->Cx);
@@ -2279,15 +2239,15 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
         // which needs a fence -- gram_partial (12 us) and the "last block" step of gram_reduce_consts (most of its 15 us:
         // __threadfence() is a cross-XCD cache write-back here) are gone.
         const bool fastsw = sweep_fast(h);
-        if (fastsw && !h->sg_slabs) {
-            const int big = h->n > h->m ? h->n : h->m;
-            HIPCHK(h, hipMalloc(&h->sg_slabs, sg_slab_count(h) * h->KP * h->KP * 8));
+        if (fastsw) {
+            int rc = ensure_sg_slabs(h);
+            if (rc != NNLM_OK) return rc;
         }
         unsigned *smax_w = fastsw ? h->maxbits + 4 + (h->sg_par ^ 1) : nullptr; // this half-step's sweep writes its max here
         h->sg_request = fastsw;
-        if (fastsw && sg_which == (which == 1 ? 0 : 1)) {
-            {
-                ProfScope ps(h, P_GRAM, h->stream);
+        {
+            ProfScope ps(h, P_GRAM, h->stream);
+            if (fastsw && sg_which == solved_by) {
                 SweepImg im;
                 im.img = nullptr; // (fp32-operand mode: sweep_scd_f_kernel builds its operands from Graw itself -- no image)
                 im.NB = (h->k + 3) / 4, im.NP = sweepq_np(im.NB, false), im.k = h->k, im.r0 = reg[0], im.r1 = reg[1];
@@ -2302,69 +2262,47 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
                     h->y16_for = -1;
                     h->err_zero_word = smax_w;
                 } else if (h->fuse_err) { // (the general routine)
-                    prepare_factor16(h, which, h->maxbits + 4 + h->sg_par, smax_w, which == 0 && sg_other == 0);
+                    prepare_factor16(h, s, h->maxbits + 4 + h->sg_par, smax_w, which == 0 && sg_other == 0);
                     gram_fold_kernel<<<h->KP * h->KP / 64, 1024, 0, h->stream>>>(h->sg_slabs, h->sg_nslabs, h->KP, h->Graw, im);
                 } else {
-                    const double *Ym = (which == 1) ? h->W64 : h->H64;
-                    const int ldm = (which == 1) ? h->npad : h->mpad, lim = (which == 1) ? h->n : h->m;
-                    const size_t cnt = (size_t)h->KP * ldm;
+                    const size_t cnt = (size_t)h->KP * s.ldy;
                     factor16_fold_kernel<<<(unsigned)(h->KP * h->KP / 64 + (cnt + 1023) / 1024), 1024, 0, h->stream>>>(
-                        Ym, ldm, lim, h->k, h->KP, ldm, h->maxbits + 4 + h->sg_par, h->scal_exp + 1, h->Y16, smax_w, h->sg_slabs, h->sg_nslabs, h->Graw, im);
+                        s.Y, s.ldy, s.p, h->k, h->KP, s.ldy, h->maxbits + 4 + h->sg_par, h->scal_exp + 1, h->Y16, smax_w, h->sg_slabs, h->sg_nslabs, h->Graw, im);
                 }
                 h->pack_ready = true;
+            } else {
+                unsigned *mb = h->maxbits + 1 + h->mb_par, *mb_next = h->maxbits + 1 + (h->mb_par ^ 1);
+                h->mb_par ^= 1;
+                const int nb = launch_gram_partial(h, s.Y, s.ldy, 0, s.p, h->gslabs, mb, h->stream);
+                prepare_factor16(h, s, mb, smax_w);
+                gram_reduce_kernel<<<(h->KP * h->KP + 255) / 256, 256, 0, h->stream>>>(h->gslabs, nb, h->KP, h->Graw);
+                HIPCHK(h, hipMemsetAsync(mb_next, 0, sizeof(unsigned), h->stream)); // the max word the NEXT half-step's gram_partial accumulates into
             }
-            {
-                ProfScope ps(h, which == 1 ? P_XPROD_H : (h->fuse_err ? P_XPROD_W_ERR : P_XPROD_W));
-                launch_xprod16(h, which, p);
-            }
-            if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
-            return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, p.S, speculative, phase);
-        }
-        unsigned *mb = h->maxbits + 1 + h->mb_par, *mb_next = h->maxbits + 1 + (h->mb_par ^ 1);
-        h->mb_par ^= 1;
-        const double *Ym = (which == 1) ? h->W64 : h->H64;
-        const int ldm = (which == 1) ? h->npad : h->mpad, lim = (which == 1) ? h->n : h->m;
-        int nb = (lim + GRAM_COLS_PER_BLOCK - 1) / GRAM_COLS_PER_BLOCK;
-        if (nb < 1) nb = 1;
-        {
-            ProfScope ps(h, P_GRAM, h->stream);
-            switch (h->NKQ) {
-            case 1: gram_partial_kernel<1><<<nb, 256, 0, h->stream>>>(Ym, ldm, 0, lim, h->gslabs, mb); break;
-            case 2: gram_partial_kernel<2><<<nb, 256, 0, h->stream>>>(Ym, ldm, 0, lim, h->gslabs, mb); break;
-            case 3: gram_partial_kernel<3><<<nb, 256, 0, h->stream>>>(Ym, ldm, 0, lim, h->gslabs, mb); break;
-            default: gram_partial_kernel<4><<<nb, 256, 0, h->stream>>>(Ym, ldm, 0, lim, h->gslabs, mb); break;
-            }
-            prepare_factor16(h, which, mb, smax_w);
-            gram_reduce_kernel<<<(h->KP * h->KP + 255) / 256, 256, 0, h->stream>>>(h->gslabs, nb, h->KP, h->Graw);
-            HIPCHK(h, hipMemsetAsync(mb_next, 0, sizeof(unsigned), h->stream)); // the max word the NEXT half-step's gram_partial accumulates into
         }
         {
-            ProfScope ps(h, which == 1 ? P_XPROD_H : (h->fuse_err ? P_XPROD_W_ERR : P_XPROD_W));
-            launch_xprod16(h, which, p);
+            ProfScope ps(h, s.prof_xprod);
+            launch_xprod16(h, s, p);
         }
         if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
-        return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, p.S, speculative, phase);
+        return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, p.S, speculative, phase);
     }
     // 1. Gram of the fixed factor over this rank's contraction slab -- on the main stream, AHEAD of the cross product.  (Rounds 1-2
     // ran it on a second stream next to the A-streaming kernel: the cross product owns every CU's LDS, the Gram kernel got slots
     // only as its workgroups retired and stretched from 0.03 to 0.5-1.0 ms while slowing the cross product down with it --
     // profiles/r03_f64_cfg2_a_kernel_stats.csv: xprod_tn 0.44 .. 1.6 ms, gram_partial 0.03 .. 0.99 ms.)
-    int gslabs = 0;
     // (multi-GPU, dense SCD, column form: the unpack of the previous half-step already summed the ranks' Gram partial sums of this
     //  half-step's fixed factor into Graw -- shard_gram_sum_kernel -- instead of every rank recomputing the whole Gram)
-    const bool gram_cached = colshard && method == 1 && !h->any_missing && !generic_rank(h) && h->gshard_for == ((which == 1) ? 0 : 1);
+    const bool gram_cached = colshard && method == 1 && !h->any_missing && !generic_rank(h) && h->gshard_for == solved_by;
     // (one GPU, strict mode, dense SCD: the sweep that solved the fixed factor left the Gram partial sums of its workgroups behind, as
     //  in the split-fp16 flow above -- one fold instead of gram_partial + gram_reduce over the whole factor)
     const bool sg_strict = !h->sharded && !h->x16 && h->prec == NNLM_PREC_F64 && method == 1 && !h->any_missing && !generic_rank(h);
     if (sg_strict) {
-        if (!h->sg_slabs) {
-            const int big = h->n > h->m ? h->n : h->m;
-            HIPCHK(h, hipMalloc(&h->sg_slabs, sg_slab_count(h) * h->KP * h->KP * 8));
-        }
+        int rc = ensure_sg_slabs(h);
+        if (rc != NNLM_OK) return rc;
         h->sg_request = true; // this half-step's sweep leaves its slabs for the next one
     }
     unsigned *gmb = nullptr;
-    if (sg_strict && sg_which == ((which == 1) ? 0 : 1)) {
+    if (sg_strict && sg_which == solved_by) {
         ProfScope ps(h, P_GRAM, h->stream);
         SweepImg im; // (the fold also writes the sweep's operand image: no sweepq_pack_kernel launch)
         im.img = h->sweepq_img, im.NB = (h->k + 3) / 4, im.NP = sweepq_np(im.NB, true), im.k = h->k, im.r0 = reg[0], im.r1 = reg[1];
@@ -2374,9 +2312,9 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     } else if (!gram_cached) {
         h->gshard_for = -1;
         ProfScope ps(h, P_GRAM, h->stream);
-        const int CE = stage_elems(h, which);
+        const int CE = stage_elems(h);
         int c0 = p.stage_begin * CE, c1 = p.stage_end * CE;
-        const int lim = (which == 1) ? h->n : h->m;
+        const int lim = s.p;
         if (c1 > lim) c1 = lim;
         if (c0 > c1) c0 = c1;
         // (one GPU, split-fp16 mode: the Gram pass also leaves max|fixed factor| for the split copies -- no absmax pass; the two
@@ -2385,31 +2323,29 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
             gmb = h->maxbits + 1 + h->mb_par;
             h->mb_par ^= 1;
         }
-        if (which == 1) launch_gram(h, h->W64, h->npad, c0, c1, &gslabs, gmb);
-        else launch_gram(h, h->H64, h->mpad, c0, c1, &gslabs, gmb);
+        launch_gram(h, s, c0, c1, gmb);
         if (gmb) HIPCHK(h, hipMemsetAsync(h->maxbits + 1 + h->mb_par, 0, sizeof(unsigned), h->stream));
     }
     // 2. cross product slabs
     if (h->x16) {
         // (multi-GPU: the unpack of the previous half-step left max|fixed factor| behind -- no absmax pass)
-        const int solved_by = (which == 1) ? 0 : 1; // the half-step that solved this half-step's fixed factor
         unsigned *mb = (h->sharded && h->upk_max_for == solved_by) ? h->maxbits + 6 + solved_by : gmb;
         // (dense SCD, column form: that unpack also wrote the split copy and its exponent -- the ranks' maxima travelled with the slabs)
-        if (!(h->sharded && mb && h->y16_for == solved_by && !h->fuse_err)) prepare_factor16(h, which, mb);
+        if (!(h->sharded && mb && h->y16_for == solved_by && !h->fuse_err)) prepare_factor16(h, s, mb);
         h->fixed_maxw = mb ? mb : h->maxbits;
     }
     if (p.tiles_x > 0) {
-        ProfScope ps(h, which == 1 ? P_XPROD_H : (h->fuse_err ? P_XPROD_W_ERR : P_XPROD_W));
+        ProfScope ps(h, s.prof_xprod);
         if (generic_rank(h)) {
-            int rcx = launch_xprod_generic(h, which, p);
+            int rcx = launch_xprod_generic(h, s, p);
             if (rcx != NNLM_OK) return rcx;
-        } else if (h->x16) launch_xprod16(h, which, p);
+        } else if (h->x16) launch_xprod16(h, s, p);
         else {
             if (which == 0) {
                 int rca = ensure_AT(h);
                 if (rca != NNLM_OK) return rca;
             }
-            launch_xprod_nkq<double>(h, which, p);
+            launch_xprod_nkq(h, s, p);
         }
     }
     if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream)); // the error block starts once A is no longer streamed
@@ -2428,8 +2364,7 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     }
     // (multi-GPU) fold the split-K slabs into the contiguous [G | C] buffer; ONE all-reduce sums it over ranks
     if (h->sharded && !colshard) {
-        const int ld = (which == 1) ? h->mpad : h->npad;
-        const size_t cnt = (size_t)h->KP * ld;
+        const size_t cnt = s.slab_stride;
         slab_reduce_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(h->Cx, p.S, cnt, h->red + (size_t)h->KP * h->KP);
         if (phase == PH_A) return NNLM_OK; // test hooks: the caller performs the exchange
         if (h->comm) {
@@ -2438,14 +2373,14 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
             if (r != ncclSuccess) return fail(h, NNLM_ERR_COMM, "ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
         }
     }
-    return half_step_solve(h, which, reg, inner_max_iter, inner_rel_tol, method, p.S, speculative, phase, colshard);
+    return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, p.S, speculative, phase, colshard);
 }
 
-static int shard_unpack(nnlm_handle *h, int which)
+static int shard_unpack(nnlm_handle *h, const Side &s)
 {
     ProfScope ps(h, P_UNPACK);
-    const int ncols = (which == 1) ? h->m : h->n;
-    const ShardCols sc = shard_cols(h, ncols);
+    const int which = s.which;
+    const ShardCols sc = shard_cols(h, s.ncols);
     const int f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
     unsigned *maxw = h->x16 ? h->maxbits + 6 + which : nullptr; // max|factor| for the next half-step's split copy (no absmax pass there)
     // dense SCD in the column form (pack_tail = KP * KP Gram partial sums + the rank's max|x|): max|factor| is known before an entry is
@@ -2458,15 +2393,9 @@ static int shard_unpack(nnlm_handle *h, int which)
     if (maxw && !tail_max) HIPCHK(h, hipMemsetAsync(maxw, 0, sizeof(unsigned), h->stream));
     h->upk_max_for = maxw ? which : -1;
     const size_t rank_stride = (size_t)h->k * sc.cpr + h->pack_tail;
-    if (which == 1)
-        shard_unpack_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, h->stream>>>(h->pack_all, h->nranks, rows, sc.cpr, h->k, ncols, h->H64,
-                                                                                   h->mpad, nullptr, 0, 0, f64, maxw, rank_stride, tail_max_off, y16,
-                                                                                   h->mpad, h->scal_exp + 1);
-    else
-        shard_unpack_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, h->stream>>>(h->pack_all, h->nranks, rows, sc.cpr, h->k, ncols,
-                                                                                   h->W64b[h->wcur ^ 1], h->npad, h->Wopb[h->wcur ^ 1],
-                                                                                   f64 ? 0 : 1, h->npad, f64, maxw, rank_stride, tail_max_off, y16,
-                                                                                   h->npad, h->scal_exp + 1);
+    shard_unpack_kernel<<<(unsigned)((tot + 255) / 256), 256, 0, h->stream>>>(h->pack_all, h->nranks, rows, sc.cpr, h->k, s.ncols, s.Xout, s.ldc, s.op,
+                                                                               s.op_mode, s.op_ld, f64, maxw, rank_stride, tail_max_off, y16, s.ldc,
+                                                                               h->scal_exp + 1);
     h->y16_for = y16 ? which : -1;
     if (h->gshard_for == which) h->gshard_for = -1; // (that factor has just been rewritten)
     if (h->pack_tail) { // the Gram of the factor just gathered = the sum of the ranks' partial sums, in rank order
@@ -2501,10 +2430,9 @@ static int pack_prepare(nnlm_handle *h, int ncols, struct ShardCols *out, size_t
     return NNLM_OK;
 }
 // ONE ncclAllGather of the packed slabs, then every rank writes masters and GEMM operands of all columns
-static int pack_gather_unpack(nnlm_handle *h, int which, int phase)
+static int pack_gather_unpack(nnlm_handle *h, const Side &s, int phase)
 {
-    const int ncols = (which == 1) ? h->m : h->n;
-    const ShardCols sc = shard_cols(h, ncols);
+    const ShardCols sc = shard_cols(h, s.ncols);
     if (h->comm) {
         ProfScope ps(h, P_ALLGATHER);
         ncclResult_t r = g_rccl.AllGather(h->pack_send, h->pack_all, (size_t)h->k * sc.cpr + h->pack_tail, ncclDouble, (ncclComm_t)h->comm,
@@ -2512,22 +2440,21 @@ static int pack_gather_unpack(nnlm_handle *h, int which, int phase)
         if (r != ncclSuccess) return fail(h, NNLM_ERR_COMM, "ncclAllGather failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?");
     } else if (phase == PH_ALL)
         return fail(h, NNLM_ERR_COMM, "virtual rank %d of %d has no communicator: drive it with nnlm_debug_phase()", h->rank, h->nranks);
-    return shard_unpack(h, which);
+    return shard_unpack(h, s);
 }
 
 // 3. per-column solve (+ multi-GPU: all-gather of the solved column slabs and unpack into the resident layouts)
 // colshard: the cross product was formed over the whole contraction for this rank's columns only (missing values: per-column
 // Grams make the column the natural unit) -- its split-K slabs are read directly, nothing was all-reduced.
-static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+static int half_step_solve(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
                            int nslabs, bool speculative, int phase, bool colshard)
 {
-    const int ncols = (which == 1) ? h->m : h->n;
-    h->cur_which = which;
+    h->cur_which = s.which;
     // dense SCD in the column form: the Gram partial sums of this rank's columns travel with its slab (shard_gram_sum_kernel)
     // (+ one double: the rank's max|x|, so that the unpack can write the split-fp16 copy of the factor as well)
     h->pack_tail = (h->sharded && colshard && method == 1 && !h->any_missing && !generic_rank(h)) ? (size_t)h->KP * h->KP + 1 : 0;
     if (phase != PH_C) {
-        ProfScope ps(h, which == 1 ? P_SWEEP_H : P_SWEEP_W);
+        ProfScope ps(h, s.prof_sweep);
         SweepArgs a;
         a.Graw = h->Graw;
         a.KPg = h->KP;
@@ -2548,33 +2475,19 @@ static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsig
             a.maxbits = h->x16 ? h->maxbits + 4 + (h->sg_par ^ 1) : nullptr; // (max|x| is the split copy's scale: fp32-operand mode only)
             a.gram_slabs = h->sg_slabs;
         }
-        if (which == 1) {
-            a.X = h->H64;
-            a.Xout = h->H64;
-            a.ldx = a.ldo = h->mpad;
-            a.ldc = h->mpad;
-            a.slab_stride = (size_t)h->KP * h->mpad;
-            a.ncols = h->m;
-            a.mask = h->has_hmask ? h->Hmask : nullptr;
-            a.op = nullptr; // (H has no GEMM-operand copy: every consumer reads the master or makes its own split / fp32 copy)
-            a.op_mode = 0;
-            a.op_ld = 0;
-        } else {
-            a.X = h->W64;
-            a.Xout = h->W64b[h->wcur ^ 1];
-            a.ldx = a.ldo = h->npad;
-            a.ldc = h->npad;
-            a.slab_stride = (size_t)h->KP * h->npad;
-            a.ncols = h->n;
-            a.mask = h->has_wmask ? h->Wmask : nullptr;
-            a.op = h->Wopb[h->wcur ^ 1];
-            a.op_mode = (h->prec == NNLM_PREC_F64) ? 0 : 1;
-            a.op_ld = h->npad;
-        }
+        a.X = s.X;
+        a.Xout = s.Xout;
+        a.ldx = a.ldo = a.ldc = s.ldc;
+        a.slab_stride = s.slab_stride;
+        a.ncols = s.ncols;
+        a.mask = s.mask;
+        a.op = s.op;
+        a.op_mode = s.op_mode;
+        a.op_ld = s.op_ld;
         a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
         if (h->sharded) { // sweep only this rank's columns into the packed slab; the unpack writes masters and operands
             ShardCols sc;
-            int rcp = pack_prepare(h, ncols, &sc, h->pack_tail);
+            int rcp = pack_prepare(h, s.ncols, &sc, h->pack_tail);
             if (rcp != NNLM_OK) return rcp;
             a.col0 = sc.col0;
             a.ncols = sc.col1;
@@ -2584,23 +2497,17 @@ static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsig
             a.op = nullptr;
             a.op_mode = 0;
             if (h->pack_tail) {
-                if (!h->sg_slabs) {
-                    const int big = h->n > h->m ? h->n : h->m;
-                    HIPCHK(h, hipMalloc(&h->sg_slabs, sg_slab_count(h) * h->KP * h->KP * 8));
-                }
+                int rc = ensure_sg_slabs(h);
+                if (rc != NNLM_OK) return rc;
                 a.gram_slabs = h->sg_slabs; // (one slab per workgroup of sweep_scd_q_kernel; folded behind the packed slab below)
                 a.maxbits = h->x16 ? h->maxbits + 8 : nullptr; // (the sweep's atomicMax; handed to the tail and cleared by gram_fold_tail_kernel)
             }
         }
         if (h->any_missing) {
             // per-column Gram over the finite rows of each column (src/update_with_missing.cpp:90), then the solver
-            const int p_len = (which == 1) ? h->n : h->m;
-            {
-                int rcg = launch_na_gram(h, which, which == 1 ? h->miss : h->missT, (which == 1 ? h->npad : h->mpad) / 32, p_len, ncols, a.col0, a.ncols, !generic_rank(h));
-                if (rcg != NNLM_OK) return rcg;
-            }
+            int rcg = launch_na_gram(h, s, a.col0, a.ncols);
+            if (rcg != NNLM_OK) return rcg;
             a.Graw = h->Gcols;
-            a.g_upper = generic_rank(h) ? 0 : 1; // (what launch_na_gram was told to write: ranks <= 64 keep the upper triangle only)
             if (generic_rank(h)) {
                 int rcs = launch_sweep_generic(h, method, a, (size_t)h->KP * h->KP);
                 if (rcs != NNLM_OK) return rcs;
@@ -2616,7 +2523,7 @@ static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsig
             if (sg) { // the next half-step finds max and Gram partial sums of this factor
                 h->sg_nslabs = h->sweep_wgs; // (one slab per workgroup of the sweep launch)
                 h->sg_par ^= 1;
-                h->sg_which = which;
+                h->sg_which = s.which;
                 h->sg_other = h->sg_prev; // the word this sweep did not touch
             }
         }
@@ -2624,10 +2531,10 @@ static int half_step_solve(nnlm_handle *h, int which, const double reg[3], unsig
         if (h->sharded && phase == PH_B) return NNLM_OK; // test hooks: the caller gathers the slabs
     }
     if (h->sharded) {
-        int rc = pack_gather_unpack(h, which, phase);
+        int rc = pack_gather_unpack(h, s, phase);
         if (rc != NNLM_OK) return rc;
     }
-    if (which == 0 && !speculative) swap_w(h);
+    if (s.which == 0 && !speculative) swap_w(h);
     return NNLM_OK;
 }
 
@@ -2650,15 +2557,16 @@ extern "C" int nnlm_debug_partial(nnlm_handle *h, int which, double *G_out, doub
     // factors) and its slabs are folded here
     int rc = half_step(h, which, z, 0, 0.0, 1, true);
     if (rc != NNLM_OK) return rc;
-    const int ld = (which == 1) ? h->mpad : h->npad;
+    const Side s = side_of(h, which);
+    const int ld = s.ldc;
     if (!h->sharded) {
         const HalfPlan q = plan_half(h, which, 0, 1);
-        const size_t cnt = (size_t)h->KP * ld;
+        const size_t cnt = s.slab_stride;
         slab_reduce_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(h->Cx, q.S, cnt, h->red + (size_t)h->KP * h->KP);
     }
     sync_all(h);
     const int KP = h->KP, k = h->k;
-    const int cols = (which == 1) ? h->m : h->n;
+    const int cols = s.ncols;
     std::vector<double> buf((size_t)KP * KP + (size_t)KP * ld);
     HIPCHK(h, hipMemcpy(buf.data(), h->red, buf.size() * 8, hipMemcpyDeviceToHost));
     if (G_out)
@@ -2693,9 +2601,9 @@ extern "C" int nnlm_debug_exchange(nnlm_handle **hs, int P, int which, int stage
         HIPCHK(hs[r], hipSetDevice(hs[r]->device));
         sync_all(hs[r]);
     }
+    const Side s0 = side_of(h0, which);
     if (stage == 1) {
-        const int ld = (which == 1) ? h0->mpad : h0->npad;
-        const size_t cnt = (size_t)h0->KP * h0->KP + (size_t)h0->KP * ld;
+        const size_t cnt = (size_t)h0->KP * h0->KP + s0.slab_stride;
         std::vector<double> sum(cnt, 0.0), tmp(cnt);
         for (int r = 0; r < P; r++) {
             HIPCHK(hs[r], hipMemcpy(tmp.data(), hs[r]->red, cnt * 8, hipMemcpyDeviceToHost));
@@ -2703,8 +2611,7 @@ extern "C" int nnlm_debug_exchange(nnlm_handle **hs, int P, int which, int stage
         }
         for (int r = 0; r < P; r++) HIPCHK(hs[r], hipMemcpy(hs[r]->red, sum.data(), cnt * 8, hipMemcpyHostToDevice));
     } else {
-        const int ncols = (which == 1) ? h0->m : h0->n;
-        const ShardCols sc = shard_cols(h0, ncols);
+        const ShardCols sc = shard_cols(h0, s0.ncols);
         const size_t per = (size_t)h0->k * sc.cpr + h0->pack_tail; // (as the ncclAllGather call: the first k rows of the slab + its tail)
         std::vector<double> all(per * P);
         for (int r = 0; r < P; r++) HIPCHK(hs[r], hipMemcpy(all.data() + per * r, hs[r]->pack_send, per * 8, hipMemcpyDeviceToHost));
@@ -2782,17 +2689,7 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
         for (int f = 0; f < 2; f++) {
             const double *X = f == 0 ? h->W64 : h->H64;
             const int ld = f == 0 ? h->npad : h->mpad, cols = f == 0 ? n : m;
-            const int nb = (cols + GRAM_COLS_PER_BLOCK - 1) / GRAM_COLS_PER_BLOCK;
-            if (generic_rank(h)) {
-                dim3 grid(nb, h->NKQ * (h->NKQ + 1) / 2);
-                gram_partial_generic_kernel<<<grid, 256, 0, st>>>(X, ld, 0, cols, h->NKQ, h->sp_eslabs);
-            } else
-                switch (h->NKQ) {
-                case 1: gram_partial_kernel<1><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
-                case 2: gram_partial_kernel<2><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
-                case 3: gram_partial_kernel<3><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
-                default: gram_partial_kernel<4><<<nb, 256, 0, st>>>(X, ld, 0, cols, h->sp_eslabs, nullptr); break;
-                }
+            const int nb = launch_gram_partial(h, X, ld, 0, cols, h->sp_eslabs, nullptr, st);
             gram_reduce_kernel<<<(KP * KP + 255) / 256, 256, 0, st>>>(h->sp_eslabs, nb, KP, G + (size_t)f * KP * KP);
             const int rb = (cols + 2047) / 2048;
             nnlm_tu_sp_rowsums(X, ld, cols, KP, h->sp_epart, rb, st);
@@ -3050,8 +2947,8 @@ extern "C" int nnlm_shard_range(int n, int m, int precision, int which, int rank
     t.npad = round_up_i(n, NNLM_PAD_N);
     t.mpad = round_up_i(m, NNLM_PAD_M);
     const HalfPlan p = plan_half(&t, which, rank, nranks);
-    const int CE = stage_elems(&t, which);
-    const int lim = (which == 1) ? n : m;
+    const int CE = stage_elems(&t);
+    const int lim = side_of(&t, which).p;
     int c0 = p.stage_begin * CE, c1 = p.stage_end * CE;
     if (c1 > lim) c1 = lim;
     if (c0 > c1) c0 = c1;
