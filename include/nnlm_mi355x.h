@@ -180,10 +180,39 @@ int nnlm_take_sweeps(nnlm_handle *h, long long *sweeps, int reset);
 int nnlm_errors(nnlm_handle *h, double *mse, double *mkl_var, double pen[6]);
 int nnlm_sync(nnlm_handle *h);
 
+/* ------------------------------------------------------------------------------------------
+ * Batched factorisation: B independent nnmf() runs of ONE dense matrix (random restarts, rank sweeps) that share every pass over A.
+ * Member b has rank k[b] and its own factors; all members share the matrix and the arguments of nnlm_run.  1 <= B <= 64, sum of
+ * k[b] <= 64, methods 1 and 2 (square loss), dense A without missing entries, one GPU, no masks: anything else is refused with
+ * NNLM_ERR_UNSUPPORTED (KL loss, missing entries, a sparse A, a communicator, a rank sum beyond 64) or NNLM_ERR_ARG (B or a rank out
+ * of range).  Each member's factors, traces, n_iteration and warning are those nnlm_run gives for that member alone (same mode).
+ * ---------------------------------------------------------------------------------------- */
+/* k[B] ranks; W = the members' n x k[b] blocks one after another (column-major each), H = their k[b] x m blocks one after another;
+ * NULL = zeros.  Replaces the handle's factors (nnlm_set_factors ends a batch). */
+int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned *k, const double *W, const double *H);
+/* The members' factors, laid out as nnlm_set_factors_batch takes them. */
+int nnlm_get_factors_batch(nnlm_handle *h, double *W, double *H);
+/* nnlm_run for every member: the four traces are [B][nnlm_trace_capacity(max_iter, trace)] (member b's trace starts at
+ * b * capacity), n_trace, n_iteration and warned are [B].  A member whose stopping rule fires (its own target error) is frozen:
+ * its later sweeps are skipped.  The loop ends when every member has stopped or max_iter is reached.  Per half-step ONE
+ * cross product of A with the stacked factors; per trace iteration ONE pass over A for the error sums of all members. */
+int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int verbose,
+                   int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                   double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
+                   unsigned *n_iteration, int *warned, const nnlm_callbacks *cb);
+/* create + set_matrix + set_factors_batch + run_batch + get_factors_batch (precision as nnlm_c_nnmf).  W_init / H_init NULL: each
+ * member gets the default init of nnlm_c_nnmf, drawn member by member (W before H). */
+int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, const unsigned *k, const double *W_init, const double *H_init,
+                      const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int n_threads, int verbose,
+                      int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out,
+                      double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
+                      unsigned *n_iteration, int *warned, const nnlm_callbacks *cb);
+
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",
  * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack";
- * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block). */
+ * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block); batched factorisation: "batch_errors" (the one pass over A of a
+ * trace iteration), "batch_pen" (the members' penalty sums). */
 int nnlm_profile_enable(nnlm_handle *h, int on);
 int nnlm_profile_get(nnlm_handle *h, const char *name, double *total_ms, long long *launches);
 int nnlm_profile_reset(nnlm_handle *h);

@@ -4,4 +4,4 @@ Host-side mirror of the reference's R interface (nnmf, nnlm, predict_nnmf, mse_m
 libnnlm_mi355x.so.  There is no CPU fallback: without the HIP library and a gfx950 device every
 compute entry raises.
 """
-from ._lib import Handle, NnlmError, PREC_F32, PREC_F64, c_nnlm, c_nnmf, comm_unique_id, load, make_callbacks  # noqa: F401
+from ._lib import Handle, NnlmError, PREC_F32, PREC_F64, c_nnlm, c_nnmf, c_nnmf_batch, comm_unique_id, load, make_callbacks  # noqa: F401

@@ -15,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnnlm_mi355x.so")
 
 NNLM_OK = 0
+ERR_ARG = 1
+ERR_UNSUPPORTED = 5
+BATCH_MAX = 64  # members of one batched factorisation, and the largest sum of their ranks
 PREC_F32 = 0
 PREC_F64 = 1
 COMM_ID_BYTES = 128
@@ -31,6 +34,7 @@ EXPORTS = [
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
     "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
+    "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
 ]
 
 
@@ -139,6 +143,16 @@ def load():
     lib.nnlm_release_caches.argtypes = []
     lib.nnlm_get_info.restype = C.c_int
     lib.nnlm_get_info.argtypes = [vp, C.c_char_p, dp]
+    up = C.POINTER(C.c_uint)
+    lib.nnlm_set_factors_batch.restype = C.c_int
+    lib.nnlm_set_factors_batch.argtypes = [vp, C.c_uint, up, dp, dp]
+    lib.nnlm_get_factors_batch.restype = C.c_int
+    lib.nnlm_get_factors_batch.argtypes = [vp, dp, dp]
+    lib.nnlm_run_batch.restype = C.c_int
+    lib.nnlm_run_batch.argtypes = lib.nnlm_run.argtypes
+    lib.nnlm_c_nnmf_batch.restype = C.c_int
+    lib.nnlm_c_nnmf_batch.argtypes = [dp, C.c_int, C.c_int, C.c_uint, up, dp, dp, dp, dp, C.c_uint, C.c_double, C.c_int, C.c_int, C.c_int,
+                                      C.c_uint, C.c_double, C.c_int, C.c_uint, dp, dp, dp, dp, dp, dp, ip, up, ip, C.POINTER(Callbacks)]
     _lib = lib
     return lib
 
@@ -241,6 +255,75 @@ def c_nnmf(A, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbos
     return dict(W=np.ascontiguousarray(Wo), H=np.ascontiguousarray(Ho), mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(),
                 target_error=terr[:e].copy(), average_epoch=ep[:e].copy(), n_iteration=int(n_it.value),
                 warning=bool(warned.value))
+
+
+def _batch_ranks(ks):
+    ks = np.asarray(ks, dtype=np.int64).ravel()
+    if ks.size < 1 or ks.size > BATCH_MAX or np.any(ks < 1):
+        raise NnlmError(ERR_ARG, f"a batch needs 1..{BATCH_MAX} members of rank >= 1 (got ranks {ks.tolist()})")
+    return np.ascontiguousarray(ks, dtype=np.uint32)
+
+
+def _batch_blocks(X, shapes, what):
+    """Member blocks -> their column-major concatenation (the layout of nnlm_set_factors_batch), or None."""
+    if X is None:
+        return None
+    if len(X) != len(shapes):
+        raise NnlmError(ERR_ARG, f"{what}: {len(X)} blocks for {len(shapes)} members")
+    out = []
+    for b, (x, shp) in enumerate(zip(X, shapes)):
+        x = np.asarray(x, dtype=np.float64)
+        if x.shape != shp:
+            raise NnlmError(ERR_ARG, f"{what}[{b}] has shape {x.shape}, member {b} needs {shp}")
+        out.append(x.ravel(order="F"))
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def _batch_split(Wc, Hc, ks, n, m):
+    Ws, Hs, wo, ho = [], [], 0, 0
+    for k in (int(v) for v in ks):
+        Ws.append(np.ascontiguousarray(Wc[wo:wo + n * k].reshape((n, k), order="F")))
+        Hs.append(np.ascontiguousarray(Hc[ho:ho + k * m].reshape((k, m), order="F")))
+        wo, ho = wo + n * k, ho + k * m
+    return Ws, Hs
+
+
+def _batch_traces(ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned):
+    out = []
+    for b in range(len(ks)):
+        e, s = int(n_trace[b]), slice(b * cap, b * cap + int(n_trace[b]))
+        out.append(dict(mse_error=mse[s].copy(), mkl_error=mkl[s].copy(), target_error=terr[s].copy(), average_epoch=ep[s].copy(),
+                        n_iteration=int(n_it[b]), warning=bool(warned[b])))
+        assert len(out[-1]["mse_error"]) == e
+    return out
+
+
+def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
+                 trace, callbacks=None):
+    """Batched c_nnmf (nnlm_c_nnmf_batch): member b has rank ks[b] and starts from W[b] (n x k_b), H[b] (k_b x m) -- either list may
+    be None for the library's default init.  Returns one c_nnmf-style dict per member."""
+    lib = load()
+    A = _f64(A)
+    n, m = A.shape
+    ks = _batch_ranks(ks)
+    Wc = _batch_blocks(W, [(n, int(k)) for k in ks], "W")
+    Hc = _batch_blocks(H, [(int(k), m) for k in ks], "H")
+    B, K = len(ks), int(ks.sum())
+    al, be = _vec3(alpha), _vec3(beta)
+    cap = lib.nnlm_trace_capacity(int(max_iter), int(trace) if int(trace) > 0 else 1)
+    Wo, Ho = np.zeros(n * K), np.zeros(K * m)
+    mse, mkl, terr, ep = (np.zeros(B * cap) for _ in range(4))
+    n_trace, warned = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+    n_it = np.zeros(B, dtype=np.uint32)
+    rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, B, ks.ctypes.data_as(C.POINTER(C.c_uint)), _dp(Wc), _dp(Hc), _dp(al), _dp(be), int(max_iter),
+                               float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter), float(inner_rel_tol),
+                               int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace),
+                               n_it.ctypes.data_as(C.POINTER(C.c_uint)), _ip(warned), C.byref(callbacks) if callbacks is not None else None)
+    _check(rc)
+    out = _batch_traces(ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned)
+    for o, Wb, Hb in zip(out, *_batch_split(Wo, Ho, ks, n, m)):
+        o["W"], o["H"] = Wb, Hb
+    return out
 
 
 def c_nnlm(x, y, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
@@ -394,6 +477,35 @@ class Handle:
         e = n_trace.value
         return dict(mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(), target_error=terr[:e].copy(),
                     average_epoch=ep[:e].copy(), n_iteration=int(n_it.value), warning=bool(warned.value))
+
+    def set_factors_batch(self, ks, W=None, H=None):
+        """Batched factorisation: member b has rank ks[b] and factors W[b] (n x k_b), H[b] (k_b x m); None = zeros."""
+        ks = _batch_ranks(ks)
+        Wc = _batch_blocks(W, [(self.n, int(k)) for k in ks], "W")
+        Hc = _batch_blocks(H, [(int(k), self.m) for k in ks], "H")
+        self._ck(self._lib.nnlm_set_factors_batch(self._h, len(ks), ks.ctypes.data_as(C.POINTER(C.c_uint)), _dp(Wc), _dp(Hc)))
+        self.k, self.ks = int(ks.sum()), [int(k) for k in ks]
+
+    def get_factors_batch(self):
+        """[(W_b, H_b)] of the members."""
+        Wc, Hc = np.zeros(self.n * self.k), np.zeros(self.k * self.m)
+        self._ck(self._lib.nnlm_get_factors_batch(self._h, _dp(Wc), _dp(Hc)))
+        return list(zip(*_batch_split(Wc, Hc, self.ks, self.n, self.m)))
+
+    def run_batch(self, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace,
+                  callbacks=None):
+        """nnlm_run for every member of the batch: one trace dict per member."""
+        a, b = _vec3(alpha), _vec3(beta)
+        B = len(self.ks)
+        cap = self._lib.nnlm_trace_capacity(int(max_iter), int(trace) if int(trace) > 0 else 1)
+        mse, mkl, terr, ep = (np.zeros(B * cap) for _ in range(4))
+        n_trace, warned = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        n_it = np.zeros(B, dtype=np.uint32)
+        self._ck(self._lib.nnlm_run_batch(self._h, _dp(a), _dp(b), int(max_iter), float(rel_tol), int(verbose), int(bool(show_warning)),
+                                          int(inner_max_iter), float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(mse),
+                                          _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace), n_it.ctypes.data_as(C.POINTER(C.c_uint)),
+                                          _ip(warned), C.byref(callbacks) if callbacks is not None else None))
+        return _batch_traces(self.ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned)
 
     def take_sweeps(self, reset=True):
         v = C.c_longlong(0)

@@ -245,36 +245,54 @@ class NnmfResult(dict):
                     int(np.sum(self["average_epochs"])), self["n_iteration"]))
 
 
+def _nnmf_matrix(A, loss):
+    """The matrix part of prepare_nnmf: A checked and converted once (dense: fp64; sparse: canonical CSC), its shape, and the largest
+    k the check_k rule allows (min(n, m), less where rows or columns have missing entries)."""
+    if is_sparse(A):  # canonical CSC (args[0]); absent entries are zeros, so there is nothing missing
+        A = _sparse_input(A, "A", loss)
+        n, m = A.shape
+        return dict(A=A, n=n, m=m, min_k=min(n, m))
+    A = np.asarray(A)
+    if A.ndim != 2:
+        raise NnlmStop("A must be a matrix")
+    check_matrix(A, input_name="A")
+    A = np.asarray(A, dtype=np.float64)
+    n, m = A.shape
+    min_k = min(n, m)
+    isna = np.isnan(A)
+    if isna.any():
+        min_k = min(min_k, int((m - isna.sum(axis=1)).min()), int((n - isna.sum(axis=0)).min()))
+    return dict(A=A, n=n, m=m, min_k=min_k)
+
+
 def prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
                  check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None):
     """Argument normalisation of nnmf(), R/nnmf.R:142-183 -> (17-tuple for c_nnmf, context dict)."""
+    args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace,
+                                 verbose, show_warning, inner_max_iter, inner_rel_tol, rng)
+    return args, ctx
+
+
+def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
+                  check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
+                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None, matrix=None):
+    """prepare_nnmf, also returning the checked matrix; `matrix` = what an earlier call returned for the same A (nnmf_batch: the
+    members share one checked, converted A)."""
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
     if inner_max_iter is None:
         inner_max_iter = 50 if loss == "mse" else 1  # R/nnmf.R:139
     if trace is None:
         trace = 100 / inner_max_iter  # R/nnmf.R:138
-    sparse = is_sparse(A)
-    if sparse:  # canonical CSC (args[0]); absent entries are zeros, so there is nothing missing
-        A = _sparse_input(A, "A", loss)
-        n, m = A.shape
-    else:
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise NnlmStop("A must be a matrix")
-        check_matrix(A, input_name="A")
-        A = np.asarray(A, dtype=np.float64)
-        n, m = A.shape
+    mat = matrix if matrix is not None else _nnmf_matrix(A, loss)
+    A, n, m = mat["A"], mat["n"], mat["m"]
     im = reformat_input(init, mask, n, m, int(k), rng=rng)
     K = im["K"]
     alpha = np.concatenate([np.atleast_1d(np.asarray(alpha, dtype=np.float64)), np.zeros(3)])[:3]
     beta = np.concatenate([np.atleast_1d(np.asarray(beta, dtype=np.float64)), np.zeros(3)])[:3]
     code = get_method_code(method, loss)
-    min_k = min(n, m)
-    isna = None if sparse else np.isnan(A)
-    if isna is not None and isna.any():
-        min_k = min(min_k, int((m - isna.sum(axis=1)).min()), int((n - isna.sum(axis=0)).min()))
+    min_k = mat["min_k"]
     if check_k and K > min_k and np.all(np.concatenate([alpha, beta]) == 0):
         raise NnlmStop("k larger than %d is not recommended, unless properly masked or regularized.\n"
                        "\t\t\t\tSet check.k = FALSE if you want to skip this checking." % min_k)
@@ -288,7 +306,7 @@ def prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="ms
     ctx = dict(method=method, loss=loss, alpha=alpha, beta=beta, init=init, mask=mask, n_threads=n_threads, trace=trace,
                verbose=verbose, max_iter=max_iter, rel_tol=rel_tol, inner_max_iter=inner_max_iter,
                inner_rel_tol=inner_rel_tol, W_norm=W_norm)
-    return args, ctx
+    return args, ctx, mat
 
 
 def finish_nnmf(out, ctx, run_time=None):
@@ -329,6 +347,81 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     else:
         out = _lib.c_nnmf(*args, callbacks=cb)
     return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
+
+
+def _batch_rank_list(k, nrun):
+    """nnmf_batch's members: every rank of k (an int or a sequence) nrun times, rank after rank."""
+    try:
+        ranks = [int(k)] if np.ndim(k) == 0 else [int(v) for v in k]
+        nrun = int(nrun)
+    except (TypeError, ValueError):
+        raise _lib.NnlmError(_lib.ERR_ARG, "k must be an integer or a sequence of integers, nrun an integer") from None
+    ks = [r for r in ranks for _ in range(nrun)]
+    if not ks or min(ks) < 1 or nrun < 1 or len(ks) > _lib.BATCH_MAX:
+        raise _lib.NnlmError(_lib.ERR_ARG, "a batch needs 1..%d members of rank >= 1 (k = %s, nrun = %d)" % (_lib.BATCH_MAX, ranks, nrun))
+    return ks
+
+
+def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
+    """Several nnmf() runs of one dense matrix at once: random restarts (nrun) and rank sweeps (k a sequence) share every pass over A.
+
+    Member list: each rank of ``k`` gets ``nrun`` members, rank after rank (k = [2, 3], nrun = 2 -> ranks 2, 2, 3, 3).  ``init`` is None
+    or one ``{"W": n x k_b, "H": k_b x m}`` dict per member (either entry may be missing); what is not given is drawn from ``rng``
+    member by member exactly as nnmf() draws it.  ``nnmf_options`` are nnmf()'s other arguments, shared by all members.
+    Each member's result is what nnmf() returns for that member alone.  Returns (list of per-member nnmf results, index of the member
+    with the smallest final target error).
+
+    Square loss only, dense A without missing entries, no masks or known profiles, ranks summing to at most 64: anything else raises
+    NnlmError with code NNLM_ERR_UNSUPPORTED; a bad k list or an init that does not match it, NNLM_ERR_ARG.
+    """
+    ks = _batch_rank_list(k, nrun)
+    B = len(ks)
+    if init is not None:
+        if isinstance(init, dict) or len(init) != B:
+            raise _lib.NnlmError(_lib.ERR_ARG, "init must be a list of %d dicts {'W': ..., 'H': ...}, one per member" % B)
+        init = [dict(x) if x is not None else {} for x in init]
+    unsupported = lambda msg: _lib.NnlmError(_lib.ERR_UNSUPPORTED, "nnmf_batch: " + msg)
+    if not _is_empty(nnmf_options.get("mask")) and any(not _is_empty(v) for v in dict(nnmf_options["mask"]).values()):
+        raise unsupported("masks are not supported by the batched factorisation")
+    if init is not None and any(x.get("W0") is not None or x.get("H0") is not None for x in init):
+        raise unsupported("known profiles (W0 / H0) are not supported by the batched factorisation")
+    if _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss") != "mse":
+        raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
+    if is_sparse(A):
+        raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    if sum(ks) > _lib.BATCH_MAX:
+        raise unsupported("the ranks sum to %d; a batch holds at most %d" % (sum(ks), _lib.BATCH_MAX))
+    shape = A.shape if isinstance(A, np.ndarray) else np.shape(A)
+    if init is not None and len(shape) == 2:
+        n, m = shape
+        for b, x in enumerate(init):
+            for key, shp in (("W", (n, ks[b])), ("H", (ks[b], m))):
+                if x.get(key) is not None and np.shape(x[key]) != shp:
+                    raise _lib.NnlmError(_lib.ERR_ARG, "init[%d]['%s'] has shape %s, member %d (rank %d) needs %s"
+                                         % (b, key, np.shape(x[key]), b, ks[b], shp))
+    opts = dict(nnmf_options)
+    opts.setdefault("verbose", 0)
+    g = rng or np.random.default_rng()
+    prep, Ws, Hs, mat = [], [], [], None
+    for b in range(B):  # member after member, each consuming the generator as nnmf() would
+        # (A is checked and converted by the first member's call only: every member shares that one fp64 copy)
+        args, ctx, mat = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
+        if b == 0 and not np.isfinite(mat["A"]).all():
+            raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
+        n, m = mat["n"], mat["m"]
+        W, H = args[2], args[3]
+        # (what nnmf() leaves empty, c_nnmf draws through unif_rand: 0.01 U(0,1), W row by row first, then H column-major)
+        Ws.append(W if np.size(W) else 0.01 * g.random(n * ks[b]).reshape((n, ks[b])))
+        Hs.append(H if np.size(H) else 0.01 * g.random(ks[b] * m).reshape((ks[b], m), order="F"))
+        prep.append((args, ctx))
+    a0 = prep[0][0]
+    cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
+    t0 = time.perf_counter()
+    outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+    run_time = time.perf_counter() - t0
+    res = [finish_nnmf(o, p[1], run_time=run_time) for o, p in zip(outs, prep)]
+    best = int(np.argmin([r["target_loss"][-1] if len(r["target_loss"]) else np.inf for r in res]))
+    return res, best
 
 
 # ------------------------------------------------------------------------------------------------

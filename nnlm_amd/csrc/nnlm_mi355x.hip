@@ -11,6 +11,7 @@
 //   penalties()      <- add_penalty()     src/nnmf.cpp:224-240
 #include "../../include/nnlm_mi355x.h"
 #include "common.h"
+#include "k_batch.h"
 #include "k_errors.h"
 #include "k_generic.h"
 #include "k_gram.h"
@@ -41,7 +42,7 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_COUNT };
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -49,8 +50,10 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  fused cross product left behind -- 5 us, no HBM work: it must not be priced as a pass over A
 //  "spmm_h" / "spmm_w": the cross products of a sparse A (row copy of the fixed factor + spmm_kernel + its fix-up); "sp_errors": the error
 //  block of a sparse A (sums over the non-zeros, the two Grams and the factors' sums)
+//  "batch_errors": the error block of a batched factorisation (errors_batch_kernel + its reduction: one pass over A for all members);
+//  "batch_pen": its per-member penalty sums
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors"};
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen"};
 
 struct ProfRec {
     int id;
@@ -175,6 +178,17 @@ struct nnlm_handle {
     bool err_hook = false, err_need_pen = true, err_launched = false;
     unsigned *err_zero_word = nullptr; // the fused kernel clears this word (max|x| of the sweep that follows it; see factor16_fold_err_kernel)
     unsigned long long *sweeps_tmp = nullptr; // device scratch for the all-reduced sweep counter
+
+    // batched factorisation (nnlm_set_factors_batch): bB members stacked in the factor buffers, member b owns rows boff[b] .. boff[b+1]-1;
+    // the factor buffers then carry row_pad zero rows behind their KP (the per-member Gram kernels read 16 ceil(k_b / 16) rows from off_b)
+    int bB = 0, row_pad = 0;
+    std::vector<int> bk, boff;
+    int *boff_dev = nullptr;                // [bB + 1]
+    double *bG = nullptr;                   // [bB][64 * 64] per-member Grams
+    unsigned long long *bsweeps = nullptr;  // [bB] per-member sweep counters
+    double *bpart = nullptr;                // partial sums of the batched error block / penalties
+    size_t bpart_elems = 0;
+    double *bres = nullptr;                 // [8 bB]: {sum sq, sum KL} per member, then 3 W and 3 H penalty sums per member
 
     // profiling
     bool prof = false;
@@ -569,8 +583,25 @@ static void invalidate_factor_caches(nnlm_handle *h)
     h->pack_ready = false;
 }
 
+static void free_batch(nnlm_handle *h)
+{
+    hipFree(h->boff_dev);
+    hipFree(h->bG);
+    hipFree(h->bsweeps);
+    hipFree(h->bpart);
+    hipFree(h->bres);
+    h->boff_dev = nullptr;
+    h->bG = h->bpart = h->bres = nullptr;
+    h->bsweeps = nullptr;
+    h->bpart_elems = 0;
+    h->bB = 0;
+    h->bk.clear();
+    h->boff.clear();
+}
+
 static void free_factors(nnlm_handle *h)
 {
+    free_batch(h);
     for (int i = 0; i < 2; i++) {
         if (h->Wopb[i] && h->Wopb[i] != (void *)h->W64b[i]) hipFree(h->Wopb[i]);
         hipFree(h->W64b[i]);
@@ -1132,33 +1163,34 @@ static void pack_mask_cols(const int *mask, int k, int ncols, bool transposed_in
         }
 }
 
-extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, const double *H, const int *Wm, const int *Hm)
+// row_pad: zero rows behind the KP rows of the masters W64b / H64 (a batched factorisation reads up to 63 rows past a member's last)
+static int set_factors_impl(nnlm_handle *h, int k, const double *W, const double *H, const int *Wm, const int *Hm, int row_pad)
 {
-    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
-    const int k = (int)k_;
-    if (k < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: rank k must be >= 1");
     HIPCHK(h, hipSetDevice(h->device));
     sync_all(h);
     invalidate_factor_caches(h);
+    free_batch(h);
     HIPCHK(h, hipMemset(h->maxbits + 8, 0, sizeof(unsigned)));
-    if (k != h->k) {
+    if (k != h->k || row_pad != h->row_pad) {
         free_factors(h);
         h->k = k;
+        h->row_pad = row_pad;
         h->NKQ = (k + 15) / 16; // > 4 beyond rank 64: the generic kernels of k_generic.h take over
         h->KP = 16 * h->NKQ;
         h->KP8 = round_up_i(k, 8);
         h->MW = (k + 63) / 64;
         const size_t es = esize(h);
         for (int i = 0; i < 2; i++) {
-            HIPCHK(h, hipMalloc(&h->W64b[i], (size_t)h->KP * h->npad * 8));
-            HIPCHK(h, hipMemset(h->W64b[i], 0, (size_t)h->KP * h->npad * 8));
+            HIPCHK(h, hipMalloc(&h->W64b[i], (size_t)(h->KP + row_pad) * h->npad * 8));
+            HIPCHK(h, hipMemset(h->W64b[i], 0, (size_t)(h->KP + row_pad) * h->npad * 8));
             if (h->prec == NNLM_PREC_F64) h->Wopb[i] = h->W64b[i];
             else {
                 HIPCHK(h, hipMalloc(&h->Wopb[i], (size_t)h->KP * h->npad * es));
                 HIPCHK(h, hipMemset(h->Wopb[i], 0, (size_t)h->KP * h->npad * es));
             }
         }
-        HIPCHK(h, hipMalloc(&h->H64, (size_t)h->KP * h->mpad * 8));
+        HIPCHK(h, hipMalloc(&h->H64, (size_t)(h->KP + row_pad) * h->mpad * 8));
+        if (row_pad) HIPCHK(h, hipMemset(h->H64 + (size_t)h->KP * h->mpad, 0, (size_t)row_pad * h->mpad * 8));
         if (h->prec == NNLM_PREC_F32) HIPCHK(h, hipMalloc(&h->Hkq, (size_t)h->KP * h->mpad * sizeof(float)));
         HIPCHK(h, hipMalloc(&h->Wmask, (size_t)h->npad * h->MW * 8));
         HIPCHK(h, hipMalloc(&h->Hmask, (size_t)h->mpad * h->MW * 8));
@@ -1226,6 +1258,14 @@ extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, co
         HIPCHK(h, hipMemcpy(h->Hmask, mk.data(), (size_t)mpad * h->MW * 8, hipMemcpyHostToDevice));
     }
     return NNLM_OK;
+}
+
+extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, const double *H, const int *Wm, const int *Hm)
+{
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
+    const int k = (int)k_;
+    if (k < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: rank k must be >= 1");
+    return set_factors_impl(h, k, W, H, Wm, Hm, 0);
 }
 
 extern "C" int nnlm_get_factors(nnlm_handle *h, double *W, double *H)
@@ -3179,6 +3219,357 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
     *n_iteration = i;
     *warned = (show_warning && rel_err > rel_tol) ? 1 : 0; // src/nnmf.cpp:208
     if (*warned && cb && cb->warning) cb->warning(cb->ctx, "Target tolerance not reached. Try a larger max.iter.");
+    return NNLM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// batched factorisation: B independent square-loss models of one dense matrix, ranks k_b with sum <= 64, stacked
+// in the factor buffers.  Per half-step ONE cross product of A with the stacked fixed factor (rows off_b .. off_b + k_b - 1 of its
+// slabs are member b's), then per active member the Gram of ITS rows of the fixed factor and the existing sweep on its row block of
+// Cx / X (pointer offsets; every sweep kernel reads and writes rows q < a.k only).  Per trace iteration one errors_batch_kernel pass.
+// ---------------------------------------------------------------------------------------------
+static int batch_refusal(nnlm_handle *h, const char *who)
+{
+    if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
+    if (h->any_missing) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
+    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the batched factorisation runs on one GPU (no communicator)", who);
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned *k, const double *W, const double *H)
+{
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: set the matrix first");
+    if (B < 1 || B > BATCH_MAX || !k) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: need 1 <= B <= %d members and their ranks (B = %u)", BATCH_MAX, B);
+    long K = 0;
+    for (unsigned b = 0; b < B; b++) {
+        if (k[b] < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: rank of member %u must be >= 1", b);
+        K += k[b];
+    }
+    int rc = batch_refusal(h, "nnlm_set_factors_batch");
+    if (rc != NNLM_OK) return rc;
+    if (K > NNLM_KQ_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_factors_batch: the ranks sum to %ld; a batch holds at most %d", K, NNLM_KQ_MAX);
+    const int m = h->m;
+    std::vector<int> off(B + 1, 0);
+    for (unsigned b = 0; b < B; b++) off[b + 1] = off[b] + (int)k[b];
+    // H arrives as the members' k_b x m blocks one after another: the stacked K x m matrix, column-major
+    std::vector<double> Hs;
+    if (H) {
+        Hs.assign((size_t)K * m, 0.0);
+        size_t src = 0;
+        for (unsigned b = 0; b < B; b++) {
+            for (int j = 0; j < m; j++)
+                for (unsigned q = 0; q < k[b]; q++) Hs[(size_t)j * K + off[b] + q] = H[src + (size_t)j * k[b] + q];
+            src += (size_t)k[b] * m;
+        }
+    }
+    // (W: the members' n x k_b blocks one after another ARE the stacked n x K matrix)
+    rc = set_factors_impl(h, (int)K, W, H ? Hs.data() : nullptr, nullptr, nullptr, 64);
+    if (rc != NNLM_OK) return rc;
+    h->bB = (int)B;
+    h->bk.assign(k, k + B);
+    h->boff = off;
+    const int nit = h->npad / 64, mt = (h->m + 63) / 64;
+    const int nch = mt < 1 ? 1 : (mt < (1024 + nit - 1) / nit ? mt : (1024 + nit - 1) / nit);
+    const size_t eparts = (size_t)2 * B * nit * nch, pparts = (size_t)3 * B * (((h->n > h->m ? h->n : h->m) + 255) / 256);
+    h->bpart_elems = eparts > pparts ? eparts : pparts;
+    HIPCHK(h, hipMalloc(&h->boff_dev, (B + 1) * sizeof(int)));
+    HIPCHK(h, hipMemcpy(h->boff_dev, off.data(), (B + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(h, hipMalloc(&h->bG, (size_t)B * 64 * 64 * 8));
+    HIPCHK(h, hipMalloc(&h->bsweeps, B * sizeof(unsigned long long)));
+    HIPCHK(h, hipMemset(h->bsweeps, 0, B * sizeof(unsigned long long)));
+    HIPCHK(h, hipMalloc(&h->bpart, h->bpart_elems * 8));
+    HIPCHK(h, hipMalloc(&h->bres, (size_t)8 * B * 8));
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_get_factors_batch(nnlm_handle *h, double *W, double *H)
+{
+    if (!h || !h->bB) return fail(h, NNLM_ERR_ARG, "nnlm_get_factors_batch: no batch set");
+    const int K = h->k, m = h->m;
+    std::vector<double> Hs;
+    if (H) Hs.resize((size_t)K * m);
+    int rc = nnlm_get_factors(h, W, H ? Hs.data() : nullptr);
+    if (rc != NNLM_OK || !H) return rc;
+    size_t dst = 0;
+    for (int b = 0; b < h->bB; b++) {
+        const int kb = h->bk[b], o = h->boff[b];
+        for (int j = 0; j < m; j++)
+            for (int q = 0; q < kb; q++) H[dst + (size_t)j * kb + q] = Hs[(size_t)j * K + o + q];
+        dst += (size_t)kb * m;
+    }
+    return NNLM_OK;
+}
+
+// One half-step of every active member (act[b] != 0).  W is solved in place (no speculation, so no second buffer): a frozen member's
+// rows are never written.
+static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+                           const std::vector<char> &act)
+{
+    g_attr_err = hipSuccess;
+    Side s = side_of(h, which);
+    if (which == 0) {
+        s.Xout = const_cast<double *>(s.X);
+        s.op = h->Wop;
+    }
+    h->sg_which = h->sg_other = -1;
+    h->sg_request = false;
+    h->fuse_err = false;
+    h->cur_which = which;
+    const HalfPlan p = plan_half(h, which, 0, 1);
+    // 1. one cross product for all members: split-fp16 copy of the whole stacked factor (ONE scale, max over all members), then the
+    //    A-streaming kernel exactly as a rank-K solo half-step launches it
+    if (h->x16) prepare_factor16(h, s);
+    else if (which == 0) {
+        int rca = ensure_AT(h);
+        if (rca != NNLM_OK) return rca;
+    }
+    {
+        // (strict mode: always the whole-tile instantiation, never the VALU tail rows of launch_xprod_nkq -- every row of the slabs is then
+        //  formed by the same MFMA sequence wherever its member sits, and a member's result does not depend on its neighbours)
+        ProfScope ps(h, s.prof_xprod);
+        if (h->x16) with_nkq(h->NKQ, [&](auto N) { launch_xprod16_m<N>(h, s, p); });
+        else
+            with_nkq(h->NKQ, [&](auto N) {
+                launch_xprod_tn<double, N, 0>(h, (const double *)a_contig(h, s), s.ldy, s.Y, s.ldy, h->Cx, s.ldc, s.slab_stride, p);
+            });
+    }
+    // 2. + 3. per member: Gram of its own rows of the fixed factor, then its sweep -- launched as a solo rank-k_b half-step launches them
+    const int K = h->k, NKQ = h->NKQ, KP = h->KP, KP8 = h->KP8, MW = h->MW;
+    const size_t es = esize(h);
+    int rc = NNLM_OK;
+    for (int b = 0; b < h->bB && rc == NNLM_OK; b++) {
+        if (!act[b]) continue;
+        const int kb = h->bk[b], o = h->boff[b];
+        h->k = kb, h->NKQ = (kb + 15) / 16, h->KP = 16 * h->NKQ, h->KP8 = round_up_i(kb, 8), h->MW = 1;
+        double *G = h->bG + (size_t)b * 64 * 64;
+        {
+            ProfScope ps(h, P_GRAM);
+            const int nb = launch_gram_partial(h, s.Y + (size_t)o * s.ldy, s.ldy, 0, s.p, h->gslabs, nullptr, h->stream);
+            gram_fold_kernel<<<h->KP * h->KP / 64, 1024, 0, h->stream>>>(h->gslabs, nb, h->KP, G, SweepImg{});
+        }
+        SweepArgs a;
+        a.Graw = G;
+        a.KPg = h->KP;
+        a.Cx = h->Cx + (size_t)o * s.ldc;
+        a.slab_stride = s.slab_stride;
+        a.nslabs = p.S;
+        a.k = kb;
+        a.r0 = reg[0], a.r1 = reg[1], a.r2 = reg[2];
+        a.max_iter = inner_max_iter;
+        a.rel_tol = inner_rel_tol;
+        a.sweeps = h->bsweeps + b;
+        a.col0 = a.ocol0 = 0;
+        a.X = s.X + (size_t)o * s.ldc;
+        a.Xout = s.Xout + (size_t)o * s.ldc;
+        a.ldx = a.ldo = a.ldc = s.ldc;
+        a.ncols = s.ncols;
+        a.mask = nullptr;
+        a.op = s.op ? (void *)((char *)s.op + (size_t)o * s.op_ld * es) : nullptr;
+        a.op_mode = s.op ? s.op_mode : 0;
+        a.op_ld = s.op_ld;
+        a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
+        h->pack_ready = false; // (strict mode: the sweep packs its operand image from this member's Gram)
+        ProfScope ps(h, s.prof_sweep);
+        rc = launch_sweep(h, method, a);
+    }
+    h->k = K, h->NKQ = NKQ, h->KP = KP, h->KP8 = KP8, h->MW = MW;
+    h->pack_ready = false;
+    if (rc != NNLM_OK) return rc;
+    LAUNCHCHK(h);
+    return NNLM_OK;
+}
+
+// Error block of every member with amask bit b set: res[2b], res[2b+1] = sum of squares / KL sum, res[2B + 3b ..] and res[5B + 3b ..]
+// the W and H penalty sums (zeros when !need_pen), sw[b] = member b's sweep counter (then cleared).  Synchronises.
+static int batch_errors(nnlm_handle *h, unsigned long long amask, bool need_pen, std::vector<double> &res, std::vector<long long> &sw)
+{
+    const int B = h->bB;
+    hipStream_t st = h->stream;
+    {
+        ProfScope ps(h, P_BATCH_ERRORS, st);
+        const int nit = h->npad / 64, mt = (h->m + 63) / 64;
+        const int nch = mt < 1 ? 1 : (mt < (1024 + nit - 1) / nit ? mt : (1024 + nit - 1) / nit);
+        const int nblk = nit * nch;
+        dim3 grid(nit, nch);
+        if (h->prec == NNLM_PREC_F64)
+            errors_batch_kernel<double><<<grid, 256, 0, st>>>((const double *)h->A, h->npad, h->W64, h->npad, h->H64, h->mpad, h->n, h->m, h->boff_dev,
+                                                             B, amask, h->bpart, nblk);
+        else
+            errors_batch_kernel<float><<<grid, 256, 0, st>>>((const float *)h->A, h->npad, h->W64, h->npad, h->H64, h->mpad, h->n, h->m, h->boff_dev,
+                                                            B, amask, h->bpart, nblk);
+        batch_reduce_kernel<<<2 * B, 256, 0, st>>>(h->bpart, nblk, h->bres);
+    }
+    if (need_pen) {
+        ProfScope ps(h, P_BATCH_PEN, st);
+        for (int f = 0; f < 2; f++) {
+            const int cols = f == 0 ? h->n : h->m, nbx = (cols + 255) / 256;
+            batch_penalty_kernel<<<dim3(nbx, B), 256, 0, st>>>(f == 0 ? h->W64 : h->H64, f == 0 ? h->npad : h->mpad, cols, h->boff_dev, h->bpart);
+            batch_reduce_kernel<<<3 * B, 256, 0, st>>>(h->bpart, nbx, h->bres + (size_t)(2 + 3 * f) * B);
+        }
+    } else
+        HIPCHK(h, hipMemsetAsync(h->bres + 2 * B, 0, (size_t)6 * B * 8, st));
+    res.resize((size_t)8 * B);
+    std::vector<unsigned long long> v(B);
+    HIPCHK(h, hipMemcpyAsync(res.data(), h->bres, (size_t)8 * B * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(v.data(), h->bsweeps, B * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemsetAsync(h->bsweeps, 0, B * sizeof(unsigned long long), st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    LAUNCHCHK(h);
+    sw.assign(B, 0);
+    for (int b = 0; b < B; b++) sw[b] = (long long)v[b];
+    return NNLM_OK;
+}
+
+// The alternating loop of c_nnmf (src/nnmf.cpp:100-209) for every member at once.  Member b stops when ITS stopping rule fires (its own
+// target error, src/nnmf.cpp:153); from then on its sweeps are skipped and its trace, n_iteration and warning stay what a solo run's are.
+// Outputs: [B][capacity] traces (capacity = nnlm_trace_capacity(max_iter, trace)), [B] n_trace / n_iteration / warned.
+extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int verbose,
+                              int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                              double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
+                              unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
+{
+    if (!h || !h->bB) return fail(h, NNLM_ERR_ARG, "nnlm_run_batch: set the matrix and a batch of factors (nnlm_set_factors_batch) first");
+    if (!alpha || !beta || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace || !n_iteration || !warned)
+        return fail(h, NNLM_ERR_ARG, "nnlm_run_batch: NULL argument");
+    if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
+    if (method >= 3) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_run_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
+    int rc = batch_refusal(h, "nnlm_run_batch");
+    if (rc != NNLM_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->device));
+    sync_all(h);
+    const int B = h->bB, n = h->n, m = h->m;
+    if (trace < 1) trace = 1;
+    const unsigned cap = nnlm_trace_capacity(max_iter, trace);
+    const double N = h->n_non_missing;
+    for (size_t e = 0; e < (size_t)B * cap; e++) mkl_error[e] = h->kl_const;
+    const bool need_pen = alpha[0] != alpha[1] || beta[0] != beta[1] || alpha[1] != 0 || beta[1] != 0 || alpha[2] != 0 || beta[2] != 0;
+    std::vector<double> rel_err(B, rel_tol + 1), terr_last(B, 1e99);
+    std::vector<unsigned> i_e(B, 0), nit(B, 0);
+    std::vector<char> act(B, 1);
+    std::vector<double> res;
+    std::vector<long long> sw;
+    auto book = [&](int b, unsigned it) {
+        const size_t e = (size_t)b * cap + i_e[b];
+        mse_error[e] = res[2 * b] / N;
+        mkl_error[e] += res[2 * b + 1] / N;
+        average_epoch[e] = (double)sw[b] / (double)(n + m); // src/nnmf.cpp:145
+        double pen[6];
+        for (int c = 0; c < 3; c++) pen[c] = res[2 * B + 3 * b + c], pen[3 + c] = res[5 * B + 3 * b + c];
+        const double t = penalties(0.5 * mse_error[e], pen, N, alpha, beta);
+        target_error[e] = t;
+        rel_err[b] = 2 * (terr_last[b] - t) / (terr_last[b] + t + NNLM_TINY); // src/nnmf.cpp:153
+        terr_last[b] = t;
+        if (verbose == 2) cb_print(cb, "%6d %10d | %10.4f | %10.4f | %10.4f | %10.g\n", b, it + 1, mse_error[e], mkl_error[e], t, rel_err[b]);
+        ++i_e[b];
+    };
+    auto mask_of = [&](const std::vector<char> &f) {
+        unsigned long long mk = 0;
+        for (int b = 0; b < B; b++)
+            if (f[b]) mk |= 1ull << b;
+        return mk;
+    };
+    if (verbose == 2) {
+        cb_print(cb, "\n%6s %10s | %10s | %10s | %10s | %10s\n", "Member", "Iteration", "MSE", "MKL", "Target", "Rel. Err.");
+        cb_print(cb, "---------------------------------------------------------------------\n");
+    }
+    unsigned i = 0;
+    for (; i < max_iter && mask_of(act); i++) {
+        if (cb && cb->check_interrupt && cb->check_interrupt(cb->ctx)) {
+            sync_all(h);
+            return fail(h, NNLM_ERR_INTERRUPT, "interrupted");
+        }
+        if (verbose == 1 && cb && cb->progress) cb->progress(cb->ctx, i + 1, max_iter);
+        CHK(batch_half_step(h, 0, alpha, inner_max_iter, inner_rel_tol, method, act)); // update W, src/nnmf.cpp:131
+        CHK(batch_half_step(h, 1, beta, inner_max_iter, inner_rel_tol, method, act));  // update H, src/nnmf.cpp:133
+        if (i % trace == 0) {
+            CHK(batch_errors(h, mask_of(act), need_pen, res, sw));
+            for (int b = 0; b < B; b++) {
+                if (!act[b]) continue;
+                book(b, i);
+                if (!(std::fabs(rel_err[b]) > rel_tol)) { // src/nnmf.cpp:109: this member's loop ends after iteration i
+                    act[b] = 0;
+                    nit[b] = i + 1;
+                }
+            }
+        }
+    }
+    // members still running reached max_iter: the last trace entry of src/nnmf.cpp:164 (unsigned arithmetic)
+    std::vector<char> last(B, 0);
+    for (int b = 0; b < B; b++)
+        if (act[b]) {
+            nit[b] = i;
+            last[b] = ((unsigned)(i - 1) % trace != 0);
+        }
+    if (mask_of(last)) {
+        CHK(batch_errors(h, mask_of(last), need_pen, res, sw));
+        for (int b = 0; b < B; b++)
+            if (last[b]) book(b, i);
+    }
+    sync_all(h);
+    LAUNCHCHK(h);
+    for (int b = 0; b < B; b++) {
+        n_trace[b] = (int)i_e[b];
+        n_iteration[b] = nit[b];
+        warned[b] = (show_warning && rel_err[b] > rel_tol) ? 1 : 0; // src/nnmf.cpp:208
+        if (warned[b] && cb && cb->warning) cb->warning(cb->ctx, "Target tolerance not reached. Try a larger max.iter.");
+    }
+    return NNLM_OK;
+}
+
+// create + set_matrix + set_factors_batch + run_batch + get_factors_batch.  W_init / H_init: the members' n x k_b / k_b x m blocks one
+// after another, or NULL for the default 0.01 U(0,1) init of each member (drawn member by member, W before H, as c_nnmf draws it).
+extern "C" int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, const unsigned *k, const double *W_init, const double *H_init,
+                                 const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int n_threads, int verbose,
+                                 int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out,
+                                 double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
+                                 unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!A || !k || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
+        !n_iteration || !warned)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: NULL argument");
+    if (B < 1 || B > BATCH_MAX) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: need 1 <= B <= %d members (B = %u)", BATCH_MAX, B);
+    long K = 0;
+    for (unsigned b = 0; b < B; b++) {
+        if (k[b] < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: rank of member %u must be >= 1", b);
+        K += k[b];
+    }
+    if (method >= 3 && method <= 4)
+        return fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
+    if (K > NNLM_KQ_MAX) return fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_batch: the ranks sum to %ld; a batch holds at most %d", K, NNLM_KQ_MAX);
+    nnlm_handle *h = nullptr;
+    int rc = nnlm_create(&h, env_device(), env_precision());
+    if (rc != NNLM_OK) return rc;
+    struct Guard {
+        nnlm_handle *h;
+        ~Guard() { nnlm_destroy(h); }
+    } guard{h};
+    CHK(nnlm_set_matrix(h, A, n, m));
+    std::vector<double> Wi, Hi;
+    if (!W_init || !H_init) {
+        Lcg lcg;
+        auto draw = [&]() { return (cb && cb->unif_rand) ? cb->unif_rand(cb->ctx) : lcg.next(); };
+        Wi.resize((size_t)n * K);
+        Hi.resize((size_t)K * m);
+        size_t wo = 0, ho = 0;
+        for (unsigned b = 0; b < B; b++) {
+            const size_t wn = (size_t)n * k[b], hn = (size_t)k[b] * m;
+            if (!W_init) // (src/nnmf.cpp:82-88: randu(k, n) * 0.01 drawn column-major, i.e. row q of W fastest)
+                for (int i = 0; i < n; i++)
+                    for (unsigned q = 0; q < k[b]; q++) Wi[wo + (size_t)q * n + i] = draw() * 0.01;
+            if (!H_init)
+                for (size_t e = 0; e < hn; e++) Hi[ho + e] = draw() * 0.01;
+            wo += wn, ho += hn;
+        }
+        if (W_init) memcpy(Wi.data(), W_init, Wi.size() * 8);
+        if (H_init) memcpy(Hi.data(), H_init, Hi.size() * 8);
+        W_init = Wi.data();
+        H_init = Hi.data();
+    }
+    CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
+    CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
+    CHK(nnlm_get_factors_batch(h, W_out, H_out));
     return NNLM_OK;
 }
 
