@@ -98,6 +98,16 @@ int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int *rowidx, co
                     double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
                     int *n_trace, unsigned *n_iteration, int *warned,
                     const nnlm_callbacks *cb);
+/* nnlm_c_nnmf_csc with the absent entries of A missing (see nnlm_set_matrix_csc_missing); same arguments.  Methods 1 and 2, k <= 64. */
+int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k,
+                            const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                            const double alpha[3], const double beta[3],
+                            unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning,
+                            unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                            double *W_out, double *H_out,
+                            double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                            int *n_trace, unsigned *n_iteration, int *warned,
+                            const nnlm_callbacks *cb);
 
 /*
  * Replaces c_nnlm (reference src/nnlm.cpp:4-53; signature src/RcppExports.cpp:10-27).
@@ -114,6 +124,12 @@ int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long long *ycolp
                     const double alpha[3], const int *mask, const double *beta0,
                     unsigned max_iter, double rel_tol, int n_threads, int method,
                     double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
+/* nnlm_c_nnlm_csc with the absent entries of y missing (the recommender's fold-in of new columns); same arguments.  Methods 1 and 2,
+ * p <= 64. */
+int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                            const double alpha[3], const int *mask, const double *beta0,
+                            unsigned max_iter, double rel_tol, int n_threads, int method,
+                            double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
 
 /* ------------------------------------------------------------------------------------------
  * Resident API: the same path with A kept in HBM across calls.  The one-shot entries are thin
@@ -147,8 +163,17 @@ int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m);
  * nnlm_errors work for methods 1 and 2 (square loss), at any rank, with masks; methods 3 and 4 (KL loss), nnlm_comm_init and
  * nnlm_debug_partial return NNLM_ERR_UNSUPPORTED.  nnlm_errors' KL sum leaves out the zeros' -eps log(wh + eps), at most 3.7e-15 each. */
 int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* The same CSC contract and validation as nnlm_set_matrix_csc, but absent entries are MISSING (a score matrix: movies x customers): every
+ * stored entry is an observation, an explicitly stored zero included, and the factorisation fits the stored entries only -- the
+ * reference's update_with_missing() (src/update_with_missing.cpp:58-139) on the matrix with NA at the absent entries, without anything
+ * n x m sized: per-column Grams over the stored rows of each column are formed in column chunks of at most min(1 GiB,
+ * nnlm_debug_alloc_limit) bytes.  nnlm_matrix_info: n_non_missing = nnz, any_missing = (nnz < n m), kl_const over the stored entries;
+ * nnlm_errors' sums run over the stored entries.  Works on such a handle: nnlm_half_step, nnlm_iterate, nnlm_run, nnlm_errors, methods 1
+ * and 2, both modes, ranks 1..64, masks and known profiles.  NNLM_ERR_UNSUPPORTED: methods 3 and 4, rank > 64 (nnlm_set_factors),
+ * nnlm_comm_init, nnlm_debug_partial and the batch entries. */
+int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
 /* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag.  Sparse A: n m and 0, and kl_const counts
- * the zeros ((n m - nnz) eps log eps). */
+ * the zeros ((n m - nnz) eps log eps); absent entries missing (nnlm_set_matrix_csc_missing): nnz and (nnz < n m). */
 int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const);
 
 /* Set rank, factors (W n x k, H k x m; NULL = zeros) and masks (NULL = none). */
@@ -211,7 +236,8 @@ int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, const unsigned 
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",
  * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack";
- * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block); batched factorisation: "batch_errors" (the one pass over A of a
+ * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block), "sp_gram" (per-column Grams when absent entries are missing);
+ * batched factorisation: "batch_errors" (the one pass over A of a
  * trace iteration), "batch_pen" (the members' penalty sums). */
 int nnlm_profile_enable(nnlm_handle *h, int on);
 int nnlm_profile_get(nnlm_handle *h, const char *name, double *total_ms, long long *launches);
@@ -273,7 +299,9 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "kl_form_w" / "kl_form_h" (KL solver of the
  * last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
  * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
- * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies). */
+ * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies),
+ * "matrix_absent_missing" (1 after nnlm_set_matrix_csc_missing, else 0), "sp_gram_chunks" / "sp_gram_bytes" (column chunks of the last
+ * half-step on such a handle, device bytes of the per-column Gram buffer). */
 int nnlm_get_info(nnlm_handle *h, const char *key, double *value);
 
 #ifdef __cplusplus

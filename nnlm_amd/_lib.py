@@ -34,6 +34,7 @@ EXPORTS = [
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
     "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
+    "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
 ]
 
@@ -86,6 +87,9 @@ def load():
     lib.nnlm_c_nnlm_csc.argtypes = [dp, C.c_int, C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnlm.argtypes[5:]
     lib.nnlm_set_matrix_csc.restype = C.c_int
     lib.nnlm_set_matrix_csc.argtypes = [vp, C.c_int, C.c_int, lp, ip, dp]
+    for name in ("nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc", "nnlm_set_matrix_csc"):  # absent entries missing: the same arguments
+        getattr(lib, name + "_missing").restype = C.c_int
+        getattr(lib, name + "_missing").argtypes = getattr(lib, name).argtypes
     lib.nnlm_create.restype = C.c_int
     lib.nnlm_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     lib.nnlm_destroy.restype = None
@@ -348,6 +352,19 @@ def c_nnlm(x, y, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callb
 def c_nnmf_csc(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
                inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
     """c_nnmf on a sparse A given as canonical CSC arrays (indptr[m+1], indices, data) of shape (n, m); square loss (methods 1, 2)."""
+    return _nnmf_csc(load().nnlm_c_nnmf_csc, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads,
+                     verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
+
+
+def c_nnmf_csc_missing(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+                       inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_csc with the absent entries of A missing (every stored entry, zeros included, is an observation); k <= 64."""
+    return _nnmf_csc(load().nnlm_c_nnmf_csc_missing, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol,
+                     n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
+
+
+def _nnmf_csc(entry, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+              inner_max_iter, inner_rel_tol, method, trace, callbacks):
     lib = load()
     n, m = (int(v) for v in shape)
     ptr, idx, val = _csc_arrays(indptr, indices, data)
@@ -361,11 +378,11 @@ def c_nnmf_csc(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_i
     Ho = np.zeros((k, m), order="F")
     mse, mkl, terr, ep = (np.zeros(cap) for _ in range(4))
     n_trace, n_it, warned = C.c_int(0), C.c_uint(0), C.c_int(0)
-    rc = lib.nnlm_c_nnmf_csc(n, m, _lp(ptr), _ip(idx), _dp(val), k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
-                             float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
-                             float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
-                             _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
-                             C.byref(callbacks) if callbacks is not None else None)
+    rc = entry(n, m, _lp(ptr), _ip(idx), _dp(val), k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
+               float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
+               float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
+               _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
+               C.byref(callbacks) if callbacks is not None else None)
     _check(rc)
     e = n_trace.value
     return dict(W=np.ascontiguousarray(Wo), H=np.ascontiguousarray(Ho), mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(),
@@ -375,7 +392,17 @@ def c_nnmf_csc(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_i
 
 def c_nnlm_csc(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
     """c_nnlm with a sparse y (canonical CSC arrays of shape (n, q)); x stays dense; square loss (methods 1, 2)."""
-    lib = load()
+    return _nnlm_csc(load().nnlm_c_nnlm_csc, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads,
+                     method, callbacks)
+
+
+def c_nnlm_csc_missing(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
+    """c_nnlm_csc with the absent entries of y missing (the recommender's fold-in of new columns); p <= 64."""
+    return _nnlm_csc(load().nnlm_c_nnlm_csc_missing, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol,
+                     n_threads, method, callbacks)
+
+
+def _nnlm_csc(entry, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks):
     x = _f64(x)
     n, p = x.shape
     if int(y_shape[0]) != n:
@@ -387,8 +414,8 @@ def c_nnlm_csc(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_
     al = _vec3(alpha)
     coef = np.zeros((p, q), order="F")
     nit = C.c_int(0)
-    rc = lib.nnlm_c_nnlm_csc(_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val), _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol),
-                             int(n_threads), int(method), _dp(coef), C.byref(nit), C.byref(callbacks) if callbacks is not None else None)
+    rc = entry(_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val), _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol),
+               int(n_threads), int(method), _dp(coef), C.byref(nit), C.byref(callbacks) if callbacks is not None else None)
     _check(rc)
     return dict(coefficient=np.ascontiguousarray(coef), n_iteration=int(nit.value))
 
@@ -435,6 +462,13 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_missing(self, indptr, indices, data, shape):
+        """Sparse A of shape (n, m) as CSC arrays whose absent entries are MISSING: every stored entry, zeros included, is an observation."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc_missing(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
         self.n, self.m = n, m
 
     def matrix_info(self):

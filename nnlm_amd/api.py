@@ -75,15 +75,35 @@ def csc_toarray(c):
     return out
 
 
-def _sparse_input(A, name, loss):
-    """Sparse argument of nnmf() / nnlm(): canonical CSC; square loss only; no missing entries."""
+def _sparse_input(A, name, loss, absent="zero"):
+    """Sparse argument of nnmf() / nnlm(): canonical CSC; square loss only; no non-finite stored values.  absent = "zero": absent entries
+    are zeros; "missing": they are missing and every stored entry (an explicit zero included) is an observation."""
     if loss == "mkl":
         raise NnlmStop("Sparse %s is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'." % name)
     c = as_csc(A)
     if not np.all(np.isfinite(c.data)):
+        if absent == "missing":
+            raise NnlmStop("Sparse %s must not store NA / non-finite values: with absent = 'missing' a missing entry is one left out of "
+                           "the structure." % name)
         raise NnlmStop("Sparse %s must not contain NA / non-finite values: absent entries are zeros, not missing; use a dense matrix for "
                        "missing values." % name)
     return c
+
+
+def _absent_arg(absent, x, name):
+    """The `absent` argument of nnmf() / nnlm() / predict_nnmf(): "zero" (default) or "missing"; "missing" needs a sparse argument (the
+    missing entries of a dense matrix are its NA)."""
+    absent = _match_arg(absent, ("zero", "missing"), "absent")
+    if absent == "missing" and not is_sparse(x):
+        raise NnlmStop("absent = 'missing' needs a sparse %s (an object with tocsc()): the missing entries of a dense matrix are its NA "
+                       "values." % name)
+    return absent
+
+
+def _stored_counts(c):
+    """Stored entries per row and per column of a CSC."""
+    n, m = c.shape
+    return np.bincount(np.asarray(c.indices, dtype=np.int64), minlength=n), np.diff(c.indptr)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -245,6 +265,18 @@ class NnmfResult(dict):
                     int(np.sum(self["average_epochs"])), self["n_iteration"]))
 
 
+def _nnmf_matrix_missing(A, loss):
+    """_nnmf_matrix for a sparse A whose absent entries are missing: canonical CSC, and check_k's bound of the reference for missing
+    data (R/nnmf.R:157-162): the fewest observed entries of a row or a column."""
+    A = _sparse_input(A, "A", loss, "missing")
+    n, m = A.shape
+    min_k = min(n, m)
+    if A.indices.size < n * m:
+        rows, cols = _stored_counts(A)
+        min_k = min(min_k, int(rows.min()), int(cols.min()))
+    return dict(A=A, n=n, m=m, min_k=min_k)
+
+
 def _nnmf_matrix(A, loss):
     """The matrix part of prepare_nnmf: A checked and converted once (dense: fp64; sparse: canonical CSC), its shape, and the largest
     k the check_k rule allows (min(n, m), less where rows or columns have missing entries)."""
@@ -267,25 +299,29 @@ def _nnmf_matrix(A, loss):
 
 def prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
                  check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
-                 inner_max_iter=None, inner_rel_tol=1e-9, rng=None):
+                 inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero"):
     """Argument normalisation of nnmf(), R/nnmf.R:142-183 -> (17-tuple for c_nnmf, context dict)."""
     args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace,
-                                 verbose, show_warning, inner_max_iter, inner_rel_tol, rng)
+                                 verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent=absent)
     return args, ctx
 
 
 def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
                   check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
-                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None, matrix=None):
+                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None, matrix=None, absent="zero"):
     """prepare_nnmf, also returning the checked matrix; `matrix` = what an earlier call returned for the same A (nnmf_batch: the
     members share one checked, converted A)."""
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
+    absent = _absent_arg(absent, A, "A")
     if inner_max_iter is None:
         inner_max_iter = 50 if loss == "mse" else 1  # R/nnmf.R:139
     if trace is None:
         trace = 100 / inner_max_iter  # R/nnmf.R:138
-    mat = matrix if matrix is not None else _nnmf_matrix(A, loss)
+    if matrix is not None:
+        mat = matrix
+    else:
+        mat = _nnmf_matrix_missing(A, loss) if absent == "missing" else _nnmf_matrix(A, loss)
     A, n, m = mat["A"], mat["n"], mat["m"]
     im = reformat_input(init, mask, n, m, int(k), rng=rng)
     K = im["K"]
@@ -305,7 +341,7 @@ def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="m
             int(n_threads), verbose, bool(show_warning), int(inner_max_iter), float(inner_rel_tol), code, int(trace))
     ctx = dict(method=method, loss=loss, alpha=alpha, beta=beta, init=init, mask=mask, n_threads=n_threads, trace=trace,
                verbose=verbose, max_iter=max_iter, rel_tol=rel_tol, inner_max_iter=inner_max_iter,
-               inner_rel_tol=inner_rel_tol, W_norm=W_norm)
+               inner_rel_tol=inner_rel_tol, W_norm=W_norm, absent=absent)
     return args, ctx, mat
 
 
@@ -325,6 +361,7 @@ def finish_nnmf(out, ctx, run_time=None):
     res["run_time"] = run_time
     res["options"] = {key: ctx[key] for key in ("method", "loss", "alpha", "beta", "init", "mask", "n_threads", "trace",
                                                 "verbose", "max_iter", "rel_tol", "inner_max_iter", "inner_rel_tol")}
+    res["options"]["absent"] = ctx.get("absent", "zero")
     if out.get("warning"):
         warnings.warn("Target tolerance not reached. Try a larger max.iter.", RuntimeWarning, stacklevel=3)
     return res
@@ -332,18 +369,21 @@ def finish_nnmf(out, ctx, run_time=None):
 
 def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
          check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=0, show_warning=True,
-         inner_max_iter=None, inner_rel_tol=1e-9, rng=None):
+         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero"):
     """Non-negative matrix factorisation A ~ W H on the MI355X (drop-in for R's NNLM::nnmf, R/nnmf.R:135-225).
 
     ``verbose`` defaults to 0 here (R: 1 = progress bar); ``rng`` seeds the default random init (R uses its global RNG).
+    ``absent`` (sparse A only): "zero" -- absent entries are zeros; "missing" -- they are missing and the fit runs over the stored
+    entries only, as the reference does for NA (a score matrix such as movies x customers; square loss, k <= 64).
     """
     args, ctx = prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads,
-                             trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng)
+                             trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random(), print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
     t0 = time.perf_counter()
     if isinstance(args[0], CSC):
-        out = _lib.c_nnmf_csc(*args[0], *args[1:], callbacks=cb)
+        entry = _lib.c_nnmf_csc_missing if ctx["absent"] == "missing" else _lib.c_nnmf_csc
+        out = entry(*args[0], *args[1:], callbacks=cb)
     else:
         out = _lib.c_nnmf(*args, callbacks=cb)
     return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
@@ -441,13 +481,14 @@ def _rcond(x):
 
 
 def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, check_x=True, max_iter=10000,
-                 rel_tol=1e-12, n_threads=1, show_warning=True):
+                 rel_tol=1e-12, n_threads=1, show_warning=True, absent="zero"):
     """Argument normalisation of nnlm(), R/nnlm.R:75-120 -> (9-tuple for c_nnlm, context)."""
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
+    absent = _absent_arg(absent, y, "y")
     x = np.asarray(x)
     y_sparse = is_sparse(y)
-    yv = _sparse_input(y, "y", loss) if y_sparse else np.asarray(y)
+    yv = _sparse_input(y, "y", loss, absent) if y_sparse else np.asarray(y)
     with np.errstate(invalid="ignore"):
         if show_warning and loss == "mkl" and (np.any(x < 0) or np.any(yv < 0)):
             warnings.warn("x or y have negative values. One should instead use method == 'mse'.", RuntimeWarning, stacklevel=3)
@@ -484,7 +525,7 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
         init_m = (~mask_m).astype(np.float64)  # masked entries fixed to 0, R/nnlm.R:110-112
     code = get_method_code(method, loss)
     args = (x, ym, alpha, mask_m, init_m, int(max_iter), float(rel_tol), int(n_threads), code)
-    ctx = dict(method=method, loss=loss, max_iter=max_iter, rel_tol=rel_tol, is_y_vector=is_y_vector, alpha=alpha, x=x, y=ym)
+    ctx = dict(method=method, loss=loss, max_iter=max_iter, rel_tol=rel_tol, is_y_vector=is_y_vector, alpha=alpha, x=x, y=ym, absent=absent)
     return args, ctx
 
 
@@ -492,9 +533,14 @@ def finish_nnlm(sol, ctx):
     """R/nnlm.R:122-144."""
     coef = np.array(sol["coefficient"])
     x, y, alpha, loss = ctx["x"], ctx["y"], ctx["alpha"], ctx["loss"]
-    if isinstance(y, CSC):  # (the summary compares y with the dense x beta: n x q either way)
-        y = csc_toarray(y)
-    err = mse_mkl(y, x @ coef, na_rm=True, show_warning=False)
+    if isinstance(y, CSC) and ctx.get("absent") == "missing":  # (mse_mkl with na.rm over the stored entries only: nothing n x q sized)
+        cols = np.repeat(np.arange(y.shape[1]), np.diff(y.indptr))
+        pred = np.einsum("ek,ek->e", x[np.asarray(y.indices, dtype=np.int64)], coef.T[cols]) if cols.size else np.zeros(0)
+        err = mse_mkl(y.data, pred, na_rm=True, show_warning=False)
+    else:
+        if isinstance(y, CSC):  # (the summary compares y with the dense x beta: n x q either way)
+            y = csc_toarray(y)
+        err = mse_mkl(y, x @ coef, na_rm=True, show_warning=False)
     target = 0.5 * err["MSE"] if loss == "mse" else err["MKL"]
     target = target + (alpha[0] - alpha[1]) * float(np.sum(coef ** 2)) + alpha[1] * float(np.sum(coef.sum(axis=0) ** 2)) \
         + alpha[2] * float(np.sum(coef))
@@ -505,22 +551,30 @@ def finish_nnlm(sol, ctx):
 
 
 def nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, check_x=True, max_iter=10000,
-         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None):
-    """Non-negative linear model y ~ x beta on the MI355X (drop-in for R's NNLM::nnlm, R/nnlm.R:70-145)."""
-    args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning)
+         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None, absent="zero"):
+    """Non-negative linear model y ~ x beta on the MI355X (drop-in for R's NNLM::nnlm, R/nnlm.R:70-145).
+
+    ``absent`` (sparse y only): "zero" -- absent entries are zeros; "missing" -- they are missing, each column of beta is fitted to the
+    stored entries of its column of y only (square loss, at most 64 columns of x)."""
+    args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning, absent)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random())
     if isinstance(args[1], CSC):
-        return finish_nnlm(_lib.c_nnlm_csc(args[0], *args[1], *args[2:], callbacks=cb), ctx)
+        entry = _lib.c_nnlm_csc_missing if ctx["absent"] == "missing" else _lib.c_nnlm_csc
+        return finish_nnlm(entry(args[0], *args[1], *args[2:], callbacks=cb), ctx)
     return finish_nnlm(_lib.c_nnlm(*args, callbacks=cb), ctx)
 
 
-def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=None, **kw):
-    """S3 predict.nnmf, R/nnmf_methods.R:22-48.  ``_nnlm`` lets the CPU tests substitute the solver."""
+def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=None, absent="zero", **kw):
+    """S3 predict.nnmf, R/nnmf_methods.R:22-48.  ``_nnlm`` lets the CPU tests substitute the solver.  ``absent = "missing"`` with a
+    sparse ``newdata`` and which = "H" is the recommender's fold-in of new users: their H columns fitted to their stored scores only
+    (which = "W": new rows, the same over their stored entries; which = "A" returns W H and ignores ``absent``)."""
     which = _match_arg(which, ("A", "W", "H"), "which")
     method = method or object["options"]["method"]
     loss = loss or object["options"]["loss"]
     solver = _nnlm or nnlm
+    if which != "A" and _absent_arg(absent, newdata, "newdata") == "missing":  # (which = "A" solves nothing: `absent` is not used)
+        kw["absent"] = "missing"
     if which != "A" and is_sparse(newdata):  # (passed on to nnlm() as it is: duck-typed there)
         nd = newdata
         want = object["H"].shape[1] if which == "W" else object["W"].shape[0]

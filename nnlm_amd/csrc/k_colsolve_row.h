@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256, (KR * CPL > 208) ? 1 : 2) void colsolve_row_ke
     const bool in_range = col < a.ncols;
     const int cc = in_range ? col : a.col0;
     const int k = a.k;
-    const double *G = a.Graw + (size_t)cc * g_stride;
+    const double *G = a.Graw + (size_t)(cc - a.gcol0) * g_stride;
     unsigned long long mword = 0ull;
     if (HAS_MASK) mword = a.mask[cc];
     const unsigned long long kmask = (k >= 64) ? ~0ull : ((1ull << k) - 1ull);
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256, (KR * CPL > 208) ? 1 : 2) void colsolve_row_ke
         constexpr int c = decltype(cq)::value;
         const bool c_in = colw + c < a.ncols; // wave-uniform
         const int ccl = c_in ? colw + c : a.col0;
-        const double *Gc = a.Graw + (size_t)ccl * g_stride;
+        const double *Gc = a.Graw + (size_t)(ccl - a.gcol0) * g_stride;
         const bool lj = lane < k;
         const int lq = lj ? lane : 0;
         double gd = 1.0; // edited G[lane][lane] (src/update_with_missing.cpp:98-103)

@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void colsolve_ls_kernel(const SweepArgs a, siz
     const int k = a.k;
     const bool lv = lane < k;
     const int lq = lv ? lane : 0;
-    const double *G = a.Graw + (size_t)col * g_stride;
+    const double *G = a.Graw + (size_t)(col - a.gcol0) * g_stride;
 
     unsigned long long mword = 0ull;
     if (a.mask) mword = a.mask[col];
@@ -625,7 +625,7 @@ __global__ __launch_bounds__(256) void colsolve_strict_kernel(const SweepArgs a,
     const int k = a.k;
     const bool lv = lane < k;
     const int lq = lv ? lane : 0;
-    const double *G = a.Graw + (size_t)col * g_stride;
+    const double *G = a.Graw + (size_t)(col - a.gcol0) * g_stride;
     unsigned long long mword = 0ull;
     if (HAS_MASK) mword = a.mask[col];
     const unsigned long long kmask = (k >= 64) ? ~0ull : ((1ull << k) - 1ull);

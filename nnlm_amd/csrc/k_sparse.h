@@ -146,7 +146,8 @@ __global__ __launch_bounds__(256) void spmm_fixup_kernel(const SpmmArgs a)
 // Error sums over the non-zeros (CSC): worker = LW lanes, lane l takes coordinates l, l + LW, ...; wh is reduced across the worker's
 // lanes.  partial[block] = {sum (a - wh)^2, sum wh^2, sum -(a + eps) log(wh + eps)} (fixed order).  Wrow: [rows][KP] fp64 copy of W,
 // H: [KP][ldh] master.  The sums over all n x m entries follow from the Grams and the factors' sums (sp_err_final_kernel).
-template <typename T, int LW>
+// MISS (absent entries are missing, k_sparse_na.h): the second sum is sum wh -- the stored entries are all there is.
+template <typename T, int LW, bool MISS = false>
 __global__ __launch_bounds__(256) void sp_errors_kernel(const long long *__restrict__ ptr, const int *__restrict__ idx, const T *__restrict__ val,
                                                         int ncols, long long nnz, long long chunk, int nworkers, const double *__restrict__ Wrow,
                                                         int KP, int k, const double *__restrict__ H, int ldh, double *__restrict__ partial)
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256) void sp_errors_kernel(const long long *__restr
                     const double av = (double)val[e];
                     const double r = av - d;
                     s1 = __builtin_fma(r, r, s1);
-                    s2 = __builtin_fma(d, d, s2);
+                    s2 = MISS ? s2 + d : __builtin_fma(d, d, s2);
                     s3 += -(av + NNLM_TINY) * nnlm_log_pos(d + NNLM_TINY);
                 }
             }

@@ -60,6 +60,8 @@ struct SweepArgs {
     // final x image while it is still in LDS -- its Gram partial sums and max|x| (the scale of its split-fp16 copy)
     unsigned *maxbits = nullptr;      // atomicMax of the float bit pattern of max|x| over the solved columns
     double *gram_slabs = nullptr;     // [workgroups][KP*KP]  Gram of each workgroup's 64 (persistent form: 16 G) columns (upper tiles)
+    // per-column Gram solvers (colsolve_*): Graw holds the Grams of columns gcol0 .. (column col at Graw + (col - gcol0) * g_stride)
+    int gcol0 = 0;
 };
 
 // The SCD sweep's operand image (k_sweep_q.h), written straight from the fold: SweepImg describes it, sweepq_img_put() stores the

@@ -42,7 +42,7 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_COUNT };
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -51,9 +51,16 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  "spmm_h" / "spmm_w": the cross products of a sparse A (row copy of the fixed factor + spmm_kernel + its fix-up); "sp_errors": the error
 //  block of a sparse A (sums over the non-zeros, the two Grams and the factors' sums)
 //  "batch_errors": the error block of a batched factorisation (errors_batch_kernel + its reduction: one pass over A for all members);
-//  "batch_pen": its per-member penalty sums
+//  "batch_pen": its per-member penalty sums; "sp_gram": the per-column Grams of a sparse A whose absent entries are missing (sp_gram_kernel
+//  + its fix-up, both half-steps)
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen"};
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram"};
+
+// A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
+// columns longc[l0 .. l1)
+struct SpgChunk {
+    int c0, c1, l0, l1;
+};
 
 struct ProfRec {
     int id;
@@ -138,6 +145,19 @@ struct nnlm_handle {
     double *sp_eslabs = nullptr;                      // error block: Gram partial sums
     double *sp_eG = nullptr;                          // error block: W^T W, H H^T [KP][KP] each, W's and H's sums over i / j [KP] each, S1..S3
     double *sp_epart = nullptr;                       // error block: per-workgroup partial sums
+    // sparse A whose absent entries are MISSING (nnlm_set_matrix_csc_missing, k_sparse_na.h).  Per orientation (0: W half-step over the
+    // CSR, 1: H half-step over the CSC), made with the matrix: the host copy of the pointers, the Gram slots of the long columns in front
+    // of each column (segoff) and the list of the long columns.  Per orientation and budget: the column chunks whose Grams are held at
+    // once; the buffer they share (freed with the factors)
+    bool sp_missing = false;
+    std::vector<long long> spg_hptr[2];
+    long long *spg_segoff[2] = {nullptr, nullptr};
+    int *spg_longc[2] = {nullptr, nullptr};
+    std::vector<SpgChunk> spg_plan[2];
+    size_t spg_plan_cap[2] = {0, 0}, spg_plan_slots[2] = {0, 0}; // Gram slots per chunk: allowed, and taken by the largest chunk (columns + segments)
+    double *spg_buf = nullptr;
+    size_t spg_buf_bytes = 0;
+    int spg_chunks = 0; // chunks of the last such half-step (nnlm_get_info "sp_gram_chunks")
     unsigned long long *sweeps = nullptr; // [2] device counters; sw_active = the one the current trace window sums into
     int sw_active = 0;
     double *host_res = nullptr;           // pinned: 8 reduction results + sweep counter of the asynchronous error block
@@ -650,6 +670,10 @@ static void free_factors(nnlm_handle *h)
     hipFree(h->sp_epart);
     h->sp_Y = nullptr;
     h->sp_carry = h->sp_Wrow = h->sp_eslabs = h->sp_eG = h->sp_epart = nullptr;
+    hipFree(h->spg_buf);
+    h->spg_buf = nullptr;
+    h->spg_buf_bytes = 0;
+    for (int o = 0; o < 2; o++) h->spg_plan[o].clear(), h->spg_plan_cap[o] = 0; // (the plan depends on KP)
     h->W64 = h->H64 = nullptr;
     h->Wop = nullptr;
     h->Wmask = h->Hmask = nullptr;
@@ -691,6 +715,16 @@ static void free_matrix(nnlm_handle *h)
     h->sp_cval = h->sp_rval = nullptr;
     h->sp_bytes = 0;
     h->sparse = false;
+    for (int o = 0; o < 2; o++) {
+        hipFree(h->spg_segoff[o]);
+        hipFree(h->spg_longc[o]);
+        h->spg_segoff[o] = nullptr;
+        h->spg_longc[o] = nullptr;
+        h->spg_hptr[o].clear();
+        h->spg_plan[o].clear();
+        h->spg_plan_cap[o] = 0;
+    }
+    h->sp_missing = false;
     h->nnz = 0;
     h->x16 = x16_enabled(h->prec); // (a sparse matrix turned it off)
     h->n = h->m = 0;
@@ -946,29 +980,54 @@ static int sp_upload(nnlm_handle *h, const long long *colptr, const int *rowidx,
     return NNLM_OK;
 }
 
-extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+// Sparse A whose absent entries are missing (k_sparse_na.h): per orientation the host copy of the pointers, the segment slots of the
+// long columns (more than SPG_SEG stored entries) in front of each column and the list of the long columns, on the device
+static int spg_layout(nnlm_handle *h, int o, const long long *ptr, int ncols)
 {
-    if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_set_matrix_csc: handle is NULL");
-    if (n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: A must be a non-empty n x m matrix with colptr[m + 1] (n=%d, m=%d)", n, m);
-    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_matrix_csc: a sparse matrix is single-GPU only (this handle has a communicator)");
-    if (colptr[0] != 0) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: colptr[0] = %lld, must be 0", colptr[0]);
+    h->spg_hptr[o].assign(ptr, ptr + ncols + 1);
+    std::vector<long long> so((size_t)ncols + 1, 0);
+    std::vector<int> lc;
+    for (int c = 0; c < ncols; c++) {
+        const long long len = ptr[c + 1] - ptr[c];
+        const long long ns = len > SPG_SEG ? (len + SPG_SEG - 1) / SPG_SEG : 0;
+        so[(size_t)c + 1] = so[c] + ns;
+        if (ns) lc.push_back(c);
+    }
+    HIPCHK(h, hipMalloc(&h->spg_segoff[o], so.size() * 8));
+    HIPCHK(h, hipMemcpy(h->spg_segoff[o], so.data(), so.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(h, hipMalloc(&h->spg_longc[o], (lc.size() + 1) * 4));
+    if (!lc.empty()) HIPCHK(h, hipMemcpy(h->spg_longc[o], lc.data(), lc.size() * 4, hipMemcpyHostToDevice));
+    h->sp_bytes += so.size() * 8 + (lc.size() + 1) * 4;
+    return NNLM_OK;
+}
+
+// nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is
+static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing,
+                               const char *who)
+{
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix with colptr[m + 1] (n=%d, m=%d)", who, n, m);
+    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is single-GPU only (this handle has a communicator)", who);
+    if (colptr[0] != 0) return fail(h, NNLM_ERR_ARG, "%s: colptr[0] = %lld, must be 0", who, colptr[0]);
     for (int j = 0; j < m; j++)
-        if (colptr[j + 1] < colptr[j]) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: colptr decreases at column %d", j);
+        if (colptr[j + 1] < colptr[j]) return fail(h, NNLM_ERR_ARG, "%s: colptr decreases at column %d", who, j);
     const long long nnz = colptr[m];
-    if (nnz > 0 && (!rowidx || !x)) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: rowidx / x is NULL with nnz = %lld", nnz);
-    if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: nnz = %lld exceeds n * m", nnz);
+    if (nnz > 0 && (!rowidx || !x)) return fail(h, NNLM_ERR_ARG, "%s: rowidx / x is NULL with nnz = %lld", who, nnz);
+    if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "%s: nnz = %lld exceeds n * m", who, nnz);
     std::vector<long long> rptr((size_t)n + 1, 0);
     double over = 0.0, mx = 0.0, klc = 0.0;
     for (int j = 0; j < m; j++)
         for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
             const int i = rowidx[e];
-            if (i < 0 || i >= n) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: row index %d out of range at entry %lld (column %d)", i, e, j);
+            if (i < 0 || i >= n) return fail(h, NNLM_ERR_ARG, "%s: row index %d out of range at entry %lld (column %d)", who, i, e, j);
             if (e > colptr[j] && i <= rowidx[e - 1])
-                return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: row indices of column %d are not strictly increasing (entry %lld)", j, e);
+                return fail(h, NNLM_ERR_ARG, "%s: row indices of column %d are not strictly increasing (entry %lld)", who, j, e);
             const double v = x[e];
             if (!std::isfinite(v))
-                return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_csc: entry %lld (row %d, column %d) is not finite; a sparse matrix has no missing entries "
-                                             "(use nnlm_set_matrix for NA data)", e, i, j);
+                return fail(h, NNLM_ERR_ARG, absent_missing ? "%s: entry %lld (row %d, column %d) is not finite; a stored entry is an observation "
+                                                              "(leave a missing entry out of the structure)"
+                                                            : "%s: entry %lld (row %d, column %d) is not finite; a sparse matrix has no missing entries "
+                                                              "(use nnlm_set_matrix for NA data)", who, e, i, j);
             rptr[(size_t)i + 1]++;
             if (std::fabs(v) > 3.4028234663852886e38) over += 1.0;
             const double fv = std::fabs((double)(float)v);
@@ -977,7 +1036,7 @@ extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long
         }
     if (h->prec == NNLM_PREC_F32 && over > 0.0)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
-                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of nnlm_c_nnmf_csc / nnlm_c_nnlm_csc)", over);
+                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over);
     if (h->prec == NNLM_PREC_F32 && mx > 0.0 && mx < 7.8886090522101181e-31)
         return fail(h, NNLM_ERR_UNSUPPORTED, "max |A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale A or use "
                                              "the strict fp64 mode", mx);
@@ -1016,13 +1075,36 @@ extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long
     if (hipMalloc(&h->partials, h->partials_elems * sizeof(double)) != hipSuccess) {
         (void)hipGetLastError();
         free_matrix(h);
-        return fail(h, NNLM_ERR_HIP, "nnlm_set_matrix_csc: hipMalloc of %zu partial sums failed", h->partials_elems);
+        return fail(h, NNLM_ERR_HIP, "%s: hipMalloc of %zu partial sums failed", who, h->partials_elems);
+    }
+    if (absent_missing) {
+        h->sp_missing = true;
+        h->n_non_missing = (double)nnz; // N_non_missing, src/nnmf.cpp:69
+        h->any_missing = (double)nnz != (double)n * (double)m;
+        h->kl_const = klc / h->n_non_missing; // src/nnmf.cpp:70: over the stored entries only
+        int rl = spg_layout(h, 1, colptr, m);
+        if (rl == NNLM_OK) rl = spg_layout(h, 0, rptr.data(), n);
+        if (rl != NNLM_OK) {
+            free_matrix(h);
+            return rl;
+        }
+        return NNLM_OK;
     }
     h->n_non_missing = (double)n * (double)m;
     h->any_missing = false;
     // the zeros add (n m - nnz) eps log eps
     h->kl_const = (klc + ((double)n * (double)m - (double)nnz) * (NNLM_TINY * std::log(NNLM_TINY))) / h->n_non_missing;
     return NNLM_OK;
+}
+
+extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc");
+}
+
+extern "C" int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, true, "nnlm_set_matrix_csc_missing");
 }
 
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
@@ -1265,6 +1347,9 @@ extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, co
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
     const int k = (int)k_;
     if (k < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: rank k must be >= 1");
+    if (h->sparse && h->sp_missing && k > NNLM_KQ_MAX)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_factors: rank %d on a sparse matrix whose absent entries are missing: the rank is at most %d", k,
+                    NNLM_KQ_MAX);
     return set_factors_impl(h, k, W, H, Wm, Hm, 0);
 }
 
@@ -2167,18 +2252,11 @@ static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsi
 
 static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int fused_nb, bool need_pen);
 
-// Square-loss half-step on a sparse A (k_sparse.h): the Gram of the fixed factor (launch_gram), a row copy of the fixed factor and the
-// SpMM -- W^T A over the CSC for the H half-step, A H^T over the CSR for the W half-step -- into ONE slab of Cx, then the solvers of the
-// dense path unchanged (half_step_solve).  Rank > 64: one SpMM launch per 64 coordinates, the generic Gram and sweep.
-static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
+// W^T A over the CSC (H half-step) / A H^T over the CSR (W half-step) into ONE slab of Cx: a row copy of the fixed factor, spmm_kernel
+// (k_sparse.h; rank > 64: one SpMM launch per 64 coordinates)
+static void sp_cross(nnlm_handle *h, const Side &s)
 {
-    if (method >= 3)
-        return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     const int p = s.p;
-    {
-        ProfScope ps(h, P_GRAM, h->stream);
-        launch_gram(h, s, 0, p);
-    }
     {
         ProfScope ps(h, s.prof_spmm);
         const bool f64 = h->prec == NNLM_PREC_F64;
@@ -2203,6 +2281,139 @@ static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], 
             nnlm_tu_spmm(a, f64, h->stream);
         }
     }
+}
+
+// Column chunks of orientation o whose Grams (slot = KP^2 doubles each, + the segment slots of their long columns) fit in
+// min(1 GiB, nnlm_debug_alloc_limit) bytes, at least one column per chunk; planned once per budget, the buffer grows to the largest chunk
+static int spg_prepare(nnlm_handle *h, int o, size_t slot)
+{
+    size_t budget = (size_t)1 << 30;
+    const size_t lim = g_debug_alloc_limit.load(std::memory_order_relaxed);
+    if (lim && lim < budget) budget = lim;
+    size_t cap = budget / (slot * 8);
+    if (cap < 1) cap = 1;
+    if (h->spg_plan_cap[o] != cap) {
+        const std::vector<long long> &hp = h->spg_hptr[o];
+        const int ncols = (int)hp.size() - 1;
+        std::vector<SpgChunk> &pl = h->spg_plan[o];
+        pl.clear();
+        size_t mx = 0, cols = 0, segs = 0;
+        SpgChunk ch{0, 0, 0, 0};
+        int l = 0;
+        auto close = [&](int c) {
+            ch.c1 = c;
+            ch.l1 = l;
+            pl.push_back(ch);
+            mx = cols + segs > mx ? cols + segs : mx;
+            ch = SpgChunk{c, c, l, l};
+            cols = segs = 0;
+        };
+        for (int c = 0; c < ncols; c++) {
+            const long long len = hp[(size_t)c + 1] - hp[c];
+            const size_t ns = len > SPG_SEG ? (size_t)((len + SPG_SEG - 1) / SPG_SEG) : 0;
+            if (cols > 0 && cols + segs + 1 + ns > cap) close(c);
+            cols++;
+            segs += ns;
+            if (ns) l++;
+        }
+        close(ncols);
+        h->spg_plan_slots[o] = mx;
+        h->spg_plan_cap[o] = cap;
+    }
+    const size_t need = h->spg_plan_slots[o] * slot * 8;
+    if (need > h->spg_buf_bytes) {
+        sync_all(h); // (the previous buffer may still be read)
+        hipFree(h->spg_buf);
+        h->spg_buf = nullptr;
+        h->spg_buf_bytes = 0;
+        HIPCHK(h, hipMalloc(&h->spg_buf, need));
+        h->spg_buf_bytes = need;
+    }
+    return NNLM_OK;
+}
+
+// Square-loss half-step on a sparse A whose absent entries are missing (k_sparse_na.h; update_with_missing, src/update_with_missing.cpp:58-139):
+// the cross product of the zero semantics (it sums over the stored entries either way), then chunk by chunk the per-column Grams over the
+// stored rows (sp_gram_kernel + its fix-up) and the dense NA path's per-column solvers on them (launch_colsolve, unchanged).  Nothing
+// max(n, m) x KP^2 sized is held: a chunk's Grams live in spg_buf, and the solvers find column col at (col - gcol0) * KP^2 (gcol0 = c0).
+static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+                                    bool speculative)
+{
+    sp_cross(h, s);
+    if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
+    h->cur_which = s.which;
+    const int o = s.which, KP = h->KP;
+    const size_t slot = (size_t)KP * KP;
+    int rc = spg_prepare(h, o, slot);
+    if (rc != NNLM_OK) return rc;
+    SweepArgs a;
+    a.KPg = KP;
+    a.Cx = h->Cx;
+    a.nslabs = 1;
+    a.k = h->k;
+    a.r0 = reg[0];
+    a.r1 = reg[1];
+    a.r2 = reg[2];
+    a.max_iter = inner_max_iter;
+    a.rel_tol = inner_rel_tol;
+    a.sweeps = h->sweeps + (speculative ? (h->sw_active ^ 1) : h->sw_active);
+    a.ocol0 = 0;
+    a.X = s.X;
+    a.Xout = s.Xout;
+    a.ldx = a.ldo = a.ldc = s.ldc;
+    a.slab_stride = s.slab_stride;
+    a.mask = s.mask;
+    a.op = s.op;
+    a.op_mode = s.op_mode;
+    a.op_ld = s.op_ld;
+    a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
+    SpGramArgs g;
+    g.ptr = s.sp_ptr;
+    g.idx = s.sp_idx;
+    g.Y = h->sp_Y;
+    g.segoff = h->spg_segoff[o];
+    g.G = h->spg_buf; // [chunk columns][slot], then the chunk's segment slots
+    const std::vector<long long> &hp = h->spg_hptr[o];
+    for (const SpgChunk &ch : h->spg_plan[o]) {
+        {
+            ProfScope ps(h, P_SP_GRAM);
+            g.c0 = ch.c0;
+            g.c1 = ch.c1;
+            g.seg = h->spg_buf + (size_t)(ch.c1 - ch.c0) * slot;
+            const long long nnz = hp[ch.c1] - hp[ch.c0];
+            g.nworkers = nnlm_spg_workers(nnz, h->cus_device);
+            g.chunk = (nnz + g.nworkers - 1) / g.nworkers;
+            if (g.chunk < 1) g.chunk = 1;
+            nnlm_tu_sp_gram(g, h->NKQ, h->prec == NNLM_PREC_F64, h->stream);
+            nnlm_tu_sp_gram_fixup(g, h->spg_longc[o] + ch.l0, ch.l1 - ch.l0, KP, h->stream);
+        }
+        ProfScope ps(h, s.prof_sweep);
+        a.col0 = ch.c0;
+        a.ncols = ch.c1;
+        a.Graw = h->spg_buf; // (the chunk's Grams: column col at spg_buf + (col - gcol0) * slot)
+        a.gcol0 = ch.c0;
+        launch_colsolve(h, method, a, slot);
+    }
+    h->spg_chunks = (int)h->spg_plan[o].size();
+    LAUNCHCHK(h);
+    if (s.which == 0 && !speculative) swap_w(h);
+    return NNLM_OK;
+}
+
+// Square-loss half-step on a sparse A (k_sparse.h): the Gram of the fixed factor (launch_gram), the SpMM (sp_cross) into ONE slab of Cx,
+// then the solvers of the dense path unchanged (half_step_solve; rank > 64: the generic Gram and sweep).  Absent entries missing (and some
+// absent): half_step_sparse_missing.
+static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
+{
+    if (method >= 3)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
+    // (every entry stored: the reference's update(), src/update_with_missing.cpp:3-55 -- the shared Gram of the zero semantics)
+    if (h->sp_missing && h->any_missing) return half_step_sparse_missing(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
+    {
+        ProfScope ps(h, P_GRAM, h->stream);
+        launch_gram(h, s, 0, s.p);
+    }
+    sp_cross(h, s);
     if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
     return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, 1, speculative, PH_ALL, false);
 }
@@ -2725,8 +2936,9 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
         ProfScope ps(h, P_SP_ERRORS, st);
         const int KP = h->KP, n = h->n, m = h->m;
         double *G = h->sp_eG, *sums = G + (size_t)2 * KP * KP, *S = sums + 2 * KP;
+        // (absent entries missing, src/nnmf.cpp:124-125: the sums over the stored entries are the sums -- S1 and S3 + sum of wh)
         factor_rows_kernel<double><<<(n + 255) / 256, 256, 0, st>>>(h->W64, h->npad, n, KP, h->sp_Wrow);
-        for (int f = 0; f < 2; f++) {
+        for (int f = 0; f < 2 && !h->sp_missing; f++) {
             const double *X = f == 0 ? h->W64 : h->H64;
             const int ld = f == 0 ? h->npad : h->mpad, cols = f == 0 ? n : m;
             const int nb = launch_gram_partial(h, X, ld, 0, cols, h->sp_eslabs, nullptr, st);
@@ -2740,9 +2952,10 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
         if (chunk < 1) chunk = 1;
         const int eb = (nw / (64 / nnlm_sp_lanes(KP)) + 3) / 4;
         nnlm_tu_sp_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, chunk, nw, h->sp_Wrow, KP, h->k, h->H64, h->mpad,
-                          h->sp_epart, eb, st);
+                          h->sp_epart, eb, h->sp_missing, st);
         reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)eb, 3, S);
-        nnlm_tu_sp_err_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->scal, st);
+        if (h->sp_missing) nnlm_tu_sp_err_final_missing(S, h->scal, st);
+        else nnlm_tu_sp_err_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->scal, st);
     } else {
         ProfScope ps(h, P_ERRORS, st);
         const uint32_t *miss = h->any_missing ? h->miss : nullptr;
@@ -2960,6 +3173,9 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
     else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
     else if (strcmp(key, "matrix_bytes") == 0) *value = matrix_bytes(h);
+    else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
+    else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
+    else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
 }
@@ -3654,6 +3870,23 @@ extern "C" int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int 
                        mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
+extern "C" int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
+                                       const double *H_init, const int *Wm, const int *Hm, const double alpha[3], const double beta[3],
+                                       unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter,
+                                       double inner_rel_tol, int method, unsigned trace, double *W_out, double *H_out, double *mse_error,
+                                       double *mkl_error, double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration,
+                                       int *warned, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!colptr || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
+        !n_iteration || !warned)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_missing: NULL argument");
+    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_missing: k must be >= 1");
+    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, m, colptr, rowidx, x); }, n, m, k, W_init, H_init, Wm, Hm,
+                       alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out,
+                       mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+}
+
 template <typename SetMatrix>
 static int c_nnlm_body(SetMatrix set_matrix, const double *x, int n, int p, int q, const double alpha[3], const int *mask, const double *beta0,
                        unsigned max_iter, double rel_tol, int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
@@ -3703,5 +3936,16 @@ extern "C" int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long 
     if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc: empty x or y");
     return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, q, ycolptr, yrowidx, yx); }, x, n, p, q, alpha, mask, beta0,
                        max_iter, rel_tol, method, coefficient, n_iteration, cb);
+}
+
+extern "C" int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                                       const double alpha[3], const int *mask, const double *beta0, unsigned max_iter, double rel_tol, int n_threads,
+                                       int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (!x || !ycolptr || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc_missing: NULL argument");
+    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc_missing: empty x or y");
+    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, q, ycolptr, yrowidx, yx); }, x, n, p, q, alpha, mask,
+                       beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
 }
 #undef CHK

@@ -1,6 +1,7 @@
-// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h), see tu_sweepq.h.
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_na.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
+#include "k_sparse_na.h"
 
 // Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
 // launched once per 64 coordinates)
@@ -38,23 +39,25 @@ void nnlm_tu_spmm(const SpmmArgs &a, bool f64, hipStream_t st)
     else launch_spmm_t<float>(a, st);
 }
 
-template <typename T>
+template <typename T, bool MISS>
 static void launch_sp_errors_t(const long long *ptr, const int *idx, const void *val, int ncols, long long nnz, long long chunk, int nworkers,
                                const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st)
 {
     const T *v = (const T *)val;
     switch (nnlm_sp_lanes(KP)) {
-    case 16: sp_errors_kernel<T, 16><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
-    case 32: sp_errors_kernel<T, 32><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
-    default: sp_errors_kernel<T, 64><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    case 16: sp_errors_kernel<T, 16, MISS><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    case 32: sp_errors_kernel<T, 32, MISS><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    default: sp_errors_kernel<T, 64, MISS><<<nblocks, 256, 0, st>>>(ptr, idx, v, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
     }
 }
 // nblocks = workgroups of four wavefronts covering the nworkers workers (the caller sizes `partial` from it: 3 doubles per workgroup)
 void nnlm_tu_sp_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nworkers,
-                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st)
+                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, bool miss, hipStream_t st)
 {
-    if (f64) launch_sp_errors_t<double>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
-    else launch_sp_errors_t<float>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    if (f64 && miss) launch_sp_errors_t<double, true>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    else if (f64) launch_sp_errors_t<double, false>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    else if (miss) launch_sp_errors_t<float, true>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    else launch_sp_errors_t<float, false>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
 }
 
 void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *partial, int nblocks, hipStream_t st)
@@ -66,3 +69,40 @@ void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, c
 {
     sp_err_final_kernel<<<1, 256, 0, st>>>(s, GW, GH, wsum, hsum, k, KP, out);
 }
+
+// ---- absent entries missing (k_sparse_na.h) ----
+int nnlm_spg_workers(long long nnz, int cus)
+{
+    long long w = (nnz + 255) / 256;
+    const long long cap = 16LL * (cus > 0 ? cus : 256);
+    if (w > cap) w = cap;
+    if (w < 1) w = 1;
+    return (int)w;
+}
+
+template <int NT> static void launch_sp_gram(const SpGramArgs &a, bool f64, hipStream_t st)
+{
+    const int nb = (a.nworkers + 3) / 4;
+    if (f64) sp_gram_kernel<double, NT><<<nb, 256, 0, st>>>(a);
+    else sp_gram_kernel<float, NT><<<nb, 256, 0, st>>>(a);
+}
+void nnlm_tu_sp_gram(const SpGramArgs &a, int NKQ, bool f64, hipStream_t st)
+{
+    switch (NKQ) {
+    case 1: launch_sp_gram<1>(a, f64, st); break;
+    case 2: launch_sp_gram<2>(a, f64, st); break;
+    case 3: launch_sp_gram<3>(a, f64, st); break;
+    default: launch_sp_gram<4>(a, f64, st); break;
+    }
+}
+void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int KP, hipStream_t st)
+{
+    if (nlong <= 0) return;
+    switch (KP) {
+    case 16: sp_gram_fixup_kernel<16><<<nlong, 256, 0, st>>>(a, longc); break;
+    case 32: sp_gram_fixup_kernel<32><<<nlong, 256, 0, st>>>(a, longc); break;
+    case 48: sp_gram_fixup_kernel<48><<<nlong, 256, 0, st>>>(a, longc); break;
+    default: sp_gram_fixup_kernel<64><<<nlong, 256, 0, st>>>(a, longc); break;
+    }
+}
+void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st) { sp_err_final_missing_kernel<<<1, 64, 0, st>>>(s, out); }

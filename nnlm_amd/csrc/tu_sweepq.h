@@ -32,8 +32,9 @@ struct SpmmArgs {
 };
 // launch entries (tu_sparse.hip); f64 selects T = double, else float
 void nnlm_tu_spmm(const SpmmArgs &a, bool f64, hipStream_t st);
+// miss: absent entries are missing -- the second sum is sum wh instead of sum wh^2 (k_sparse_na.h)
 void nnlm_tu_sp_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nworkers,
-                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, hipStream_t st);
+                       const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks, bool miss, hipStream_t st);
 // workers of one launch: a multiple of the workers per wavefront; nnz / workers non-zeros each, at least ~64, at most 16 wavefronts per CU
 int nnlm_sp_workers(long long nnz, int KP, int cus);
 int nnlm_sp_lanes(int KP);
@@ -42,3 +43,24 @@ void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *part
 // out[0] = sum of squares, out[1] = KL sum over all n x m entries from s = {S1, S2, S3}, the Grams and the factors' sums (k_sparse.h)
 void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP, double *out,
                           hipStream_t st);
+
+// Sparse A whose absent entries are missing (k_sparse_na.h, tu_sparse.hip): per-column Grams over the stored rows of columns [c0, c1)
+#define SPG_SEG 2048 // stored entries per segment: a longer column is summed in segments of its own, added in order by the fix-up
+struct SpGramArgs {
+    const long long *ptr;   // [ncols + 1] CSC (H half-step) / CSR (W half-step)
+    const int *idx;         // [nnz] row of the fixed factor of each stored entry
+    const void *Y;          // [rows][KP] T, row-major fixed factor
+    const long long *segoff; // [ncols + 1] segment slots of the long columns in front of column c
+    int c0, c1;             // the launch's columns
+    long long chunk;        // stored entries per worker
+    int nworkers;
+    double *G;              // [c1 - c0][KP][KP] per-column Grams (upper triangle)
+    double *seg;            // segment sums of the launch's long columns, [segoff[c1] - segoff[c0]][KP][KP]
+};
+// workers (one wavefront each) of one Gram launch over nnz stored entries: ~256 each, at most 16 wavefronts per CU
+int nnlm_spg_workers(long long nnz, int cus);
+void nnlm_tu_sp_gram(const SpGramArgs &a, int NKQ, bool f64, hipStream_t st);
+// the nlong long columns longc[0 .. nlong) of the launch: their segment sums into G
+void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int KP, hipStream_t st);
+// out[0] = S1, out[1] = S3 + S2 (sum of squares, KL sum over the stored entries)
+void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st);
