@@ -239,6 +239,14 @@ def c_nnmf(A, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbos
     lib = load()
     A = _f64(A)
     n, m = A.shape
+    return _nnmf(lib.nnlm_c_nnmf, (_dp(A), n, m), n, m, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose,
+                 show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
+
+
+def _nnmf(entry, lead, n, m, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter,
+          inner_rel_tol, method, trace, callbacks):
+    """The body of the c_nnmf entries: lead = the entry's matrix arguments (in front of k)."""
+    lib = load()
     k = int(k)
     Wi = _f64(W, (n, k)) if W is not None and np.size(W) > 0 else None
     Hi = _f64(H, (k, m)) if H is not None and np.size(H) > 0 else None
@@ -249,11 +257,11 @@ def c_nnmf(A, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbos
     Ho = np.zeros((k, m), order="F")
     mse, mkl, terr, ep = (np.zeros(cap) for _ in range(4))
     n_trace, n_it, warned = C.c_int(0), C.c_uint(0), C.c_int(0)
-    rc = lib.nnlm_c_nnmf(_dp(A), n, m, k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
-                         float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
-                         float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
-                         _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
-                         C.byref(callbacks) if callbacks is not None else None)
+    rc = entry(*lead, k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
+               float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
+               float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
+               _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
+               C.byref(callbacks) if callbacks is not None else None)
     _check(rc)
     e = n_trace.value
     return dict(W=np.ascontiguousarray(Wo), H=np.ascontiguousarray(Ho), mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(),
@@ -337,14 +345,18 @@ def c_nnlm(x, y, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callb
     n, p = x.shape
     y = _f64(np.asarray(y, dtype=np.float64).reshape(n, -1))
     q = y.shape[1]
+    return _nnlm(lib.nnlm_c_nnlm, (_dp(x), _dp(y), n, p, q), p, q, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks)
+
+
+def _nnlm(entry, lead, p, q, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks):
+    """The body of the c_nnlm entries: lead = the entry's arguments in front of alpha (x, y and the shape)."""
     b0 = _f64(beta0, (p, q)) if beta0 is not None and np.size(beta0) > 0 else None
     mk = _lgl(mask, (p, q))
     al = _vec3(alpha)
     coef = np.zeros((p, q), order="F")
     nit = C.c_int(0)
-    rc = lib.nnlm_c_nnlm(_dp(x), _dp(y), n, p, q, _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol),
-                         int(n_threads), int(method), _dp(coef), C.byref(nit),
-                         C.byref(callbacks) if callbacks is not None else None)
+    rc = entry(*lead, _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol), int(n_threads), int(method), _dp(coef), C.byref(nit),
+               C.byref(callbacks) if callbacks is not None else None)
     _check(rc)
     return dict(coefficient=np.ascontiguousarray(coef), n_iteration=int(nit.value))
 
@@ -365,29 +377,10 @@ def c_nnmf_csc_missing(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, bet
 
 def _nnmf_csc(entry, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
               inner_max_iter, inner_rel_tol, method, trace, callbacks):
-    lib = load()
     n, m = (int(v) for v in shape)
     ptr, idx, val = _csc_arrays(indptr, indices, data)
-    k = int(k)
-    Wi = _f64(W, (n, k)) if W is not None and np.size(W) > 0 else None
-    Hi = _f64(H, (k, m)) if H is not None and np.size(H) > 0 else None
-    Wm_, Hm_ = _lgl(Wm, (n, k)), _lgl(Hm, (k, m))
-    al, be = _vec3(alpha), _vec3(beta)
-    cap = lib.nnlm_trace_capacity(int(max_iter), int(trace) if int(trace) > 0 else 1)
-    Wo = np.zeros((n, k), order="F")
-    Ho = np.zeros((k, m), order="F")
-    mse, mkl, terr, ep = (np.zeros(cap) for _ in range(4))
-    n_trace, n_it, warned = C.c_int(0), C.c_uint(0), C.c_int(0)
-    rc = entry(n, m, _lp(ptr), _ip(idx), _dp(val), k, _dp(Wi), _dp(Hi), _ip(Wm_), _ip(Hm_), _dp(al), _dp(be), int(max_iter),
-               float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter),
-               float(inner_rel_tol), int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl),
-               _dp(terr), _dp(ep), C.byref(n_trace), C.byref(n_it), C.byref(warned),
-               C.byref(callbacks) if callbacks is not None else None)
-    _check(rc)
-    e = n_trace.value
-    return dict(W=np.ascontiguousarray(Wo), H=np.ascontiguousarray(Ho), mse_error=mse[:e].copy(), mkl_error=mkl[:e].copy(),
-                target_error=terr[:e].copy(), average_epoch=ep[:e].copy(), n_iteration=int(n_it.value),
-                warning=bool(warned.value))
+    return _nnmf(entry, (n, m, _lp(ptr), _ip(idx), _dp(val)), n, m, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose,
+                 show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
 
 
 def c_nnlm_csc(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
@@ -409,15 +402,8 @@ def _nnlm_csc(entry, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0
         raise ValueError("y has %d rows, x has %d" % (int(y_shape[0]), n))
     q = int(y_shape[1])
     ptr, idx, val = _csc_arrays(y_indptr, y_indices, y_data)
-    b0 = _f64(beta0, (p, q)) if beta0 is not None and np.size(beta0) > 0 else None
-    mk = _lgl(mask, (p, q))
-    al = _vec3(alpha)
-    coef = np.zeros((p, q), order="F")
-    nit = C.c_int(0)
-    rc = entry(_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val), _dp(al), _ip(mk), _dp(b0), int(max_iter), float(rel_tol),
-               int(n_threads), int(method), _dp(coef), C.byref(nit), C.byref(callbacks) if callbacks is not None else None)
-    _check(rc)
-    return dict(coefficient=np.ascontiguousarray(coef), n_iteration=int(nit.value))
+    return _nnlm(entry, (_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val)), p, q, alpha, mask, beta0, max_iter, rel_tol, n_threads, method,
+                 callbacks)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -237,6 +237,9 @@ static int fail(nnlm_handle *h, int code, const char *fmt, ...)
     return code;
 }
 
+template <typename... P>
+static bool any_null(const P *...p) { return (... || !p); }
+
 #define HIPCHK(h, call)                                                                                              \
     do {                                                                                                             \
         hipError_t e__ = (call);                                                                                     \
@@ -1211,6 +1214,37 @@ static Side side_of(const nnlm_handle *h, int which)
 // A with the contraction contiguous, [ncols][ldy] in the mode's element type (the W half-step's copy AT: ensure_AT first)
 static const void *a_contig(const nnlm_handle *h, const Side &s) { return s.which == 1 ? h->A : h->AT; }
 
+// The sweep counter a half-step adds to: the active one, or the alternate one of a speculative half-step (accepted by sw_active ^= 1)
+static unsigned long long *sweep_counter(nnlm_handle *h, bool speculative) { return h->sweeps + (speculative ? h->sw_active ^ 1 : h->sw_active); }
+
+// The sweep of side s at rank h->k over all its columns, from the Gram h->Graw and one slab of h->Cx; callers change what differs
+static SweepArgs sweep_args(const nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol,
+                            unsigned long long *sweeps)
+{
+    SweepArgs a;
+    a.X = s.X;
+    a.Xout = s.Xout;
+    a.ldx = a.ldo = a.ldc = s.ldc;
+    a.ocol0 = a.col0 = 0;
+    a.Graw = h->Graw;
+    a.KPg = h->KP;
+    a.Cx = h->Cx;
+    a.slab_stride = s.slab_stride;
+    a.nslabs = 1;
+    a.ncols = s.ncols;
+    a.k = h->k;
+    a.r0 = reg[0], a.r1 = reg[1], a.r2 = reg[2];
+    a.mask = s.mask;
+    a.max_iter = inner_max_iter;
+    a.rel_tol = inner_rel_tol;
+    a.op = s.op;
+    a.op_mode = s.op_mode;
+    a.op_ld = s.op_ld;
+    a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
+    a.sweeps = sweeps;
+    return a;
+}
+
 // contraction elements one stage of a cross product covers (the granularity of the multi-GPU split): 256 bytes of A in the mode's type
 // (the split-fp16 kernels' stages of 64 elements are the same in the fp32-operand mode, the only mode that has them)
 static int stage_elems(const nnlm_handle *h) { return XPROD_ROWB / (int)esize(h); }
@@ -2095,7 +2129,7 @@ static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsi
     a.r2 = reg[2];
     a.max_iter = inner_max_iter;
     a.rel_tol = inner_rel_tol;
-    a.sweeps = h->sweeps + (speculative ? (h->sw_active ^ 1) : h->sw_active);
+    a.sweeps = sweep_counter(h, speculative);
     a.A = h->A;
     a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
     a.X = s.X; a.Xout = s.Xout; a.ldx = s.ldc; a.Y = s.Y; a.ldy = s.ldy;
@@ -2346,27 +2380,7 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
     const size_t slot = (size_t)KP * KP;
     int rc = spg_prepare(h, o, slot);
     if (rc != NNLM_OK) return rc;
-    SweepArgs a;
-    a.KPg = KP;
-    a.Cx = h->Cx;
-    a.nslabs = 1;
-    a.k = h->k;
-    a.r0 = reg[0];
-    a.r1 = reg[1];
-    a.r2 = reg[2];
-    a.max_iter = inner_max_iter;
-    a.rel_tol = inner_rel_tol;
-    a.sweeps = h->sweeps + (speculative ? (h->sw_active ^ 1) : h->sw_active);
-    a.ocol0 = 0;
-    a.X = s.X;
-    a.Xout = s.Xout;
-    a.ldx = a.ldo = a.ldc = s.ldc;
-    a.slab_stride = s.slab_stride;
-    a.mask = s.mask;
-    a.op = s.op;
-    a.op_mode = s.op_mode;
-    a.op_ld = s.op_ld;
-    a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
+    SweepArgs a = sweep_args(h, s, reg, inner_max_iter, inner_rel_tol, sweep_counter(h, speculative));
     SpGramArgs g;
     g.ptr = s.sp_ptr;
     g.idx = s.sp_idx;
@@ -2706,36 +2720,15 @@ static int half_step_solve(nnlm_handle *h, const Side &s, const double reg[3], u
     h->pack_tail = (h->sharded && colshard && method == 1 && !h->any_missing && !generic_rank(h)) ? (size_t)h->KP * h->KP + 1 : 0;
     if (phase != PH_C) {
         ProfScope ps(h, s.prof_sweep);
-        SweepArgs a;
-        a.Graw = h->Graw;
-        a.KPg = h->KP;
-        a.Cx = (h->sharded && !colshard) ? h->red + (size_t)h->KP * h->KP : h->Cx;
-        a.nslabs = (h->sharded && !colshard) ? 1 : nslabs;
-        a.k = h->k;
-        a.r0 = reg[0];
-        a.r1 = reg[1];
-        a.r2 = reg[2];
-        a.max_iter = inner_max_iter;
-        a.rel_tol = inner_rel_tol;
-        a.sweeps = h->sweeps + (speculative ? (h->sw_active ^ 1) : h->sw_active);
-        a.col0 = 0;
-        a.ocol0 = 0;
+        SweepArgs a = sweep_args(h, s, reg, inner_max_iter, inner_rel_tol, sweep_counter(h, speculative));
+        if (h->sharded && !colshard) a.Cx = h->red + (size_t)h->KP * h->KP; // (the all-reduced [G | C] buffer: one slab)
+        else a.nslabs = nslabs;
         const bool sg = h->sg_request; // (only on the dense one-GPU split-fp16 path, where k_sweep_q.h runs)
         h->sg_request = false;
         if (sg) {
             a.maxbits = h->x16 ? h->maxbits + 4 + (h->sg_par ^ 1) : nullptr; // (max|x| is the split copy's scale: fp32-operand mode only)
             a.gram_slabs = h->sg_slabs;
         }
-        a.X = s.X;
-        a.Xout = s.Xout;
-        a.ldx = a.ldo = a.ldc = s.ldc;
-        a.slab_stride = s.slab_stride;
-        a.ncols = s.ncols;
-        a.mask = s.mask;
-        a.op = s.op;
-        a.op_mode = s.op_mode;
-        a.op_ld = s.op_ld;
-        a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
         if (h->sharded) { // sweep only this rank's columns into the packed slab; the unpack writes masters and operands
             ShardCols sc;
             int rcp = pack_prepare(h, s.ncols, &sc, h->pack_tail);
@@ -3279,6 +3272,86 @@ static double penalties(double terr, const double pen[6], double N, const double
     return terr;
 }
 
+// What the alternating loops of nnlm_run (one model) and nnlm_run_batch (one per member) share of the reference's outer loop,
+// src/nnmf.cpp:100-209: their arguments, the checks, the trace setup and the poll at the top of every iteration.
+struct OuterLoop {
+    nnlm_handle *h;
+    const double *alpha, *beta;
+    unsigned max_iter;
+    double rel_tol;
+    int verbose, show_warning, method;
+    unsigned trace;
+    double *mse_error, *mkl_error, *target_error, *average_epoch; // [models][cap]
+    int *n_trace;
+    unsigned *n_iteration;
+    int *warned;
+    const nnlm_callbacks *cb;
+    unsigned cap = 0; // trace entries of one model
+    bool need_pen = false;
+
+    int check(const char *who) const
+    {
+        if (any_null(alpha, beta, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned))
+            return fail(h, NNLM_ERR_ARG, "%s: NULL argument", who);
+        if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
+        return NNLM_OK;
+    }
+    void start(unsigned models)
+    {
+        if (trace < 1) trace = 1; // src/nnmf.cpp:53
+        cap = nnlm_trace_capacity(max_iter, trace);
+        for (size_t e = 0; e < (size_t)models * cap; e++) mkl_error[e] = h->kl_const; // src/nnmf.cpp:70,73
+        // the six penalty sums are read by penalties() only through these conditions (src/nnmf.cpp:224-240)
+        need_pen = alpha[0] != alpha[1] || beta[0] != beta[1] || alpha[1] != 0 || beta[1] != 0 || alpha[2] != 0 || beta[2] != 0;
+    }
+    int poll(unsigned i) const
+    {
+        if (cb && cb->check_interrupt && cb->check_interrupt(cb->ctx)) { // src/nnmf.cpp:111
+            sync_all(h);
+            return fail(h, NNLM_ERR_INTERRUPT, "interrupted");
+        }
+        if (verbose == 1 && cb && cb->progress) cb->progress(cb->ctx, i + 1, max_iter); // src/nnmf.cpp:112
+        return NNLM_OK;
+    }
+    bool closing_entry(unsigned i) const { return (unsigned)(i - 1) % trace != 0; } // src/nnmf.cpp:164 (unsigned arithmetic)
+};
+
+// The stopping rule of one model and its trace: entries base .. base + cap - 1 of the four arrays (src/nnmf.cpp:135-160, 208)
+struct StopRule {
+    int member;      // the batch member its verbose rows name; -1 in a solo run
+    size_t base;
+    double rel_err;  // rel_tol + 1 before the first entry
+    double terr_last = 1e99;
+    unsigned n = 0;  // entries booked
+    bool running(const OuterLoop &L) const { return std::fabs(rel_err) > L.rel_tol; } // src/nnmf.cpp:109
+    // mse, kl: the sums already divided by the non-missing entries of A; raw: the sweeps since the previous entry
+    void book(const OuterLoop &L, unsigned it, double mse, double kl, const double pen[6], long long raw)
+    {
+        const size_t e = base + n++;
+        L.mse_error[e] = mse;
+        L.mkl_error[e] += kl;
+        L.average_epoch[e] = (double)raw / (double)(L.h->n + L.h->m); // src/nnmf.cpp:145
+        const double t = penalties((L.method < 3) ? 0.5 * mse : L.mkl_error[e], pen, L.h->n_non_missing, L.alpha, L.beta);
+        L.target_error[e] = t;
+        rel_err = 2 * (terr_last - t) / (terr_last + t + NNLM_TINY); // src/nnmf.cpp:153
+        terr_last = t;
+        if (L.verbose == 2) {
+            char row[512];
+            snprintf(row, sizeof row, "%10d | %10.4f | %10.4f | %10.4f | %10.g\n", it + 1, mse, L.mkl_error[e], t, rel_err);
+            if (member < 0) cb_print(L.cb, "%s", row);
+            else cb_print(L.cb, "%6d %s", member, row);
+        }
+    }
+    void finish(const OuterLoop &L, unsigned n_iteration)
+    {
+        const size_t b = member < 0 ? 0 : member;
+        L.n_trace[b] = (int)n;
+        L.n_iteration[b] = n_iteration;
+        L.warned[b] = (L.show_warning && rel_err > L.rel_tol) ? 1 : 0; // src/nnmf.cpp:208
+        if (L.warned[b] && L.cb && L.cb->warning) L.cb->warning(L.cb->ctx, "Target tolerance not reached. Try a larger max.iter.");
+    }
+};
+
 // The alternating loop of c_nnmf (reference src/nnmf.cpp:100-209) on a resident handle: matrix and factors are already in
 // HBM.  Semantics are the reference's, iteration by iteration.  What is MI355X-specific is the schedule at a trace
 // iteration: the error block runs on its own stream (HBM/MFMA bound) while the NEXT iteration's W half-step is enqueued
@@ -3291,13 +3364,13 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                         unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
 {
     if (!has_matrix(h) || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_run: matrix and factors must be set first");
-    if (!alpha || !beta || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace || !n_iteration || !warned)
-        return fail(h, NNLM_ERR_ARG, "nnlm_run: NULL argument");
-    if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
+    OuterLoop L{h, alpha, beta, max_iter, rel_tol, verbose, show_warning, method, trace, mse_error, mkl_error, target_error, average_epoch,
+                n_trace, n_iteration, warned, cb};
+    int rc = L.check("nnlm_run");
+    if (rc != NNLM_OK) return rc;
     if (h->sparse && method >= 3)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     HIPCHK(h, hipSetDevice(h->device));
-    int rc;
 #define CHK(x)                  \
     do {                        \
         rc = (x);               \
@@ -3307,33 +3380,13 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
         }                       \
     } while (0)
 
-    if (trace < 1) trace = 1; // src/nnmf.cpp:53
-    const unsigned err_len = nnlm_trace_capacity(max_iter, trace);
-    const double N = h->n_non_missing;
-    const int n = h->n, m = h->m;
-    for (unsigned e = 0; e < err_len; e++) mkl_error[e] = h->kl_const; // src/nnmf.cpp:70,73
-
+    L.start(1);
     if (verbose == 2) { // src/nnmf.cpp:100-104
         cb_print(cb, "\n%10s | %10s | %10s | %10s | %10s\n", "Iteration", "MSE", "MKL", "Target", "Rel. Err.");
         cb_print(cb, "--------------------------------------------------------------\n");
     }
-
-    // the six penalty sums are read by penalties() only through these conditions (src/nnmf.cpp:224-240)
-    const bool need_pen = alpha[0] != alpha[1] || beta[0] != beta[1] || alpha[1] != 0 || beta[1] != 0 || alpha[2] != 0 || beta[2] != 0;
-    double rel_err = rel_tol + 1, terr_last = 1e99;
-    unsigned i = 0, i_e = 0;
-    auto book = [&](unsigned it, double mse, double kl, const double pen[6], long long raw) {
-        mse_error[i_e] = mse;
-        mkl_error[i_e] += kl;
-        average_epoch[i_e] = (double)raw / (double)(n + m); // src/nnmf.cpp:145
-        double t = (method < 3) ? 0.5 * mse_error[i_e] : mkl_error[i_e];
-        t = penalties(t, pen, N, alpha, beta);
-        target_error[i_e] = t;
-        rel_err = 2 * (terr_last - t) / (terr_last + t + NNLM_TINY); // src/nnmf.cpp:153
-        terr_last = t;
-        if (verbose == 2) cb_print(cb, "%10d | %10.4f | %10.4f | %10.4f | %10.g\n", it + 1, mse_error[i_e], mkl_error[i_e], t, rel_err);
-        ++i_e;
-    };
+    StopRule rule{-1, 0, rel_tol + 1};
+    unsigned i = 0;
 
     // spec.pending: the W half-step of iteration i is already enqueued (speculatively).  Whatever way this function is left
     // with one pending (stopping rule, interrupt, a failed call), the guard drops it: W_i is untouched, the alternate sweep
@@ -3348,18 +3401,13 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
             h->gshard_for = h->upk_max_for = h->y16_for = -1; // (multi-GPU: what the dropped half-step's unpack left behind describes a W that is not current)
             h->fuse_err = false;
             h->fused_nb = 0;
-            hipMemsetAsync(h->sweeps + (h->sw_active ^ 1), 0, sizeof(unsigned long long), h->stream);
+            hipMemsetAsync(sweep_counter(h, true), 0, sizeof(unsigned long long), h->stream);
             pending = false;
         }
         ~SpecDrop() { drop(); }
     } spec{h};
-    for (; i < max_iter && std::fabs(rel_err) > rel_tol; i++) { // src/nnmf.cpp:109
-        if (cb && cb->check_interrupt && cb->check_interrupt(cb->ctx)) { // src/nnmf.cpp:111
-            sync_all(h);
-            g_last_error = "interrupted";
-            return NNLM_ERR_INTERRUPT;
-        }
-        if (verbose == 1 && cb && cb->progress) cb->progress(cb->ctx, i + 1, max_iter); // src/nnmf.cpp:112
+    for (; i < max_iter && rule.running(L); i++) { // src/nnmf.cpp:109
+        CHK(L.poll(i));
         if (spec.pending) { // accept: its buffers and its sweep counter become the current ones
             swap_w(h);
             h->sw_active ^= 1;
@@ -3367,7 +3415,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
         } else
             CHK(half_step(h, 0, alpha, inner_max_iter, inner_rel_tol, method)); // update W, src/nnmf.cpp:131
         CHK(half_step(h, 1, beta, inner_max_iter, inner_rel_tol, method));      // update H, src/nnmf.cpp:133
-        if (i % trace == 0) {                                                   // src/nnmf.cpp:135-160
+        if (i % L.trace == 0) {                                                 // src/nnmf.cpp:135-160
             HIPCHK(h, hipEventRecord(h->ev_hdone, h->stream));
             HIPCHK(h, hipStreamWaitEvent(h->stream_e, h->ev_hdone, 0));
             // (multi-GPU: the dense square-loss flows of the fp32-operand mode at rank <= 64 -- every rank's speculative cross product
@@ -3386,7 +3434,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                 h->fuse_err = h->x16 && !generic_rank(h);
                 h->fused_nb = 0;
                 h->err_hook = h->sharded;
-                h->err_need_pen = need_pen;
+                h->err_need_pen = L.need_pen;
                 rc = half_step(h, 0, alpha, inner_max_iter, inner_rel_tol, method, false, true);
                 h->fuse_err = false;
                 h->err_hook = false;
@@ -3405,7 +3453,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                 if (h->prec == NNLM_PREC_F64 && !h->fused_nb) HIPCHK(h, hipStreamWaitEvent(h->stream_e, h->ev_xdone, 0));
             } else
                 h->fused_nb = 0;
-            if (!h->err_launched) CHK(errors_launch(h, h->stream_e, true, h->fused_nb, need_pen)); // reads W_i, H_i and the active sweep counter (then zeroes it)
+            if (!h->err_launched) CHK(errors_launch(h, h->stream_e, true, h->fused_nb, L.need_pen)); // reads W_i, H_i and the active sweep counter (then zeroes it)
             h->err_launched = false;
             h->fused_nb = 0;
             // H (and the fp32 copy the error kernel reads) must not be rewritten before the error block is done
@@ -3413,16 +3461,16 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
             double mse, kl, pen[6];
             long long raw = 0;
             CHK(errors_collect(h, &mse, &kl, pen, &raw));
-            book(i, mse, kl, pen, raw);
+            rule.book(L, i, mse, kl, pen, raw);
         }
     }
     spec.drop(); // the stopping rule fired: the speculative half-step (if any) is discarded, W_i is untouched
-    if ((unsigned)(i - 1) % trace != 0) { // src/nnmf.cpp:164 (unsigned arithmetic)
+    if (L.closing_entry(i)) {
         double mse, kl, pen[6];
         long long raw = 0;
-        CHK(errors_launch(h, h->stream, true, 0, need_pen)); // (error sums and the sweep counter in one round trip)
+        CHK(errors_launch(h, h->stream, true, 0, L.need_pen)); // (error sums and the sweep counter in one round trip)
         CHK(errors_collect(h, &mse, &kl, pen, &raw));
-        book(i, mse, kl, pen, raw);
+        rule.book(L, i, mse, kl, pen, raw);
     }
 
     if (verbose == 2) { // src/nnmf.cpp:194-198
@@ -3431,10 +3479,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
     }
     sync_all(h);
     LAUNCHCHK(h);
-    *n_trace = (int)i_e;
-    *n_iteration = i;
-    *warned = (show_warning && rel_err > rel_tol) ? 1 : 0; // src/nnmf.cpp:208
-    if (*warned && cb && cb->warning) cb->warning(cb->ctx, "Target tolerance not reached. Try a larger max.iter.");
+    rule.finish(L, i);
     return NNLM_OK;
 }
 
@@ -3452,21 +3497,32 @@ static int batch_refusal(nnlm_handle *h, const char *who)
     return NNLM_OK;
 }
 
+// The members' ranks: 1 <= B <= BATCH_MAX of them (need: what the message asks for), each >= 1 (NNLM_ERR_ARG); then the caller's own
+// refusals (refuse()); then a sum of at most 64 (NNLM_ERR_UNSUPPORTED)
+template <typename Refuse>
+static int batch_ranks(nnlm_handle *h, const char *who, const char *need, unsigned B, const unsigned *k, Refuse refuse)
+{
+    if (B < 1 || B > BATCH_MAX || !k) return fail(h, NNLM_ERR_ARG, "%s: need 1 <= B <= %d %s (B = %u)", who, BATCH_MAX, need, B);
+    long K = 0;
+    for (unsigned b = 0; b < B; b++) {
+        if (k[b] < 1) return fail(h, NNLM_ERR_ARG, "%s: rank of member %u must be >= 1", who, b);
+        K += k[b];
+    }
+    const int rc = refuse();
+    if (rc != NNLM_OK) return rc;
+    if (K > NNLM_KQ_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the ranks sum to %ld; a batch holds at most %d", who, K, NNLM_KQ_MAX);
+    return NNLM_OK;
+}
+
 extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned *k, const double *W, const double *H)
 {
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: set the matrix first");
-    if (B < 1 || B > BATCH_MAX || !k) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: need 1 <= B <= %d members and their ranks (B = %u)", BATCH_MAX, B);
-    long K = 0;
-    for (unsigned b = 0; b < B; b++) {
-        if (k[b] < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: rank of member %u must be >= 1", b);
-        K += k[b];
-    }
-    int rc = batch_refusal(h, "nnlm_set_factors_batch");
+    int rc = batch_ranks(h, "nnlm_set_factors_batch", "members and their ranks", B, k, [&] { return batch_refusal(h, "nnlm_set_factors_batch"); });
     if (rc != NNLM_OK) return rc;
-    if (K > NNLM_KQ_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_factors_batch: the ranks sum to %ld; a batch holds at most %d", K, NNLM_KQ_MAX);
     const int m = h->m;
     std::vector<int> off(B + 1, 0);
     for (unsigned b = 0; b < B; b++) off[b + 1] = off[b] + (int)k[b];
+    const int K = off[B];
     // H arrives as the members' k_b x m blocks one after another: the stacked K x m matrix, column-major
     std::vector<double> Hs;
     if (H) {
@@ -3479,7 +3535,7 @@ extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned
         }
     }
     // (W: the members' n x k_b blocks one after another ARE the stacked n x K matrix)
-    rc = set_factors_impl(h, (int)K, W, H ? Hs.data() : nullptr, nullptr, nullptr, 64);
+    rc = set_factors_impl(h, K, W, H ? Hs.data() : nullptr, nullptr, nullptr, 64);
     if (rc != NNLM_OK) return rc;
     h->bB = (int)B;
     h->bk.assign(k, k + B);
@@ -3563,27 +3619,15 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
             const int nb = launch_gram_partial(h, s.Y + (size_t)o * s.ldy, s.ldy, 0, s.p, h->gslabs, nullptr, h->stream);
             gram_fold_kernel<<<h->KP * h->KP / 64, 1024, 0, h->stream>>>(h->gslabs, nb, h->KP, G, SweepImg{});
         }
-        SweepArgs a;
+        // (the member's rows of the stacked slabs and factor; a batch has no masks)
+        SweepArgs a = sweep_args(h, s, reg, inner_max_iter, inner_rel_tol, h->bsweeps + b);
         a.Graw = G;
-        a.KPg = h->KP;
         a.Cx = h->Cx + (size_t)o * s.ldc;
-        a.slab_stride = s.slab_stride;
         a.nslabs = p.S;
-        a.k = kb;
-        a.r0 = reg[0], a.r1 = reg[1], a.r2 = reg[2];
-        a.max_iter = inner_max_iter;
-        a.rel_tol = inner_rel_tol;
-        a.sweeps = h->bsweeps + b;
-        a.col0 = a.ocol0 = 0;
         a.X = s.X + (size_t)o * s.ldc;
         a.Xout = s.Xout + (size_t)o * s.ldc;
-        a.ldx = a.ldo = a.ldc = s.ldc;
-        a.ncols = s.ncols;
-        a.mask = nullptr;
-        a.op = s.op ? (void *)((char *)s.op + (size_t)o * s.op_ld * es) : nullptr;
-        a.op_mode = s.op ? s.op_mode : 0;
-        a.op_ld = s.op_ld;
-        a.op_f64 = (h->prec == NNLM_PREC_F64) ? 1 : 0;
+        if (s.op) a.op = (char *)s.op + (size_t)o * s.op_ld * es;
+        else a.op_mode = 0;
         h->pack_ready = false; // (strict mode: the sweep packs its operand image from this member's Gram)
         ProfScope ps(h, s.prof_sweep);
         rc = launch_sweep(h, method, a);
@@ -3645,38 +3689,27 @@ extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const doubl
                               unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
 {
     if (!h || !h->bB) return fail(h, NNLM_ERR_ARG, "nnlm_run_batch: set the matrix and a batch of factors (nnlm_set_factors_batch) first");
-    if (!alpha || !beta || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace || !n_iteration || !warned)
-        return fail(h, NNLM_ERR_ARG, "nnlm_run_batch: NULL argument");
-    if (method < 1 || method > 4) return fail(h, NNLM_ERR_ARG, "method must be 1..4 (got %d)", method);
+    OuterLoop L{h, alpha, beta, max_iter, rel_tol, verbose, show_warning, method, trace, mse_error, mkl_error, target_error, average_epoch,
+                n_trace, n_iteration, warned, cb};
+    int rc = L.check("nnlm_run_batch");
+    if (rc != NNLM_OK) return rc;
     if (method >= 3) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_run_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
-    int rc = batch_refusal(h, "nnlm_run_batch");
+    rc = batch_refusal(h, "nnlm_run_batch");
     if (rc != NNLM_OK) return rc;
     HIPCHK(h, hipSetDevice(h->device));
     sync_all(h);
-    const int B = h->bB, n = h->n, m = h->m;
-    if (trace < 1) trace = 1;
-    const unsigned cap = nnlm_trace_capacity(max_iter, trace);
-    const double N = h->n_non_missing;
-    for (size_t e = 0; e < (size_t)B * cap; e++) mkl_error[e] = h->kl_const;
-    const bool need_pen = alpha[0] != alpha[1] || beta[0] != beta[1] || alpha[1] != 0 || beta[1] != 0 || alpha[2] != 0 || beta[2] != 0;
-    std::vector<double> rel_err(B, rel_tol + 1), terr_last(B, 1e99);
-    std::vector<unsigned> i_e(B, 0), nit(B, 0);
+    const int B = h->bB;
+    L.start(B);
+    std::vector<StopRule> rule;
+    for (int b = 0; b < B; b++) rule.push_back(StopRule{b, (size_t)b * L.cap, rel_tol + 1});
+    std::vector<unsigned> nit(B, 0);
     std::vector<char> act(B, 1);
     std::vector<double> res;
     std::vector<long long> sw;
     auto book = [&](int b, unsigned it) {
-        const size_t e = (size_t)b * cap + i_e[b];
-        mse_error[e] = res[2 * b] / N;
-        mkl_error[e] += res[2 * b + 1] / N;
-        average_epoch[e] = (double)sw[b] / (double)(n + m); // src/nnmf.cpp:145
         double pen[6];
         for (int c = 0; c < 3; c++) pen[c] = res[2 * B + 3 * b + c], pen[3 + c] = res[5 * B + 3 * b + c];
-        const double t = penalties(0.5 * mse_error[e], pen, N, alpha, beta);
-        target_error[e] = t;
-        rel_err[b] = 2 * (terr_last[b] - t) / (terr_last[b] + t + NNLM_TINY); // src/nnmf.cpp:153
-        terr_last[b] = t;
-        if (verbose == 2) cb_print(cb, "%6d %10d | %10.4f | %10.4f | %10.4f | %10.g\n", b, it + 1, mse_error[e], mkl_error[e], t, rel_err[b]);
-        ++i_e[b];
+        rule[b].book(L, it, res[2 * b] / h->n_non_missing, res[2 * b + 1] / h->n_non_missing, pen, sw[b]);
     };
     auto mask_of = [&](const std::vector<char> &f) {
         unsigned long long mk = 0;
@@ -3690,19 +3723,15 @@ extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const doubl
     }
     unsigned i = 0;
     for (; i < max_iter && mask_of(act); i++) {
-        if (cb && cb->check_interrupt && cb->check_interrupt(cb->ctx)) {
-            sync_all(h);
-            return fail(h, NNLM_ERR_INTERRUPT, "interrupted");
-        }
-        if (verbose == 1 && cb && cb->progress) cb->progress(cb->ctx, i + 1, max_iter);
+        CHK(L.poll(i));
         CHK(batch_half_step(h, 0, alpha, inner_max_iter, inner_rel_tol, method, act)); // update W, src/nnmf.cpp:131
         CHK(batch_half_step(h, 1, beta, inner_max_iter, inner_rel_tol, method, act));  // update H, src/nnmf.cpp:133
-        if (i % trace == 0) {
-            CHK(batch_errors(h, mask_of(act), need_pen, res, sw));
+        if (i % L.trace == 0) {
+            CHK(batch_errors(h, mask_of(act), L.need_pen, res, sw));
             for (int b = 0; b < B; b++) {
                 if (!act[b]) continue;
                 book(b, i);
-                if (!(std::fabs(rel_err[b]) > rel_tol)) { // src/nnmf.cpp:109: this member's loop ends after iteration i
+                if (!rule[b].running(L)) { // src/nnmf.cpp:109: this member's loop ends after iteration i
                     act[b] = 0;
                     nit[b] = i + 1;
                 }
@@ -3714,22 +3743,59 @@ extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const doubl
     for (int b = 0; b < B; b++)
         if (act[b]) {
             nit[b] = i;
-            last[b] = ((unsigned)(i - 1) % trace != 0);
+            last[b] = L.closing_entry(i);
         }
     if (mask_of(last)) {
-        CHK(batch_errors(h, mask_of(last), need_pen, res, sw));
+        CHK(batch_errors(h, mask_of(last), L.need_pen, res, sw));
         for (int b = 0; b < B; b++)
             if (last[b]) book(b, i);
     }
     sync_all(h);
     LAUNCHCHK(h);
-    for (int b = 0; b < B; b++) {
-        n_trace[b] = (int)i_e[b];
-        n_iteration[b] = nit[b];
-        warned[b] = (show_warning && rel_err[b] > rel_tol) ? 1 : 0; // src/nnmf.cpp:208
-        if (warned[b] && cb && cb->warning) cb->warning(cb->ctx, "Target tolerance not reached. Try a larger max.iter.");
-    }
+    for (int b = 0; b < B; b++) rule[b].finish(L, nit[b]);
     return NNLM_OK;
+}
+
+// The handle of a one-shot entry: created on NNLM_DEVICE in the NNLM_PRECISION mode and given the matrix (set_matrix(h)); destroyed
+// when the entry returns
+struct OneShot {
+    nnlm_handle *h = nullptr;
+    template <typename SetMatrix>
+    int open(SetMatrix set_matrix)
+    {
+        const int rc = nnlm_create(&h, env_device(), env_precision());
+        return rc != NNLM_OK ? rc : set_matrix(h);
+    }
+    ~OneShot() { nnlm_destroy(h); }
+};
+
+// default init of the c_nnmf one-shots, src/nnmf.cpp:82-98: 0.01 U(0,1) from cb->unif_rand or the built-in generator, member by member
+// (ranks k[0 .. B-1]), W before H, W.randu(k, n) drawn column-major (row q of W fastest), masked entries (solo runs only) drawn and
+// zeroed.  Only a factor the caller left NULL is drawn: *W / *H then point at the draw.
+static void default_factors(const nnlm_callbacks *cb, int n, int m, unsigned B, const unsigned *k, const int *Wm, const int *Hm,
+                            const double **W, const double **H, std::vector<double> &Wi, std::vector<double> &Hi)
+{
+    size_t K = 0;
+    for (unsigned b = 0; b < B; b++) K += k[b];
+    if (!*W) Wi.resize((size_t)n * K);
+    if (!*H) Hi.resize(K * m);
+    Lcg lcg;
+    auto draw = [&]() { return (cb && cb->unif_rand) ? cb->unif_rand(cb->ctx) : lcg.next(); };
+    for (size_t b = 0, wo = 0, ho = 0; b < B; wo += (size_t)n * k[b], ho += (size_t)k[b] * m, b++) {
+        if (!*W)
+            for (int i = 0; i < n; i++)
+                for (unsigned q = 0; q < k[b]; q++) {
+                    const double v = draw() * 0.01; // (Wm > 0 on the reference's unsigned matrix: any non-zero, NA_LOGICAL included)
+                    Wi[wo + (size_t)q * n + i] = (Wm && Wm[(size_t)q * n + i] != 0) ? 0.0 : v;
+                }
+        if (!*H)
+            for (size_t e = 0; e < (size_t)k[b] * m; e++) {
+                const double v = draw() * 0.01;
+                Hi[ho + e] = (Hm && Hm[e] != 0) ? 0.0 : v;
+            }
+    }
+    if (!*W) *W = Wi.data();
+    if (!*H) *H = Hi.data();
 }
 
 // create + set_matrix + set_factors_batch + run_batch + get_factors_batch.  W_init / H_init: the members' n x k_b / k_b x m blocks one
@@ -3741,47 +3807,19 @@ extern "C" int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, cons
                                  unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!A || !k || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
-        !n_iteration || !warned)
+    if (any_null(A, k, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned))
         return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: NULL argument");
-    if (B < 1 || B > BATCH_MAX) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: need 1 <= B <= %d members (B = %u)", BATCH_MAX, B);
-    long K = 0;
-    for (unsigned b = 0; b < B; b++) {
-        if (k[b] < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_batch: rank of member %u must be >= 1", b);
-        K += k[b];
-    }
-    if (method >= 3 && method <= 4)
-        return fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
-    if (K > NNLM_KQ_MAX) return fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_batch: the ranks sum to %ld; a batch holds at most %d", K, NNLM_KQ_MAX);
-    nnlm_handle *h = nullptr;
-    int rc = nnlm_create(&h, env_device(), env_precision());
+    int rc = batch_ranks(nullptr, "nnlm_c_nnmf_batch", "members", B, k, [&] {
+        return (method >= 3 && method <= 4) ? fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method)
+                                            : NNLM_OK;
+    });
     if (rc != NNLM_OK) return rc;
-    struct Guard {
-        nnlm_handle *h;
-        ~Guard() { nnlm_destroy(h); }
-    } guard{h};
-    CHK(nnlm_set_matrix(h, A, n, m));
+    OneShot os;
+    rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix(h, A, n, m); });
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
     std::vector<double> Wi, Hi;
-    if (!W_init || !H_init) {
-        Lcg lcg;
-        auto draw = [&]() { return (cb && cb->unif_rand) ? cb->unif_rand(cb->ctx) : lcg.next(); };
-        Wi.resize((size_t)n * K);
-        Hi.resize((size_t)K * m);
-        size_t wo = 0, ho = 0;
-        for (unsigned b = 0; b < B; b++) {
-            const size_t wn = (size_t)n * k[b], hn = (size_t)k[b] * m;
-            if (!W_init) // (src/nnmf.cpp:82-88: randu(k, n) * 0.01 drawn column-major, i.e. row q of W fastest)
-                for (int i = 0; i < n; i++)
-                    for (unsigned q = 0; q < k[b]; q++) Wi[wo + (size_t)q * n + i] = draw() * 0.01;
-            if (!H_init)
-                for (size_t e = 0; e < hn; e++) Hi[ho + e] = draw() * 0.01;
-            wo += wn, ho += hn;
-        }
-        if (W_init) memcpy(Wi.data(), W_init, Wi.size() * 8);
-        if (H_init) memcpy(Hi.data(), H_init, Hi.size() * 8);
-        W_init = Wi.data();
-        H_init = Hi.data();
-    }
+    default_factors(cb, n, m, B, k, nullptr, nullptr, &W_init, &H_init, Wi, Hi);
     CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
     CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
                        mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
@@ -3789,46 +3827,24 @@ extern "C" int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, cons
     return NNLM_OK;
 }
 
-// The one-shot entries share these bodies; the dense and the sparse entries differ only in how the matrix is set (set_matrix(h)).
+// The one-shot entries share these bodies; the dense and the sparse entries differ only in how the matrix is set (set_matrix(h)) and in
+// the name their errors carry (who); matrix: the entry's first matrix array, checked for NULL.
 template <typename SetMatrix>
-static int c_nnmf_body(SetMatrix set_matrix, int n, int m, unsigned k, const double *W_init, const double *H_init, const int *Wm, const int *Hm,
-                       const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int verbose, int show_warning,
-                       unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out, double *H_out, double *mse_error,
-                       double *mkl_error, double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
-                       const nnlm_callbacks *cb)
+static int c_nnmf_body(const char *who, const void *matrix, SetMatrix set_matrix, int n, int m, unsigned k, const double *W_init, const double *H_init,
+                       const int *Wm, const int *Hm, const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int verbose,
+                       int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out, double *H_out,
+                       double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration,
+                       int *warned, const nnlm_callbacks *cb)
 {
-    nnlm_handle *h = nullptr;
-    int rc = nnlm_create(&h, env_device(), env_precision());
+    if (any_null(matrix, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned))
+        return fail(nullptr, NNLM_ERR_ARG, "%s: NULL argument", who);
+    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "%s: k must be >= 1", who);
+    OneShot os;
+    int rc = os.open(set_matrix);
     if (rc != NNLM_OK) return rc;
-    struct Guard {
-        nnlm_handle *h;
-        ~Guard() { nnlm_destroy(h); }
-    } guard{h};
-    CHK(set_matrix(h));
-
-    // default init, src/nnmf.cpp:82-98: W.randu(k,n)*0.01 drawn column-major, W first, masked entries zeroed
+    nnlm_handle *h = os.h;
     std::vector<double> Wi, Hi;
-    Lcg lcg;
-    auto draw = [&]() { return (cb && cb->unif_rand) ? cb->unif_rand(cb->ctx) : lcg.next(); };
-    if (!W_init) {
-        Wi.resize((size_t)n * k);
-        for (int i = 0; i < n; i++)
-            for (unsigned q = 0; q < k; q++) {
-                double v = draw() * 0.01;
-                if (Wm && Wm[(size_t)q * n + i] != 0) v = 0.0; // (Wm > 0 on the reference's unsigned matrix: any non-zero, NA_LOGICAL included)
-                Wi[(size_t)q * n + i] = v;
-            }
-        W_init = Wi.data();
-    }
-    if (!H_init) {
-        Hi.resize((size_t)k * m);
-        for (size_t e = 0; e < (size_t)k * m; e++) {
-            double v = draw() * 0.01;
-            if (Hm && Hm[e] != 0) v = 0.0;
-            Hi[e] = v;
-        }
-        H_init = Hi.data();
-    }
+    default_factors(cb, n, m, 1, &k, Wm, Hm, &W_init, &H_init, Wi, Hi);
     CHK(nnlm_set_factors(h, k, W_init, H_init, Wm, Hm));
     CHK(nnlm_run(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
                  mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
@@ -3844,13 +3860,9 @@ extern "C" int nnlm_c_nnmf(const double *A, int n, int m, unsigned k, const doub
                            const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!A || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
-        !n_iteration || !warned)
-        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: NULL argument");
-    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf: k must be >= 1");
-    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix(h, A, n, m); }, n, m, k, W_init, H_init, Wm, Hm, alpha, beta, max_iter,
-                       rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out, mse_error, mkl_error,
-                       target_error, average_epoch, n_trace, n_iteration, warned, cb);
+    return c_nnmf_body("nnlm_c_nnmf", A, [&](nnlm_handle *h) { return nnlm_set_matrix(h, A, n, m); }, n, m, k, W_init, H_init, Wm, Hm, alpha,
+                       beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
 extern "C" int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
@@ -3861,13 +3873,9 @@ extern "C" int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int 
                                const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!colptr || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
-        !n_iteration || !warned)
-        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc: NULL argument");
-    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc: k must be >= 1");
-    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, m, colptr, rowidx, x); }, n, m, k, W_init, H_init, Wm, Hm, alpha,
-                       beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out, mse_error,
-                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+    return c_nnmf_body("nnlm_c_nnmf_csc", colptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, m, colptr, rowidx, x); }, n, m, k,
+                       W_init, H_init, Wm, Hm, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
+                       trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
 extern "C" int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
@@ -3878,28 +3886,23 @@ extern "C" int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, co
                                        int *warned, const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!colptr || !alpha || !beta || !W_out || !H_out || !mse_error || !mkl_error || !target_error || !average_epoch || !n_trace ||
-        !n_iteration || !warned)
-        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_missing: NULL argument");
-    if (k < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_missing: k must be >= 1");
-    return c_nnmf_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, m, colptr, rowidx, x); }, n, m, k, W_init, H_init, Wm, Hm,
-                       alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, W_out, H_out,
-                       mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+    return c_nnmf_body("nnlm_c_nnmf_csc_missing", colptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, m, colptr, rowidx, x); },
+                       n, m, k, W_init, H_init, Wm, Hm, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol,
+                       method, trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
 template <typename SetMatrix>
-static int c_nnlm_body(SetMatrix set_matrix, const double *x, int n, int p, int q, const double alpha[3], const int *mask, const double *beta0,
-                       unsigned max_iter, double rel_tol, int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
+static int c_nnlm_body(const char *who, const void *y, SetMatrix set_matrix, const double *x, int n, int p, int q, const double alpha[3],
+                       const int *mask, const double *beta0, unsigned max_iter, double rel_tol, int method, double *coefficient, int *n_iteration,
+                       const nnlm_callbacks *cb)
 {
-    nnlm_handle *h = nullptr;
-    int rc = nnlm_create(&h, env_device(), env_precision());
-    if (rc != NNLM_OK) return rc;
-    struct Guard {
-        nnlm_handle *h;
-        ~Guard() { nnlm_destroy(h); }
-    } guard{h};
+    if (any_null(x, y, alpha, coefficient, n_iteration)) return fail(nullptr, NNLM_ERR_ARG, "%s: NULL argument", who);
+    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "%s: empty x or y", who);
     // y plays A (n x q), x plays W (n x p), beta plays H (p x q): one H half-step, src/nnlm.cpp:44-47
-    CHK(set_matrix(h));
+    OneShot os;
+    int rc = os.open(set_matrix);
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
     std::vector<double> b0;
     if (!beta0) { // beta.randu(), src/nnlm.cpp:38-39
         b0.resize((size_t)p * q);
@@ -3921,10 +3924,8 @@ extern "C" int nnlm_c_nnlm(const double *x, const double *y, int n, int p, int q
                            int *n_iteration, const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!x || !y || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: NULL argument");
-    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm: empty x or y");
-    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix(h, y, n, q); }, x, n, p, q, alpha, mask, beta0, max_iter, rel_tol, method,
-                       coefficient, n_iteration, cb);
+    return c_nnlm_body("nnlm_c_nnlm", y, [&](nnlm_handle *h) { return nnlm_set_matrix(h, y, n, q); }, x, n, p, q, alpha, mask, beta0, max_iter,
+                       rel_tol, method, coefficient, n_iteration, cb);
 }
 
 extern "C" int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
@@ -3932,10 +3933,8 @@ extern "C" int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long 
                                int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!x || !ycolptr || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc: NULL argument");
-    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc: empty x or y");
-    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, q, ycolptr, yrowidx, yx); }, x, n, p, q, alpha, mask, beta0,
-                       max_iter, rel_tol, method, coefficient, n_iteration, cb);
+    return c_nnlm_body("nnlm_c_nnlm_csc", ycolptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, q, ycolptr, yrowidx, yx); }, x, n, p,
+                       q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
 }
 
 extern "C" int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
@@ -3943,9 +3942,7 @@ extern "C" int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, con
                                        int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
 {
     (void)n_threads;
-    if (!x || !ycolptr || !alpha || !coefficient || !n_iteration) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc_missing: NULL argument");
-    if (n < 1 || p < 1 || q < 1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnlm_csc_missing: empty x or y");
-    return c_nnlm_body([&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, q, ycolptr, yrowidx, yx); }, x, n, p, q, alpha, mask,
-                       beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
+    return c_nnlm_body("nnlm_c_nnlm_csc_missing", ycolptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, q, ycolptr, yrowidx, yx); },
+                       x, n, p, q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
 }
 #undef CHK

@@ -45,6 +45,7 @@ def test_check_interrupt_aborts_at_the_iteration_and_leaves_the_handle_consisten
         with pytest.raises(_lib.NnlmError) as ei:
             h.run(z, z, 10, -1.0, 0, False, 5, 1e-9, 1, 1, callbacks=cb)
         assert ei.value.code == 3 and len(calls) == stop_at + 1
+        assert _lib.load().nnlm_last_error(h._h) == b"interrupted"
         Wi, Hi = h.get_factors()
         sweeps_i = h.take_sweeps(reset=False)
         # continue for the remaining iterations on the same handle
@@ -64,16 +65,25 @@ def test_check_interrupt_aborts_at_the_iteration_and_leaves_the_handle_consisten
     assert sweeps_i <= (80 + 60) * 5  # at most the open trace window's sweeps; never the dropped half-step's
 
 
-def test_progress_callback_counts_every_iteration(monkeypatch):
-    """verbose == 1: RcppProgress is incremented once per outer iteration (src/nnmf.cpp:60,112)."""
+@pytest.mark.parametrize("loop", ["solo", "batch"])
+def test_progress_callback_counts_every_iteration(monkeypatch, loop):
+    """verbose == 1: RcppProgress is incremented once per outer iteration (src/nnmf.cpp:60,112) -- once per iteration of the
+    batch, not per member."""
     monkeypatch.setenv("NNLM_PRECISION", "f64")
     A, W0, H0 = _problem()
     seen = []
     cb = _lib.make_callbacks(progress=lambda d, t: seen.append((d, t)))
-    r = nnlm_amd.c_nnmf(A, 4, W0, H0, None, None, [0, 0, 0], [0, 0, 0], 7, -1.0, 1, 1, False, 5, 1e-9, 1, 2, callbacks=cb)
-    assert r["n_iteration"] == 7 and seen == [(i + 1, 7) for i in range(7)]
+
+    def run(verbose):
+        z = [0, 0, 0]
+        if loop == "solo":
+            return [nnlm_amd.c_nnmf(A, 4, W0, H0, None, None, z, z, 7, -1.0, 1, verbose, False, 5, 1e-9, 1, 2, callbacks=cb)]
+        return nnlm_amd.c_nnmf_batch(A, [2, 4], None, None, z, z, 7, -1.0, 1, verbose, False, 5, 1e-9, 1, 2, callbacks=cb)
+
+    assert [r["n_iteration"] for r in run(1)] == ([7] if loop == "solo" else [7, 7]) and seen == [(i + 1, 7) for i in range(7)]
     seen.clear()
-    nnlm_amd.c_nnmf(A, 4, W0, H0, None, None, [0, 0, 0], [0, 0, 0], 7, -1.0, 1, 0, False, 5, 1e-9, 1, 2, callbacks=cb)
+    run(0)
+    run(2)
     assert seen == []  # verbose 0 and 2 do not drive the bar
 
 
@@ -107,6 +117,67 @@ def test_verbose2_table_text(monkeypatch, method, trace):
         assert cells[1] == ("%10.4f" % mse).strip() and cells[2] == ("%10.4f" % mkl).strip() and cells[3] == ("%10.4f" % terr).strip()
         assert abs(float(cells[4]) - rel) <= 0.35 * abs(rel)  # "%10.g": one significant digit
         assert len(row) == 5 * 10 + 4 * 3
+
+
+@pytest.mark.parametrize("prec", [_lib.PREC_F64, _lib.PREC_F32])
+@pytest.mark.parametrize("stop_at", [0, 1, 3])
+def test_check_interrupt_of_the_batch_loop(prec, stop_at):
+    """The batched loop polls like the solo one: an interrupt at the top of iteration i returns NNLM_ERR_INTERRUPT with exactly i
+    iterations applied to every member, and the handle's last error names it."""
+    A, W0, H0 = _problem()
+    z, ks = [0.0, 0.0, 0.0], [2, 4]
+    Ws, Hs = [W0[:, :k] for k in ks], [H0[:k] for k in ks]
+    calls = []
+
+    def intr():
+        calls.append(len(calls))
+        return len(calls) - 1 == stop_at
+
+    with nnlm_amd.Handle(0, prec) as h:
+        h.set_matrix(A)
+        h.set_factors_batch(ks, Ws, Hs)
+        with pytest.raises(_lib.NnlmError) as ei:
+            h.run_batch(z, z, 10, -1.0, 0, False, 5, 1e-9, 1, 2, callbacks=_lib.make_callbacks(check_interrupt=intr))
+        assert ei.value.code == 3 and len(calls) == stop_at + 1
+        assert _lib.load().nnlm_last_error(h._h) == b"interrupted"
+        got = h.get_factors_batch()
+    with nnlm_amd.Handle(0, prec) as h:
+        h.set_matrix(A)
+        h.set_factors_batch(ks, Ws, Hs)
+        if stop_at:
+            h.run_batch(z, z, stop_at, -1.0, 0, False, 5, 1e-9, 1, 2)
+        want = h.get_factors_batch()
+    tol = 1e-12 if prec == _lib.PREC_F64 else 1e-6
+    for (Wg, Hg), (Ww, Hw) in zip(got, want):
+        assert relF(Wg, Ww) < tol and relF(Hg, Hw) < tol
+
+
+@pytest.mark.parametrize("max_iter,rel_tol,trace", [(6, -1.0, 2), (40, 1e-3, 1)])
+def test_verbose2_table_text_of_the_batch(monkeypatch, max_iter, rel_tol, trace):
+    """verbose == 2 of the batched loop: the member column in front of the solo table's header and rule, then one row per booked
+    trace entry -- the solo row behind its member's number, in the order the entries are booked (by iteration, then member) and
+    holding exactly that member's trace -- and no footer."""
+    monkeypatch.setenv("NNLM_PRECISION", "f64")
+    A, W0, H0 = _problem()
+    ks = [1, 4]
+    out = []
+    res = nnlm_amd.c_nnmf_batch(A, ks, [W0[:, :k] for k in ks], [H0[:k] for k in ks], [0.01, 0, 0], [0, 0, 0.01], max_iter, rel_tol, 1,
+                                2, False, 5, 1e-9, 1, trace, callbacks=_lib.make_callbacks(print_fn=out.append))
+    head = "\n%6s %10s | %10s | %10s | %10s | %10s\n" % ("Member", "Iteration", "MSE", "MKL", "Target", "Rel. Err.")
+    rule = "---------------------------------------------------------------------\n"
+    rows = []
+    for b, r in enumerate(res):
+        nit = r["n_iteration"]
+        its = [i + 1 for i in range(nit) if i % trace == 0]
+        if nit == max_iter and (max_iter - 1) % trace != 0:
+            its.append(max_iter + 1)  # the closing entry prints i+1 with i == max_iter (src/nnmf.cpp:188-189)
+        assert len(its) == len(r["mse_error"])
+        last = 1e99
+        for it, mse, mkl, terr in zip(its, r["mse_error"], r["mkl_error"], r["target_error"]):
+            rel = 2 * (last - terr) / (last + terr + 1e-16)
+            last = terr
+            rows.append((it, b, "%6d %10d | %10.4f | %10.4f | %10.4f | %10.g\n" % (b, it, mse, mkl, terr, rel)))
+    assert "".join(out) == head + rule + "".join(row for _, _, row in sorted(rows))
 
 
 def test_warning_callback_and_flag(monkeypatch):
