@@ -158,6 +158,7 @@ struct nnlm_handle {
     double *spg_buf = nullptr;
     size_t spg_buf_bytes = 0;
     int spg_chunks = 0; // chunks of the last such half-step (nnlm_get_info "sp_gram_chunks")
+    int spg_workers = 0; // sp_gram_kernel workers of that half-step, summed over its chunks (nnlm_get_info "sp_gram_workers")
     unsigned long long *sweeps = nullptr; // [2] device counters; sw_active = the one the current trace window sums into
     int sw_active = 0;
     double *host_res = nullptr;           // pinned: 8 reduction results + sweep counter of the asynchronous error block
@@ -2380,6 +2381,7 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
     const size_t slot = (size_t)KP * KP;
     int rc = spg_prepare(h, o, slot);
     if (rc != NNLM_OK) return rc;
+    int workers = 0;
     SweepArgs a = sweep_args(h, s, reg, inner_max_iter, inner_rel_tol, sweep_counter(h, speculative));
     SpGramArgs g;
     g.ptr = s.sp_ptr;
@@ -2396,6 +2398,7 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
             g.seg = h->spg_buf + (size_t)(ch.c1 - ch.c0) * slot;
             const long long nnz = hp[ch.c1] - hp[ch.c0];
             g.nworkers = nnlm_spg_workers(nnz, h->cus_device);
+            workers += g.nworkers;
             g.chunk = (nnz + g.nworkers - 1) / g.nworkers;
             if (g.chunk < 1) g.chunk = 1;
             nnlm_tu_sp_gram(g, h->NKQ, h->prec == NNLM_PREC_F64, h->stream);
@@ -2409,6 +2412,7 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
         launch_colsolve(h, method, a, slot);
     }
     h->spg_chunks = (int)h->spg_plan[o].size();
+    h->spg_workers = workers;
     LAUNCHCHK(h);
     if (s.which == 0 && !speculative) swap_w(h);
     return NNLM_OK;
@@ -3169,6 +3173,8 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
     else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
+    else if (strcmp(key, "sp_workers") == 0) *value = (h->sparse && h->KP > 0) ? nnlm_sp_workers(h->nnz, h->KP, h->cus_device) : 0;
+    else if (strcmp(key, "sp_gram_workers") == 0) *value = h->spg_workers;
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
 }

@@ -1,11 +1,33 @@
 """Diagnosis aid for tests/test_gpu_fuzz.py (run on the GPU box: python tests/fuzz_table.py): one line per failing or degenerate case of the
-first NNLM_FUZZ_SEEDS (default 150) seeds of both modes -- deviations of W and H, iteration and sweep counts, the case's parameters."""
+first NNLM_FUZZ_SEEDS (default 150) seeds of both modes -- deviations of W and H, iteration and sweep counts, the case's parameters.
+--sparse: the same for the whole-run cases of tests/test_gpu_fuzz_sparse.py (sparse_cases.make_case under both semantics)."""
 import os, sys
 import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE); sys.path.insert(0, os.path.dirname(HERE))
 import test_gpu_fuzz as F
 from helpers import relF
+if "--sparse" in sys.argv:
+    import sparse_cases as sc
+    import test_gpu_fuzz_sparse as S
+    from oracle import ref
+    for mode in ("f64", "f32"):
+        os.environ["NNLM_PRECISION"] = mode
+        tol = 1e-9 if mode == "f64" else 1e-4
+        for semantics in sc.SEMANTICS:
+            for seed in range(int(os.environ.get("NNLM_FUZZ_SEEDS", "150"))):
+                c = sc.make_case(seed, semantics)
+                try:
+                    r, o = S.run_both(c)
+                except Exception as e:
+                    print(mode, semantics, seed, "EXC", repr(e)[:200], sc.describe(c)); continue
+                ew, eh = relF(r["W"], o["W"]), relF(r["H"], o["H"])
+                ep = np.array_equal(r["average_epoch"], o["average_epoch"]) if r["average_epoch"].shape == o["average_epoch"].shape else "shape"
+                deg = sc.degenerate(c, ref)
+                if deg or not (ew < tol and eh < tol) or r["n_iteration"] != o["n_iteration"] or (mode == "f64" and ep is not True):
+                    print(mode, semantics, seed, "DEG" if deg else "   ", "LOOSE" if sc.rank_deficient(c) else "     ",
+                          f"W {ew:.2e} H {eh:.2e} nit {r['n_iteration']}/{o['n_iteration']} ep_eq {ep}", sc.describe(c), flush=True)
+    sys.exit(0)
 HARD = os.environ.get("NNLM_FUZZ_F32_HARD", "0") == "1"  # F32 mode on the strict mode's cases too (ranks up to the smaller dimension, up to 90 % missing)
 for mode, wc in (("f64", False), ("f32", not HARD)):
     os.environ["NNLM_PRECISION"] = mode
