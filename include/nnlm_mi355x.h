@@ -172,6 +172,20 @@ int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, c
  * and 2, both modes, ranks 1..64, masks and known profiles.  NNLM_ERR_UNSUPPORTED: methods 3 and 4, rank > 64 (nnlm_set_factors),
  * nnlm_comm_init, nnlm_debug_partial and the batch entries. */
 int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* Dense finite A (fp64, column-major) with a HOLD-OUT set: colptr[m + 1] / rowidx[] is a canonical CSC pattern (the validation of
+ * nnlm_set_matrix_csc; an empty pattern is legal) of the entries kept out of the fit.  The handle is then in the state nnlm_set_matrix
+ * leaves for A with NA at the pattern -- missing bits, 0 in every resident copy, n_non_missing / any_missing / kl_const over the
+ * training entries -- and keeps the held-out entries on the device as a CSC of their own (values in the mode's type, int32 indices,
+ * int64 pointers: O(held-out entries)).  The pattern is applied chunk by chunk in the upload's host staging buffer: A is not
+ * written and no second n x m array is made.  NNLM_ERR_ARG: a non-finite entry of A (named in the message), a non-canonical pattern,
+ * a pattern that holds out every entry.  nnlm_half_step, nnlm_iterate, nnlm_run and nnlm_errors behave as on the NA matrix (all four
+ * methods); nnlm_set_factors_batch / nnlm_run_batch accept such a handle (below); nnlm_comm_init returns NNLM_ERR_UNSUPPORTED.
+ * nnlm_get_info "matrix_holdout": the held-out count, -1 on any other handle. */
+int nnlm_set_matrix_holdout(nnlm_handle *h, const double *A, int n, int m, const long long *colptr, const int *rowidx);
+/* Errors of the current factors on the held-out entries: mse[b] = mean (a - wh)^2, mkl[b] = mean (a + eps) log((a + eps) / (wh + eps))
+ * - a + wh, for the B members of a batch (arrays of length B) or the solo factors (length 1).  fp64 sums in a fixed order, no
+ * atomics; synchronises.  An empty hold-out set gives NaN for both; NNLM_ERR_ARG on a handle without a hold-out set. */
+int nnlm_holdout_errors(nnlm_handle *h, double *mse, double *mkl);
 /* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag.  Sparse A: n m and 0, and kl_const counts
  * the zeros ((n m - nnz) eps log eps); absent entries missing (nnlm_set_matrix_csc_missing): nnz and (nnz < n m). */
 int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const);
@@ -211,6 +225,9 @@ int nnlm_sync(nnlm_handle *h);
  * k[b] <= 64, methods 1 and 2 (square loss), dense A without missing entries, one GPU, no masks: anything else is refused with
  * NNLM_ERR_UNSUPPORTED (KL loss, missing entries, a sparse A, a communicator, a rank sum beyond 64) or NNLM_ERR_ARG (B or a rank out
  * of range).  Each member's factors, traces, n_iteration and warning are those nnlm_run gives for that member alone (same mode).
+ * Missing entries are accepted in ONE form: a hold-out handle (nnlm_set_matrix_holdout).  Every member then solves each column with the
+ * Gram over that column's observed rows, as a solo missing-value run does, behind the same single cross product; the traces' sums
+ * run over the training entries.  A matrix that arrived with NA / NaN / Inf through nnlm_set_matrix stays refused.
  * ---------------------------------------------------------------------------------------- */
 /* k[B] ranks; W = the members' n x k[b] blocks one after another (column-major each), H = their k[b] x m blocks one after another;
  * NULL = zeros.  Replaces the handle's factors (nnlm_set_factors ends a batch). */
@@ -232,6 +249,15 @@ int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, const unsigned 
                       int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out,
                       double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
                       unsigned *n_iteration, int *warned, const nnlm_callbacks *cb);
+
+/* nnlm_c_nnmf_batch on A with the pattern (colptr, rowidx) held out (nnlm_set_matrix_holdout), + holdout_mse[B], holdout_mkl[B]:
+ * nnlm_holdout_errors of the final factors. */
+int nnlm_c_nnmf_holdout_batch(const double *A, int n, int m, const long long *colptr, const int *rowidx, unsigned B, const unsigned *k,
+                              const double *W_init, const double *H_init, const double alpha[3], const double beta[3], unsigned max_iter,
+                              double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                              int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                              double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                              double *holdout_mse, double *holdout_mkl, const nnlm_callbacks *cb);
 
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",

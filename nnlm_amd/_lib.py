@@ -36,6 +36,7 @@ EXPORTS = [
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
+    "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
 ]
 
 
@@ -157,6 +158,13 @@ def load():
     lib.nnlm_c_nnmf_batch.restype = C.c_int
     lib.nnlm_c_nnmf_batch.argtypes = [dp, C.c_int, C.c_int, C.c_uint, up, dp, dp, dp, dp, C.c_uint, C.c_double, C.c_int, C.c_int, C.c_int,
                                       C.c_uint, C.c_double, C.c_int, C.c_uint, dp, dp, dp, dp, dp, dp, ip, up, ip, C.POINTER(Callbacks)]
+    lib.nnlm_set_matrix_holdout.restype = C.c_int
+    lib.nnlm_set_matrix_holdout.argtypes = [vp, dp, C.c_int, C.c_int, lp, ip]
+    lib.nnlm_holdout_errors.restype = C.c_int
+    lib.nnlm_holdout_errors.argtypes = [vp, dp, dp]
+    lib.nnlm_c_nnmf_holdout_batch.restype = C.c_int
+    lib.nnlm_c_nnmf_holdout_batch.argtypes = (lib.nnlm_c_nnmf_batch.argtypes[:3] + [lp, ip] + lib.nnlm_c_nnmf_batch.argtypes[3:-1]
+                                              + [dp, dp, C.POINTER(Callbacks)])
     _lib = lib
     return lib
 
@@ -310,8 +318,22 @@ def _batch_traces(ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned):
     return out
 
 
+def _pattern_arrays(indptr, indices):
+    """A hold-out pattern in the types of the C ABI (int64 pointers, int32 row indices); the library validates it."""
+    return np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32)
+
+
+def c_nnmf_holdout_batch(A, indptr, indices, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter,
+                         inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_batch on A with the CSC pattern (indptr[m + 1], indices) held out (nnlm_c_nnmf_holdout_batch): each member's dict also
+    carries holdout_mse and holdout_mkl, the errors of its final factors on the held-out entries."""
+    ptr, idx = _pattern_arrays(indptr, indices)
+    return c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol,
+                        method, trace, callbacks, _holdout=(ptr, idx))
+
+
 def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
-                 trace, callbacks=None):
+                 trace, callbacks=None, _holdout=None):
     """Batched c_nnmf (nnlm_c_nnmf_batch): member b has rank ks[b] and starts from W[b] (n x k_b), H[b] (k_b x m) -- either list may
     be None for the library's default init.  Returns one c_nnmf-style dict per member."""
     lib = load()
@@ -327,14 +349,23 @@ def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose
     mse, mkl, terr, ep = (np.zeros(B * cap) for _ in range(4))
     n_trace, warned = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
     n_it = np.zeros(B, dtype=np.uint32)
-    rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, B, ks.ctypes.data_as(C.POINTER(C.c_uint)), _dp(Wc), _dp(Hc), _dp(al), _dp(be), int(max_iter),
-                               float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter), float(inner_rel_tol),
-                               int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace),
-                               n_it.ctypes.data_as(C.POINTER(C.c_uint)), _ip(warned), C.byref(callbacks) if callbacks is not None else None)
+    args = [B, ks.ctypes.data_as(C.POINTER(C.c_uint)), _dp(Wc), _dp(Hc), _dp(al), _dp(be), int(max_iter),
+            float(rel_tol), int(n_threads), int(verbose), int(bool(show_warning)), int(inner_max_iter), float(inner_rel_tol),
+            int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace),
+            n_it.ctypes.data_as(C.POINTER(C.c_uint)), _ip(warned)]
+    cbp = C.byref(callbacks) if callbacks is not None else None
+    if _holdout is None:
+        rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, *args, cbp)
+    else:
+        hmse, hmkl = np.zeros(B), np.zeros(B)
+        rc = lib.nnlm_c_nnmf_holdout_batch(_dp(A), n, m, _lp(_holdout[0]), _ip(_holdout[1]), *args, _dp(hmse), _dp(hmkl), cbp)
     _check(rc)
     out = _batch_traces(ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned)
     for o, Wb, Hb in zip(out, *_batch_split(Wo, Ho, ks, n, m)):
         o["W"], o["H"] = Wb, Hb
+    if _holdout is not None:
+        for b, o in enumerate(out):
+            o["holdout_mse"], o["holdout_mkl"] = float(hmse[b]), float(hmkl[b])
     return out
 
 
@@ -457,6 +488,26 @@ class Handle:
         self._ck(self._lib.nnlm_set_matrix_csc_missing(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
         self.n, self.m = n, m
 
+    def set_matrix_holdout(self, A, indptr, indices):
+        """Dense finite A with the CSC pattern (indptr[m + 1], indices) held out: the handle of set_matrix(A with NaN at the pattern) that
+        also keeps the held-out entries (holdout_errors) and is accepted by the batch entries."""
+        A = _f64(A)
+        ptr, idx = _pattern_arrays(indptr, indices)
+        n, m = A.shape
+        if ptr.size != m + 1:
+            raise NnlmError(ERR_ARG, f"the hold-out pattern has {ptr.size} column pointers, A has {m} columns")
+        if idx.size < (int(ptr[-1]) if ptr.size else 0):
+            raise NnlmError(ERR_ARG, "the hold-out pattern has fewer row indices than its last column pointer")
+        self._ck(self._lib.nnlm_set_matrix_holdout(self._h, _dp(A), n, m, _lp(ptr), _ip(idx)))
+        self.n, self.m = n, m
+
+    def holdout_errors(self):
+        """(mse, mkl) arrays over the held-out entries: one value per batch member, or one for solo factors."""
+        B = len(self.ks) if getattr(self, "_batch", False) else 1
+        mse, mkl = np.zeros(B), np.zeros(B)
+        self._ck(self._lib.nnlm_holdout_errors(self._h, _dp(mse), _dp(mkl)))
+        return mse, mkl
+
     def matrix_info(self):
         nn, am, kc = C.c_double(0), C.c_int(0), C.c_double(0)
         self._ck(self._lib.nnlm_matrix_info(self._h, C.byref(nn), C.byref(am), C.byref(kc)))
@@ -464,6 +515,7 @@ class Handle:
 
     def set_factors(self, k, W=None, H=None, Wm=None, Hm=None):
         self.k = int(k)
+        self._batch = False  # (a solo set ends a batch)
         Wi = _f64(W, (self.n, self.k)) if W is not None else None
         Hi = _f64(H, (self.k, self.m)) if H is not None else None
         self._ck(self._lib.nnlm_set_factors(self._h, self.k, _dp(Wi), _dp(Hi), _ip(_lgl(Wm, (self.n, self.k))),
@@ -504,7 +556,7 @@ class Handle:
         Wc = _batch_blocks(W, [(self.n, int(k)) for k in ks], "W")
         Hc = _batch_blocks(H, [(int(k), self.m) for k in ks], "H")
         self._ck(self._lib.nnlm_set_factors_batch(self._h, len(ks), ks.ctypes.data_as(C.POINTER(C.c_uint)), _dp(Wc), _dp(Hc)))
-        self.k, self.ks = int(ks.sum()), [int(k) for k in ks]
+        self.k, self.ks, self._batch = int(ks.sum()), [int(k) for k in ks], True
 
     def get_factors_batch(self):
         """[(W_b, H_b)] of the members."""

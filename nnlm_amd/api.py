@@ -15,6 +15,7 @@ pure host logic and are split out so they can be unit-tested without a GPU.
 """
 from __future__ import annotations
 
+import os
 import time
 import warnings
 from collections import namedtuple
@@ -462,6 +463,131 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
     res = [finish_nnmf(o, p[1], run_time=run_time) for o, p in zip(outs, prep)]
     best = int(np.argmin([r["target_loss"][-1] if len(r["target_loss"]) else np.inf for r in res]))
     return res, best
+
+
+def _pack_batches(ks, cap=None):
+    """nnmf_cv's batches: the members in order, a new batch whenever the next rank would take the rank sum beyond `cap` (64) ->
+    [(first, last + 1)].  A single rank beyond the cap fits no batch (NNLM_ERR_UNSUPPORTED)."""
+    cap = _lib.BATCH_MAX if cap is None else cap
+    out, start, tot = [], 0, 0
+    for b, kb in enumerate(ks):
+        if kb > cap:
+            raise _lib.NnlmError(_lib.ERR_UNSUPPORTED, "nnmf_cv: rank %d exceeds %d, the largest rank sum of a batch" % (kb, cap))
+        if tot + kb > cap:
+            out.append((start, b))
+            start, tot = b, 0
+        tot += kb
+    out.append((start, len(ks)))
+    return out
+
+
+def _holdout_pattern(holdout, n, m, rng):
+    """nnmf_cv's hold-out set as a canonical CSC pattern (indptr int64 [m + 1], row indices int32).  A fraction in (0, 1): round(f n m)
+    entries drawn uniformly without replacement from `rng`; a boolean n x m array: its True entries; a {"indptr", "indices"} dict (what
+    nnmf_cv returned): that pattern again."""
+    if isinstance(holdout, dict):
+        ptr, idx = np.asarray(holdout["indptr"], dtype=np.int64), np.asarray(holdout["indices"], dtype=np.int32)
+        if ptr.shape != (m + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != idx.size:
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: the hold-out pattern needs indptr of length ncol + 1, non-decreasing from 0 to len(indices)")
+        return ptr, idx
+    if np.ndim(holdout) == 0:
+        f = float(holdout)
+        if not 0.0 < f < 1.0:
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: holdout must be a fraction in (0, 1) or a boolean %d x %d array (got %r)" % (n, m, holdout))
+        flat = np.sort(rng.choice(n * m, size=int(round(f * n * m)), replace=False))  # column-major position j n + i
+        cols, rows = flat // n, flat % n
+    else:
+        mask = np.asarray(holdout)
+        if mask.dtype != np.bool_ or mask.shape != (n, m):
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: holdout must be a fraction in (0, 1) or a boolean %d x %d array" % (n, m))
+        cols, rows = np.nonzero(mask.T)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(cols, minlength=m))]).astype(np.int64)
+    return ptr, rows.astype(np.int32)
+
+
+def _env_precision():
+    """The precision rule of the one-shot entries: NNLM_PRECISION = f32 selects the fp32-operand mode, anything else strict fp64."""
+    return _lib.PREC_F32 if os.environ.get("NNLM_PRECISION") in ("f32", "fp32", "0") else _lib.PREC_F64
+
+
+def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
+    """Rank selection on held-out entries (the reference's vignette method): a share of the entries of the dense matrix A is kept out
+    of the fit, every member (``k`` and ``nrun`` as in nnmf_batch) is fitted on the rest by the batched factorisation, and the member
+    whose reconstruction of the held-out entries has the lowest mean squared error is ``best``.
+
+    ``holdout``: a fraction in (0, 1), drawn uniformly without replacement from ``rng`` BEFORE any member's init is drawn; or a boolean
+    n x m array (True = held out); or the ``holdout`` entry of an earlier result.  With check_k (the default) and no penalties, a
+    hold-out set that leaves a row or a column fewer than max(k) + 1 training entries is rejected (NnlmStop, the check_k wording).
+    Members whose ranks sum to more than 64 run as successive batches, in order, on one handle: A is uploaded once.
+    Refused as by nnmf_batch (NnlmError, NNLM_ERR_UNSUPPORTED): loss = 'mkl', masks, known profiles, a sparse A, an A with non-finite
+    entries; a single rank above 64.  The arithmetic mode is NNLM_PRECISION's, as for nnmf().
+
+    Returns a dict: fits (nnmf results with holdout_mse / holdout_mkl added), k (rank per member), holdout_mse, holdout_mkl (arrays),
+    best (index of the lowest holdout_mse, the first on ties), holdout ({"indptr", "indices", "shape"}: the pattern used)."""
+    ks = _batch_rank_list(k, nrun)
+    B = len(ks)
+    if init is not None:
+        if isinstance(init, dict) or len(init) != B:
+            raise _lib.NnlmError(_lib.ERR_ARG, "init must be a list of %d dicts {'W': ..., 'H': ...}, one per member" % B)
+        init = [dict(x) if x is not None else {} for x in init]
+    unsupported = lambda msg: _lib.NnlmError(_lib.ERR_UNSUPPORTED, "nnmf_cv: " + msg)
+    if not _is_empty(nnmf_options.get("mask")) and any(not _is_empty(v) for v in dict(nnmf_options["mask"]).values()):
+        raise unsupported("masks are not supported by the batched factorisation")
+    if init is not None and any(x.get("W0") is not None or x.get("H0") is not None for x in init):
+        raise unsupported("known profiles (W0 / H0) are not supported by the batched factorisation")
+    if _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss") != "mse":
+        raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
+    if is_sparse(A):
+        raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    batches = _pack_batches(ks)
+    mat = _nnmf_matrix(A, "mse")
+    if not np.isfinite(mat["A"]).all():
+        raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation takes missing entries through the "
+                          "hold-out set only")
+    n, m = mat["n"], mat["m"]
+    if init is not None:
+        for b, x in enumerate(init):
+            for key, shp in (("W", (n, ks[b])), ("H", (ks[b], m))):
+                if x.get(key) is not None and np.shape(x[key]) != shp:
+                    raise _lib.NnlmError(_lib.ERR_ARG, "init[%d]['%s'] has shape %s, member %d (rank %d) needs %s"
+                                         % (b, key, np.shape(x[key]), b, ks[b], shp))
+    g = rng or np.random.default_rng()
+    ptr, idx = _holdout_pattern(holdout, n, m, g)
+    # check.k (R/nnmf.R:157-164) on the training entries: k + 1 of them in every row and column
+    row_obs = m - np.bincount(idx, minlength=n)
+    col_obs = n - np.diff(ptr)
+    mat = dict(mat, min_k=min(mat["min_k"], int(row_obs.min()) - 1, int(col_obs.min()) - 1))
+    opts = dict(nnmf_options)
+    opts.setdefault("verbose", 0)
+    prep, Ws, Hs = [], [], []
+    _prepare_nnmf(A, max(ks), rng=np.random.default_rng(0), matrix=mat, **opts)  # (the check_k rule at the largest rank, before any init is drawn from g)
+    for b in range(B):  # member after member, each consuming the generator as nnmf() would
+        args, ctx, _ = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
+        W, H = args[2], args[3]
+        Ws.append(W if np.size(W) else 0.01 * g.random(n * ks[b]).reshape((n, ks[b])))
+        Hs.append(H if np.size(H) else 0.01 * g.random(ks[b] * m).reshape((ks[b], m), order="F"))
+        prep.append((args, ctx))
+    a0 = prep[0][0]
+    cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
+    fits, hmse, hmkl = [], np.zeros(B), np.zeros(B)
+    with _lib.Handle(int(os.environ.get("NNLM_DEVICE", "0") or 0), _env_precision()) as h:
+        h.set_matrix_holdout(mat["A"], ptr, idx)
+        for b0, b1 in batches:
+            t0 = time.perf_counter()
+            h.set_factors_batch(ks[b0:b1], Ws[b0:b1], Hs[b0:b1])
+            # (alpha, beta, max_iter, rel_tol | verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace: n_threads has no place)
+            outs = h.run_batch(*a0[6:10], *a0[11:], callbacks=cb)
+            facs = h.get_factors_batch()
+            hmse[b0:b1], hmkl[b0:b1] = h.holdout_errors()
+            run_time = time.perf_counter() - t0
+            for b, o, (W, H) in zip(range(b0, b1), outs, facs):
+                o["W"], o["H"] = W, H
+                r = finish_nnmf(o, prep[b][1], run_time=run_time)
+                r["holdout_mse"], r["holdout_mkl"] = float(hmse[b]), float(hmkl[b])
+                fits.append(r)
+    best = int(np.argmin(np.where(np.isnan(hmse), np.inf, hmse)))
+    return dict(fits=fits, k=list(ks), holdout_mse=hmse, holdout_mkl=hmkl, best=best,
+                holdout=dict(indptr=ptr, indices=idx, shape=(n, m)))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -10,16 +10,26 @@
 // partial[(2 b + t) nblk + blk] and batch_reduce_kernel adds the blocks in order.
 // Bound: n m sizeof(T) bytes of A once, but B x (the MFMA steps of the member's segment + ~30 VALU slots) per entry: issue bound
 // beyond a few members.
+// NA = true (a hold-out handle): entries whose bit is set in miss [mpad][words] (bit i % 32 of word [j][i / 32]) are
+// left out of both sums -- 16 word reads per lane and j-tile beside the 16 entries of A (the 16 lanes of a row group read the same
+// word), kept as a 16-bit lane mask; the member loop is unchanged.
+//
+// holdout_errors_kernel: the two sums of every member over the HELD-OUT entries, a CSC of its own (row, column and value per entry).
+// Block (x, b): member b over the entries [x chunk, (x + 1) chunk), a lane takes every 256th of them: wh = the dot over the member's k_b
+// coordinates of row i of W and row j of H (row copies [n][K], [m][K]: two contiguous reads of k_b doubles), one logarithm, fp64
+// throughout.  Lane sums, wave_sum, the four wavefronts in order, then batch_reduce_kernel over the blocks: a fixed order, no atomics.
+// Bound: latency of the two gathered rows per entry (2 k_b 8 bytes); nothing n x m sized is touched.
 #pragma once
 #include "common.h"
 #include "k_errors.h"
 
 #define BATCH_MAX 64
 
-template <typename T>
+template <typename T, bool NA = false>
 __global__ __launch_bounds__(256) void errors_batch_kernel(const T *__restrict__ A, int lda, const double *__restrict__ W64, int ldw,
                                                            const double *__restrict__ H64, int ldh, int n, int m, const int *__restrict__ off,
-                                                           int B, unsigned long long amask, double *__restrict__ partial, int nblk)
+                                                           int B, unsigned long long amask, double *__restrict__ partial, int nblk,
+                                                           const uint32_t *__restrict__ miss = nullptr, int words = 0)
 {
     using M = Mfma<double>;
     __shared__ double red[BATCH_MAX][4][2];
@@ -43,6 +53,20 @@ __global__ __launch_bounds__(256) void errors_batch_kernel(const T *__restrict__
             for (int b = 0; b < 2; b++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) av[a][b][r] = (double)A[(size_t)(jb + 16 * b + M::row_of(lane, r)) * lda + ib + 16 * a + l15];
+        unsigned obs = 0xFFFFu; // NA: bit 8 a + 4 b + r = the lane's entry (a, b, r) is observed
+        if constexpr (NA) {
+            obs = 0u;
+#pragma unroll
+            for (int a = 0; a < 2; a++)
+#pragma unroll
+                for (int b = 0; b < 2; b++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int i = ib + 16 * a + l15, j = jb + 16 * b + M::row_of(lane, r);
+                        const uint32_t w = miss[(size_t)j * words + (i >> 5)];
+                        obs |= (((w >> (i & 31)) & 1u) ^ 1u) << (8 * a + 4 * b + r);
+                    }
+        }
         for (int mb = 0; mb < B; mb++) {
             if (!((amask >> mb) & 1ull)) continue; // (uniform: frozen members are not summed)
             const int q0 = off[mb], q1 = off[mb + 1];
@@ -77,7 +101,8 @@ __global__ __launch_bounds__(256) void errors_batch_kernel(const T *__restrict__
                     for (int r = 0; r < 4; r++) {
                         const int j = jb + 16 * b + M::row_of(lane, r);
                         const double ah = acc[a][b][r], x = av[a][b][r];
-                        const bool valid = (i < n) && (j < m);
+                        bool valid = (i < n) && (j < m);
+                        if constexpr (NA) valid = valid && ((obs >> (8 * a + 4 * b + r)) & 1u);
                         const double d = x - ah;
                         // ln(wh + eps): strict mode the table logarithm of errors64_kernel (absolute error ~2e-16); fp32-operand mode the
                         // native fp32 one of its own error kernels (relative 1e-7 per term) -- the per-member logarithm is this kernel's
@@ -146,4 +171,37 @@ __global__ __launch_bounds__(256) void batch_reduce_kernel(const double *__restr
     if (lane == 0) red[wave] = s;
     __syncthreads();
     if (threadIdx.x == 0) out[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// Held-out sums of member blockIdx.y (see the head of this file).  off[b] .. off[b + 1] - 1: the member's coordinates in the row copies
+// Wrow [n][K], Hrow [m][K]; partial[(2 b + t) gridDim.x + blockIdx.x] = the block's {sum (a - wh)^2, sum (a + eps) ln((a + eps) / (wh + eps)) - a + wh}
+template <typename T>
+__global__ __launch_bounds__(256) void holdout_errors_kernel(const int *__restrict__ ridx, const int *__restrict__ cidx, const T *__restrict__ val,
+                                                             long long nnz, long long chunk, const double *__restrict__ Wrow,
+                                                             const double *__restrict__ Hrow, int K, const int *__restrict__ off,
+                                                             double *__restrict__ partial)
+{
+    __shared__ double red[2][4];
+    const int mb = blockIdx.y, q0 = off[mb], kb = off[mb + 1] - q0;
+    const long long e0 = (long long)blockIdx.x * chunk;
+    long long e1 = e0 + chunk;
+    if (e1 > nnz) e1 = nnz;
+    double s2 = 0.0, skl = 0.0;
+    for (long long e = e0 + threadIdx.x; e < e1; e += 256) {
+        const double *w = Wrow + (size_t)ridx[e] * K + q0, *x = Hrow + (size_t)cidx[e] * K + q0;
+        double wh = 0.0;
+        for (int q = 0; q < kb; q++) wh = __builtin_fma(w[q], x[q], wh);
+        const double a = (double)val[e], d = a - wh;
+        s2 += d * d;
+        skl += (a + NNLM_TINY) * log((a + NNLM_TINY) / (wh + NNLM_TINY)) - a + wh;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    s2 = wave_sum(s2);
+    skl = wave_sum(skl);
+    if (lane == 0) red[0][wave] = s2, red[1][wave] = skl;
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const int t = threadIdx.x;
+        partial[(size_t)(2 * mb + t) * gridDim.x + blockIdx.x] = ((red[t][0] + red[t][1]) + red[t][2]) + red[t][3];
+    }
 }

@@ -41,13 +41,14 @@ __global__ __launch_bounds__(256) void miss_transpose_kernel(const uint32_t *__r
 }
 
 // Yrow[c][q] = Y[q][c] for q < KP, so that a row of the fixed factor is one contiguous KP-element read (T = double, or
-// float for the fp32-operand mode's per-column Grams).
+// float for the fp32-operand mode's per-column Grams).  k: rows q >= k are written as zeros and not read (a member of a batched
+// factorisation: the rows behind its k_b are its neighbour's, and a solo factor has zeros there); the default reads all KP rows.
 template <typename T = double>
-__global__ __launch_bounds__(256) void factor_rows_kernel(const double *__restrict__ Y, int ld, int ncols, int KP, T *__restrict__ Yrow)
+__global__ __launch_bounds__(256) void factor_rows_kernel(const double *__restrict__ Y, int ld, int ncols, int KP, T *__restrict__ Yrow, int k = 1 << 30)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= ncols) return;
-    for (int q = 0; q < KP; q++) Yrow[(size_t)c * KP + q] = (T)Y[(size_t)q * ld + c];
+    for (int q = 0; q < KP; q++) Yrow[(size_t)c * KP + q] = q < k ? (T)Y[(size_t)q * ld + c] : (T)0;
 }
 
 // One wavefront per column, lane = coordinate (k <= 64).  a.Graw is either one shared Gram (g_stride = 0) or the

@@ -175,7 +175,7 @@ struct nnlm_handle {
     bool x16 = false;
     uint32_t *A16 = nullptr, *A16T = nullptr, *Y16 = nullptr;
     unsigned *maxbits = nullptr; // device [16]: bit patterns of max|factor|: [0] absmax_f64_kernel, [1],[2] alternately gram_partial_kernel, [3] block counter, [6],[7] shard_unpack_kernel (W, H),
-                                 // [4],[5] alternately the fast sweep kernel's own max of what it solved (k_sweep_q.h), [8] the same for a rank's
+                                 // [11] a batch member's own rows of the fixed factor (hold-out handle), [4],[5] alternately the fast sweep kernel's own max of what it solved (k_sweep_q.h), [8] the same for a rank's
                                  // column shard (travels behind its packed slab: gram_fold_tail_kernel clears it)
     // What the fast sweep leaves behind for the next half-step (dense one-GPU split-fp16 path): max|x| in maxbits[4 + sg_par] and
     // sg_nslabs Gram partial sums (one per workgroup) in sg_slabs.  sg_which: the factor they describe (1 = H, 0 = W, -1 = none).
@@ -210,6 +210,14 @@ struct nnlm_handle {
     double *bpart = nullptr;                // partial sums of the batched error block / penalties
     size_t bpart_elems = 0;
     double *bres = nullptr;                 // [8 bB]: {sum sq, sum KL} per member, then 3 W and 3 H penalty sums per member
+
+    // hold-out set (nnlm_set_matrix_holdout): the resident matrix is A with NA at the pattern (the dense NA layout
+    // above); the held-out entries themselves stay here as a CSC -- values in the mode's type, the column of every entry beside its row
+    bool holdout = false;
+    long long ho_nnz = 0;
+    long long *ho_cptr = nullptr; // [m + 1]
+    int *ho_ridx = nullptr, *ho_cidx = nullptr;
+    void *ho_val = nullptr;
 
     // profiling
     bool prof = false;
@@ -730,6 +738,15 @@ static void free_matrix(nnlm_handle *h)
     }
     h->sp_missing = false;
     h->nnz = 0;
+    hipFree(h->ho_cptr);
+    hipFree(h->ho_ridx);
+    hipFree(h->ho_cidx);
+    hipFree(h->ho_val);
+    h->ho_cptr = nullptr;
+    h->ho_ridx = h->ho_cidx = nullptr;
+    h->ho_val = nullptr;
+    h->ho_nnz = 0;
+    h->holdout = false;
     h->x16 = x16_enabled(h->prec); // (a sparse matrix turned it off)
     h->n = h->m = 0;
 }
@@ -787,10 +804,13 @@ extern "C" void nnlm_destroy(nnlm_handle *h)
 // ---------------------------------------------------------------------------------------------
 // matrix upload
 // ---------------------------------------------------------------------------------------------
-extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
+// nnlm_set_matrix and nnlm_set_matrix_holdout: one upload.  ho_colptr / ho_rowidx (validated by the caller, NULL for a plain upload):
+// the held-out pattern.  Every chunk of columns then passes through a host staging buffer in which A is checked to be finite and the
+// pattern's entries are replaced by NaN before the DMA -- prep_convert_kernel sees exactly what it sees for a matrix that arrived with
+// NaN there, so the resident state is that upload's bit for bit, and no second n x m array exists anywhere.  ho_val[e]: the values taken out.
+static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const long long *ho_colptr, const int *ho_rowidx, double *ho_val)
 {
-    if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_set_matrix: handle is NULL");
-    if (!A || n <= 0 || m <= 0) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix: A must be a non-empty n x m matrix (n=%d, m=%d)", n, m);
+    const bool ho = ho_colptr != nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     free_factors(h);
     free_matrix(h);
@@ -828,6 +848,15 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
     // (matrices of a few MB go through the runtime's pageable path: its own staging buffers are pinned already)
     bool bounce_cached = false;
     bool pinned = (size_t)n * m * 8 >= ((size_t)4 << 20) && bounce_acquire(chunk_bytes, bounce, &bounce_cached);
+    std::vector<double> hostbuf[2]; // hold-out upload without the pinned buffers: the chunk's host copy (the caller's A is not written)
+    if (ho && !pinned) {
+        try {
+            hostbuf[0].resize(chunk_bytes / 8);
+            hostbuf[1].resize(chunk_bytes / 8);
+        } catch (...) {
+            rc = fail(h, NNLM_ERR_HIP, "nnlm_set_matrix_holdout: host staging buffer (%zu bytes)", chunk_bytes);
+        }
+    }
     for (int b = 0; b < 2 && rc == NNLM_OK; b++) {
         if (hipMalloc(&stage[b], chunk_bytes) != hipSuccess) rc = fail(h, NNLM_ERR_HIP, "nnlm_set_matrix: staging buffer (%zu bytes)", chunk_bytes);
         else if (hipHostMalloc(&hp[b], 3 * prep_blocks * sizeof(double)) != hipSuccess || hipEventCreateWithFlags(&ev_done[b], hipEventDisableTiming) != hipSuccess)
@@ -884,6 +913,33 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
         if (pinned) {
             host_copy(bounce[slot], src, bytes);
             src = bounce[slot];
+        } else if (ho) {
+            memcpy(hostbuf[slot].data(), src, bytes);
+            src = hostbuf[slot].data();
+        }
+        if (ho) { // finite A, then NaN at the pattern (the slot's previous DMA has been waited for above)
+            double *buf = const_cast<double *>(src);
+            for (int c = 0; c < cols && rc == NNLM_OK; c++) {
+                double *col = buf + (size_t)c * n;
+                unsigned long long bad = 0;
+                for (int i = 0; i < n; i++) {
+                    unsigned long long u;
+                    memcpy(&u, col + i, 8);
+                    bad |= (unsigned long long)(((u >> 52) & 0x7FFull) == 0x7FFull);
+                }
+                if (bad) {
+                    int i = 0;
+                    while (std::isfinite(col[i])) i++;
+                    rc = fail(h, NNLM_ERR_ARG, "nnlm_set_matrix_holdout: A[%d, %d] is not finite; a hold-out handle needs a finite A (missing "
+                                               "entries enter through the pattern only)", i, j0 + c);
+                    break;
+                }
+                for (long long q = ho_colptr[j0 + c]; q < ho_colptr[j0 + c + 1]; q++) {
+                    ho_val[q] = col[ho_rowidx[q]];
+                    col[ho_rowidx[q]] = std::nan("");
+                }
+            }
+            if (rc != NNLM_OK) break;
         }
         hipError_t e = hipMemcpyAsync(stage[slot], src, bytes, hipMemcpyHostToDevice, h->stream);
         if (e != hipSuccess) { rc = fail(h, NNLM_ERR_HIP, "upload of A failed: %s", hipGetErrorString(e)); break; }
@@ -910,7 +966,10 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
         if (hp[b]) hipHostFree(hp[b]);
         if (ev_done[b]) hipEventDestroy(ev_done[b]);
     }
-    if (rc != NNLM_OK) return rc;
+    if (rc != NNLM_OK) {
+        if (ho) free_matrix(h);
+        return rc;
+    }
     if (over > 0.0) {
         free_matrix(h);
         return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f finite entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
@@ -952,6 +1011,66 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     return NNLM_OK;
+}
+
+extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
+{
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_set_matrix: handle is NULL");
+    if (!A || n <= 0 || m <= 0) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix: A must be a non-empty n x m matrix (n=%d, m=%d)", n, m);
+    return set_matrix_impl(h, A, n, m, nullptr, nullptr, nullptr);
+}
+
+// Dense finite A with a hold-out pattern (include/nnlm_mi355x.h)
+extern "C" int nnlm_set_matrix_holdout(nnlm_handle *h, const double *A, int n, int m, const long long *colptr, const int *rowidx)
+{
+    const char *who = "nnlm_set_matrix_holdout";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!A || n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix with a pattern colptr[m + 1] (n=%d, m=%d)", who, n, m);
+    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a hold-out handle is single-GPU only (this handle has a communicator)", who);
+    // the pattern: canonical CSC, as nnlm_set_matrix_csc checks it
+    if (colptr[0] != 0) return fail(h, NNLM_ERR_ARG, "%s: colptr[0] = %lld, must be 0", who, colptr[0]);
+    for (int j = 0; j < m; j++)
+        if (colptr[j + 1] < colptr[j]) return fail(h, NNLM_ERR_ARG, "%s: colptr decreases at column %d", who, j);
+    const long long nnz = colptr[m];
+    if (nnz > 0 && !rowidx) return fail(h, NNLM_ERR_ARG, "%s: rowidx is NULL with %lld held-out entries", who, nnz);
+    if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "%s: %lld held-out entries exceed n * m", who, nnz);
+    for (int j = 0; j < m; j++)
+        for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
+            const int i = rowidx[e];
+            if (i < 0 || i >= n) return fail(h, NNLM_ERR_ARG, "%s: row index %d out of range at entry %lld (column %d)", who, i, e, j);
+            if (e > colptr[j] && i <= rowidx[e - 1])
+                return fail(h, NNLM_ERR_ARG, "%s: row indices of column %d are not strictly increasing (entry %lld)", who, j, e);
+        }
+    if (nnz == (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "%s: every entry is held out; nothing is left to fit", who);
+    std::vector<double> hv((size_t)nnz);
+    std::vector<int> cidx((size_t)nnz);
+    for (int j = 0; j < m; j++)
+        for (long long e = colptr[j]; e < colptr[j + 1]; e++) cidx[e] = j;
+    int rc = set_matrix_impl(h, A, n, m, colptr, rowidx, hv.data());
+    if (rc != NNLM_OK) return rc;
+    h->holdout = true;
+    h->ho_nnz = nnz;
+    const size_t es = esize(h);
+    auto up = [&]() -> int {
+        HIPCHK(h, hipMalloc(&h->ho_cptr, (size_t)(m + 1) * 8));
+        HIPCHK(h, hipMalloc(&h->ho_ridx, (size_t)nnz * 4 + 64));
+        HIPCHK(h, hipMalloc(&h->ho_cidx, (size_t)nnz * 4 + 64));
+        HIPCHK(h, hipMalloc(&h->ho_val, (size_t)nnz * es + 64));
+        HIPCHK(h, hipMemcpy(h->ho_cptr, colptr, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+        if (nnz > 0) {
+            HIPCHK(h, hipMemcpy(h->ho_ridx, rowidx, (size_t)nnz * 4, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(h->ho_cidx, cidx.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+            if (h->prec == NNLM_PREC_F64) HIPCHK(h, hipMemcpy(h->ho_val, hv.data(), (size_t)nnz * 8, hipMemcpyHostToDevice));
+            else {
+                std::vector<float> hf(hv.begin(), hv.end());
+                HIPCHK(h, hipMemcpy(h->ho_val, hf.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+            }
+        }
+        return NNLM_OK;
+    };
+    rc = up();
+    if (rc != NNLM_OK) free_matrix(h);
+    return rc;
 }
 
 // Sparse A (include/nnlm_mi355x.h): canonical CSC, absent entries are zeros.  Validated on the host, the CSR of the same matrix is built
@@ -1977,10 +2096,15 @@ static int ensure_klsw_cols(nnlm_handle *h)
     return NNLM_OK;
 }
 
-// Per-column Grams of columns [c0, c1) into Gcols (row lists exist for all the side's columns)
-static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1)
+// Per-column Grams of columns [c0, c1) into Gcols (row lists exist for all the side's columns).  A member of a batched factorisation
+// (member = true) passes ITS rows of the fixed factor (Y, rank h->k = k_b: rows behind k_b are its neighbour's and enter the row copy
+// as zeros), its own full Gram (Gfull, row stride h->KP) and the word that holds max|Y| over its own rows (maxw, F32 mode)
+static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1, const double *Y = nullptr, const double *Gfull = nullptr,
+                          const unsigned *maxw = nullptr)
 {
     const int nc = c1 - c0, p = s.p;
+    const bool member = Y != nullptr;
+    if (!member) Y = s.Y, Gfull = h->Graw, maxw = h->fixed_maxw ? h->fixed_maxw : h->maxbits;
     if (nc <= 0) return NNLM_OK;
     int rc = ensure_na_lists(h, s);
     if (rc != NNLM_OK) return rc;
@@ -1991,17 +2115,18 @@ static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1)
     // max|fixed factor| is in *fixed_maxw (prepare_factor16 ran for this half-step's cross product).
     if (h->x16 && !generic_rank(h)) {
         // [p + 64 rows][64 hi | 64 lo halves]; rows p .. are zero (the kernel's "no row" index)
-        factor16c_kernel<<<p / 64 + 1, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->k, h->fixed_maxw ? h->fixed_maxw : h->maxbits, h->scal_exp + 3, (uint32_t *)h->Yrow);
+        factor16c_kernel<<<p / 64 + 1, 256, 0, h->stream>>>(Y, s.ldy, p, h->k, maxw, h->scal_exp + 3, (uint32_t *)h->Yrow);
         const int nb = (nc + 3) / 4;
         with_nkq(h->NKQ, [&](auto N) {
-            na_gram_f16_kernel<N><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const uint32_t *)h->Yrow, p, h->scal_exp + 3, h->Graw, h->Gcols, c1, c0, h->k);
+            na_gram_f16_kernel<N><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const uint32_t *)h->Yrow, p, h->scal_exp + 3, Gfull, h->Gcols, c1, c0, h->k);
         });
         return NNLM_OK;
     }
-    factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, p, h->KP, h->Yrow);
+    if (member) factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(Y, s.ldy, p, h->KP, h->Yrow, h->k);
+    else factor_rows_kernel<double><<<(p + 255) / 256, 256, 0, h->stream>>>(Y, s.ldy, p, h->KP, h->Yrow);
     if (generic_rank(h)) { // rank > 64: k_generic.h
         const int lds = 16 * h->KP * 8;
-        na_gram_generic_kernel<<<nc, 256, lds, h->stream>>>(ptr, meta, idx, h->Yrow, h->KP, h->Graw, h->Gcols, c0);
+        na_gram_generic_kernel<<<nc, 256, lds, h->stream>>>(ptr, meta, idx, h->Yrow, h->KP, Gfull, h->Gcols, c0);
         return NNLM_OK;
     }
     // strict mode: fp64 rows gathered by LDS-DMA, v_mfma_f64_16x16x4_f64 (k_missing.h, na_gram_lds_kernel); tail form for k = 16 j + 1, + 2
@@ -2010,7 +2135,7 @@ static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1)
     const bool tl = h->NKQ >= 2 && (ntail == 1 || ntail == 2);
     with_nkq(h->NKQ, [&](auto N) {
         auto go = [&](auto nt, auto tail) {
-            na_gram_lds_kernel<double, nt, tail><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const double *)h->Yrow, h->Graw, h->Gcols, c1, c0, h->k);
+            na_gram_lds_kernel<double, nt, tail><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const double *)h->Yrow, Gfull, h->Gcols, c1, c0, h->k);
         };
         if constexpr (N == 1) go(N, std::false_type{});
         else if (tl) go(std::integral_constant<int, N - 1>{}, std::true_type{});
@@ -3121,6 +3246,7 @@ extern "C" int nnlm_comm_init(nnlm_handle *h, const char id[NNLM_COMM_ID_BYTES],
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_comm_init: handle is NULL");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, NNLM_ERR_ARG, "nnlm_comm_init: bad rank %d of %d", rank, nranks);
     if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a sparse matrix; the sparse path is single-GPU only");
+    if (h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a matrix with a hold-out set; that path is single-GPU only");
     HIPCHK(h, hipSetDevice(h->device));
     if (h->comm) {
         g_rccl.CommDestroy((ncclComm_t)h->comm);
@@ -3169,6 +3295,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "kl_form_w") == 0) *value = h->kl_form[0];
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
     else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
+    else if (strcmp(key, "matrix_holdout") == 0) *value = h->holdout ? (double)h->ho_nnz : -1.0;
     else if (strcmp(key, "matrix_bytes") == 0) *value = matrix_bytes(h);
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
     else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
@@ -3498,7 +3625,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
 static int batch_refusal(nnlm_handle *h, const char *who)
 {
     if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
-    if (h->any_missing) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
+    if (h->any_missing && !h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
     if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the batched factorisation runs on one GPU (no communicator)", who);
     return NNLM_OK;
 }
@@ -3594,6 +3721,19 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     h->fuse_err = false;
     h->cur_which = which;
     const HalfPlan p = plan_half(h, which, 0, 1);
+    // Hold-out handle with a non-empty set: A has missing entries, every column solves with a Gram of its own.  The
+    // cross product below needs nothing new (A holds 0 at a missing entry); the NA workspaces: the row copy for the stacked KP (at least
+    // any member's), ONE buffer of per-column Grams sized for the largest member -- the members run one after another on this stream
+    const bool na = h->any_missing;
+    if (na) {
+        int rcw = ensure_yrow(h);
+        if (rcw != NNLM_OK) return rcw;
+        if (!h->Gcols) {
+            int kpm = 16;
+            for (int b = 0; b < h->bB; b++) kpm = kpm > 16 * ((h->bk[b] + 15) / 16) ? kpm : 16 * ((h->bk[b] + 15) / 16);
+            HIPCHK(h, hipMalloc(&h->Gcols, (size_t)(h->n > h->m ? h->n : h->m) * kpm * kpm * 8));
+        }
+    }
     // 1. one cross product for all members: split-fp16 copy of the whole stacked factor (ONE scale, max over all members), then the
     //    A-streaming kernel exactly as a rank-K solo half-step launches it
     if (h->x16) prepare_factor16(h, s);
@@ -3636,6 +3776,27 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
         else a.op_mode = 0;
         h->pack_ready = false; // (strict mode: the sweep packs its operand image from this member's Gram)
         ProfScope ps(h, s.prof_sweep);
+        if (na) {
+            // as a solo rank-k_b missing-value half-step launches them (half_step_solve): the member's per-column Grams over the observed
+            // rows from ITS rows of the fixed factor and ITS full Gram (complement form), then the column solver on its row block.
+            // F32 mode: the split-fp16 row copy takes its scale from max|Y| over the member's own k_b rows (the stacked factor's scale
+            // would cost a small member the bits its neighbours' magnitude takes, and make it depend on them)
+            const double *Yb = s.Y + (size_t)o * s.ldy;
+            unsigned *mw = h->maxbits + 11;
+            if (h->x16) {
+                if (hipMemsetAsync(mw, 0, sizeof(unsigned), h->stream) != hipSuccess) {
+                    rc = fail(h, NNLM_ERR_HIP, "batch half-step: hipMemsetAsync failed");
+                    break;
+                }
+                absmax_f64_kernel<<<(s.p + 255) / 256, 256, 0, h->stream>>>(Yb, s.ldy, s.p, kb, mw);
+            }
+            rc = launch_na_gram(h, s, 0, s.ncols, Yb, G, mw);
+            if (rc != NNLM_OK) break;
+            a.Graw = h->Gcols;
+            a.nslabs = p.S;
+            launch_colsolve(h, method, a, (size_t)h->KP * h->KP);
+            continue;
+        }
         rc = launch_sweep(h, method, a);
     }
     h->k = K, h->NKQ = NKQ, h->KP = KP, h->KP8 = KP8, h->MW = MW;
@@ -3657,7 +3818,14 @@ static int batch_errors(nnlm_handle *h, unsigned long long amask, bool need_pen,
         const int nch = mt < 1 ? 1 : (mt < (1024 + nit - 1) / nit ? mt : (1024 + nit - 1) / nit);
         const int nblk = nit * nch;
         dim3 grid(nit, nch);
-        if (h->prec == NNLM_PREC_F64)
+        if (h->any_missing) { // (a hold-out handle: the entries with a set miss bit stay out of both sums)
+            if (h->prec == NNLM_PREC_F64)
+                errors_batch_kernel<double, true><<<grid, 256, 0, st>>>((const double *)h->A, h->npad, h->W64, h->npad, h->H64, h->mpad, h->n, h->m,
+                                                                       h->boff_dev, B, amask, h->bpart, nblk, h->miss, h->npad / 32);
+            else
+                errors_batch_kernel<float, true><<<grid, 256, 0, st>>>((const float *)h->A, h->npad, h->W64, h->npad, h->H64, h->mpad, h->n, h->m,
+                                                                      h->boff_dev, B, amask, h->bpart, nblk, h->miss, h->npad / 32);
+        } else if (h->prec == NNLM_PREC_F64)
             errors_batch_kernel<double><<<grid, 256, 0, st>>>((const double *)h->A, h->npad, h->W64, h->npad, h->H64, h->mpad, h->n, h->m, h->boff_dev,
                                                              B, amask, h->bpart, nblk);
         else
@@ -3762,6 +3930,60 @@ extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const doubl
     return NNLM_OK;
 }
 
+// Held-out errors of the current factors (include/nnlm_mi355x.h): mse[b], mkl[b] for the bB members of a batch, or [0] for solo factors.
+// Row copies of W and H, holdout_errors_kernel over the held-out CSC, batch_reduce_kernel; workspaces live for the call.  Synchronises.
+extern "C" int nnlm_holdout_errors(nnlm_handle *h, double *mse, double *mkl)
+{
+    if (!h || !h->holdout) return fail(h, NNLM_ERR_ARG, "nnlm_holdout_errors: the handle has no hold-out set (nnlm_set_matrix_holdout)");
+    if (!h->W64 || !mse || !mkl) return fail(h, NNLM_ERR_ARG, "nnlm_holdout_errors: set the factors first; mse and mkl must not be NULL");
+    HIPCHK(h, hipSetDevice(h->device));
+    g_attr_err = hipSuccess;
+    const int B = h->bB ? h->bB : 1, K = h->k, n = h->n, m = h->m;
+    if (h->ho_nnz == 0) {
+        for (int b = 0; b < B; b++) mse[b] = mkl[b] = std::nan("");
+        sync_all(h);
+        return NNLM_OK;
+    }
+    std::vector<int> off(B + 1, 0);
+    if (h->bB) off = h->boff;
+    else off[1] = K;
+    const long long nnz = h->ho_nnz;
+    long long nbx = (nnz + 1023) / 1024; // at least four entries per lane
+    if (nbx > 2048) nbx = 2048;
+    const long long chunk = (nnz + nbx - 1) / nbx;
+    double *rows = nullptr, *part = nullptr;
+    int *offd = nullptr;
+    const size_t nrow = (size_t)(n + m) * K, npart = (size_t)2 * B * nbx;
+    hipError_t e = hipMalloc(&rows, nrow * 8);
+    if (e == hipSuccess) e = hipMalloc(&part, (npart + 2 * B) * 8);
+    if (e == hipSuccess) e = hipMalloc(&offd, (B + 1) * sizeof(int));
+    std::vector<double> out((size_t)2 * B);
+    hipStream_t st = h->stream;
+    if (e == hipSuccess) e = hipMemcpyAsync(offd, off.data(), (B + 1) * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        double *Wrow = rows, *Hrow = rows + (size_t)n * K;
+        factor_rows_kernel<double><<<(n + 255) / 256, 256, 0, st>>>(h->W64, h->npad, n, K, Wrow);
+        factor_rows_kernel<double><<<(m + 255) / 256, 256, 0, st>>>(h->H64, h->mpad, m, K, Hrow);
+        dim3 grid((unsigned)nbx, B);
+        if (h->prec == NNLM_PREC_F64)
+            holdout_errors_kernel<double><<<grid, 256, 0, st>>>(h->ho_ridx, h->ho_cidx, (const double *)h->ho_val, nnz, chunk, Wrow, Hrow, K, offd, part);
+        else
+            holdout_errors_kernel<float><<<grid, 256, 0, st>>>(h->ho_ridx, h->ho_cidx, (const float *)h->ho_val, nnz, chunk, Wrow, Hrow, K, offd, part);
+        batch_reduce_kernel<<<2 * B, 256, 0, st>>>(part, (int)nbx, part + npart);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out.data(), part + npart, (size_t)2 * B * 8, hipMemcpyDeviceToHost, st);
+    }
+    const hipError_t es = hipStreamSynchronize(st); // (before the workspaces go)
+    if (e == hipSuccess) e = es;
+    hipFree(rows);
+    hipFree(part);
+    hipFree(offd);
+    if (e != hipSuccess) return fail(h, NNLM_ERR_HIP, "nnlm_holdout_errors failed: %s", hipGetErrorString(e));
+    sync_all(h);
+    for (int b = 0; b < B; b++) mse[b] = out[2 * b] / (double)nnz, mkl[b] = out[2 * b + 1] / (double)nnz;
+    return NNLM_OK;
+}
+
 // The handle of a one-shot entry: created on NNLM_DEVICE in the NNLM_PRECISION mode and given the matrix (set_matrix(h)); destroyed
 // when the entry returns
 struct OneShot {
@@ -3830,6 +4052,37 @@ extern "C" int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, cons
     CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
                        mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
     CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    return NNLM_OK;
+}
+
+// nnlm_c_nnmf_batch on A with the pattern (colptr, rowidx) held out: + the held-out errors of the final factors, per member
+extern "C" int nnlm_c_nnmf_holdout_batch(const double *A, int n, int m, const long long *colptr, const int *rowidx, unsigned B, const unsigned *k,
+                                         const double *W_init, const double *H_init, const double alpha[3], const double beta[3],
+                                         unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning,
+                                         unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out, double *H_out,
+                                         double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
+                                         unsigned *n_iteration, int *warned, double *holdout_mse, double *holdout_mkl, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (any_null(A, colptr, k, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned) ||
+        any_null(holdout_mse, holdout_mkl))
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_holdout_batch: NULL argument");
+    int rc = batch_ranks(nullptr, "nnlm_c_nnmf_holdout_batch", "members", B, k, [&] {
+        return (method >= 3 && method <= 4) ? fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_holdout_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method)
+                                            : NNLM_OK;
+    });
+    if (rc != NNLM_OK) return rc;
+    OneShot os;
+    rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix_holdout(h, A, n, m, colptr, rowidx); });
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
+    std::vector<double> Wi, Hi;
+    default_factors(cb, n, m, B, k, nullptr, nullptr, &W_init, &H_init, Wi, Hi);
+    CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
+    CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
+    CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    CHK(nnlm_holdout_errors(h, holdout_mse, holdout_mkl));
     return NNLM_OK;
 }
 
