@@ -194,6 +194,34 @@ int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, do
 int nnlm_set_factors(nnlm_handle *h, unsigned k, const double *W, const double *H, const int *Wm, const int *Hm);
 int nnlm_get_factors(nnlm_handle *h, double *W, double *H);
 
+/* ------------------------------------------------------------------------------------------
+ * Matrices and factors that already live in device memory (a tensor pipeline's output, an earlier fit): no trip through the host.
+ * A descriptor is plain data: element (i, j) of the matrix is at ptr[i * row_stride + j * col_stride], strides in ELEMENTS, both
+ * positive, and the layout may not overlap itself: col_stride >= rows * row_stride (column-major family) or row_stride >= cols *
+ * col_stride (row-major family).  ptr is device or managed memory of the handle's device.  Every rule is checked before a kernel reads
+ * the pointer; a violation is NNLM_ERR_ARG naming the argument (a host pointer, another device's memory, a dtype out of range, a zero
+ * or negative stride, an overlapping layout, an extent past the end of its allocation, and -- best effort -- a buffer of the handle itself).
+ * `stream` is the caller's hipStream_t on which the data was produced or will be consumed (NULL: the default stream).  Ordering goes
+ * through events: an input entry makes the handle's stream wait for what the caller's stream holds at the call; the output entry also
+ * makes the caller's stream wait for the export.  The two set entries return after their kernels have run (as the host entries return
+ * after their copies); the get entry does not wait on the host at all.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct { const void *ptr; int dtype; long long row_stride, col_stride; } nnlm_dev_matrix; /* strides in elements */
+enum { NNLM_DT_F64 = 0, NNLM_DT_F32 = 1, NNLM_DT_F16 = 2, NNLM_DT_BF16 = 3 };
+/* nnlm_set_matrix on the fp64 widening of A's values (any of the four types, exact): non-finite entries are missing, NNLM_PREC_F32
+ * applies the same range rule (NNLM_ERR_UNSUPPORTED), and the handle afterwards is the plain dense handle nnlm_set_matrix leaves -- A,
+ * the missing bits and n_non_missing are that upload's bit for bit; kl_const too when row_stride = 1 (the same partial sums in the same
+ * order), otherwise it differs by summation order only.  row_stride = 1 (R / Fortran order) and col_stride = 1 (C order) are read and
+ * written in contiguous runs (one pass over A); other strides are gathered element by element: correct, not fast. */
+int nnlm_set_matrix_device(nnlm_handle *h, const nnlm_dev_matrix *A, int n, int m, void *stream);
+/* nnlm_set_factors with W (n x k) and H (k x m) in device memory, any of the four types; a NULL descriptor = zeros; the masks stay
+ * host arrays with the same meaning. */
+int nnlm_set_factors_device(nnlm_handle *h, unsigned k, const nnlm_dev_matrix *W, const nnlm_dev_matrix *H, const int *Wm, const int *Hm,
+                            void *stream);
+/* The current factors into the caller's buffers: dtype NNLM_DT_F64 or NNLM_DT_F32 (rounded to nearest); only the n x k / k x m entries
+ * are written, the gaps of a strided buffer stay as they are; a NULL descriptor = not wanted. */
+int nnlm_get_factors_device(nnlm_handle *h, const nnlm_dev_matrix *W, const nnlm_dev_matrix *H, void *stream);
+
 /*
  * One half-step = update()/update_with_missing() (reference src/update_with_missing.cpp:3-55, :58-139).
  * which = 0 updates W (solves A^T ~ H^T W^T with `reg` = alpha), 1 updates H (`reg` = beta).
@@ -326,6 +354,8 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
  * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
  * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies),
+ * "matrix_min_col_observed" / "matrix_min_row_observed" (dense matrix: the fewest observed -- finite -- entries of any column / any row,
+ * n / m without missing entries; counted on the device at the first query; -1 on a sparse handle),
  * "matrix_absent_missing" (1 after nnlm_set_matrix_csc_missing, else 0), "sp_gram_chunks" / "sp_gram_bytes" (column chunks of the last
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),

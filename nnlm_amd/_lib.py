@@ -37,6 +37,7 @@ EXPORTS = [
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
     "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
+    "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
 ]
 
 
@@ -44,6 +45,17 @@ class NnlmError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libnnlm_mi355x error {code}: {msg}")
         self.code = code
+
+
+class DevMatrix(C.Structure):
+    """nnlm_dev_matrix: element (i, j) at ptr[i * row_stride + j * col_stride], strides in elements."""
+    _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("row_stride", C.c_longlong), ("col_stride", C.c_longlong)]
+
+
+DT_F64, DT_F32, DT_F16, DT_BF16 = 0, 1, 2, 3
+_DT_SIZE = {DT_F64: 8, DT_F32: 4, DT_F16: 2, DT_BF16: 2}
+_DT_NAMES = {"float64": DT_F64, "float32": DT_F32, "float16": DT_F16, "bfloat16": DT_BF16, "double": DT_F64, "float": DT_F32, "half": DT_F16}
+_DT_TYPESTR = {"f8": DT_F64, "f4": DT_F32, "f2": DT_F16}
 
 
 class Callbacks(C.Structure):
@@ -165,6 +177,13 @@ def load():
     lib.nnlm_c_nnmf_holdout_batch.restype = C.c_int
     lib.nnlm_c_nnmf_holdout_batch.argtypes = (lib.nnlm_c_nnmf_batch.argtypes[:3] + [lp, ip] + lib.nnlm_c_nnmf_batch.argtypes[3:-1]
                                               + [dp, dp, C.POINTER(Callbacks)])
+    dmp = C.POINTER(DevMatrix)
+    lib.nnlm_set_matrix_device.restype = C.c_int
+    lib.nnlm_set_matrix_device.argtypes = [vp, dmp, C.c_int, C.c_int, vp]
+    lib.nnlm_set_factors_device.restype = C.c_int
+    lib.nnlm_set_factors_device.argtypes = [vp, C.c_uint, dmp, dmp, ip, ip, vp]
+    lib.nnlm_get_factors_device.restype = C.c_int
+    lib.nnlm_get_factors_device.argtypes = [vp, dmp, dmp, vp]
     _lib = lib
     return lib
 
@@ -210,6 +229,113 @@ def _csc_arrays(indptr, indices, data):
     (nnlm_set_matrix_csc checks it: canonicalisation is the caller's, see api.as_csc)."""
     return (np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32),
             np.ascontiguousarray(data, dtype=np.float64))
+
+
+# ----------------------------------------------------------------------------------------------
+# arrays in device memory (nnlm_dev_matrix); no tensor library is ever imported here
+# ----------------------------------------------------------------------------------------------
+def _is_tensor_like(x):
+    return all(hasattr(x, a) for a in ("data_ptr", "stride", "shape", "dtype", "device")) and callable(x.data_ptr)
+
+
+def is_device_array(x):
+    """True for what dev_matrix() takes as device memory: a tensor-like object (data_ptr(), stride(), shape, dtype, device) whose
+    device is not the CPU, or any other object exposing __cuda_array_interface__."""
+    if x is None or isinstance(x, (np.ndarray, np.generic, list, tuple, dict, int, float)):
+        return False
+    if _is_tensor_like(x):
+        return getattr(x.device, "type", "cpu") != "cpu"
+    try:
+        return isinstance(getattr(x, "__cuda_array_interface__", None), dict)
+    except Exception:
+        return False
+
+
+def _dev_restrict(what):
+    return ValueError("device array: " + what)
+
+
+def dev_matrix(x, device=None):
+    """(DevMatrix, keep-alive, (rows, cols), stream or None) of a 2-D floating-point array in device memory.
+
+    x: a tensor-like object (duck-typed on data_ptr(), stride() in elements, shape, dtype, device) or any object with
+    __cuda_array_interface__ (versions 2 and 3; strides in bytes, None = C-contiguous).  device: the handle's device index, checked
+    against the tensor's when it names one.  The `stream` of a version-3 interface is returned (1 = the default stream -> None).
+    ValueError, before any device call, for anything not 2-D, an integer / bool / complex dtype, a zero or negative stride, a host
+    tensor, a tensor of another device."""
+    stream = None
+    if _is_tensor_like(x):
+        dev = x.device
+        if getattr(dev, "type", "cpu") == "cpu":
+            raise _dev_restrict("the tensor lives in host memory (device %s); pass it as a host array, or move it to the GPU" % (dev,))
+        idx = getattr(dev, "index", None)
+        if device is not None and idx is not None and int(idx) != int(device):
+            raise _dev_restrict("the tensor lives on device %d, the handle on device %d" % (int(idx), int(device)))
+        shape = tuple(int(v) for v in x.shape)
+        name = str(x.dtype).split(".")[-1]
+        if name not in _DT_NAMES:
+            raise _dev_restrict("dtype %s is not supported: float64, float32, float16 or bfloat16 (no integer, bool or complex)" % (x.dtype,))
+        dt = _DT_NAMES[name]
+        if len(shape) != 2:
+            raise _dev_restrict("a %d-D array; the matrix must be 2-D" % len(shape))
+        strides = tuple(int(v) for v in x.stride())
+        ptr = int(x.data_ptr())
+    else:
+        try:
+            cai = x.__cuda_array_interface__
+        except Exception:
+            cai = None
+        if not isinstance(cai, dict):
+            raise _dev_restrict("%s is neither a tensor (data_ptr / stride / shape / dtype / device) nor a __cuda_array_interface__ "
+                                "producer" % type(x).__name__)
+        if int(cai.get("version", 0)) < 2:
+            raise _dev_restrict("__cuda_array_interface__ version %s; versions 2 and 3 are supported" % cai.get("version"))
+        shape = tuple(int(v) for v in cai["shape"])
+        ts = str(cai["typestr"])
+        if ts[:1] == ">" or ts[1:] not in _DT_TYPESTR:
+            raise _dev_restrict("typestr %r is not supported: little-endian f8, f4 or f2 (no integer, bool or complex)" % ts)
+        dt = _DT_TYPESTR[ts[1:]]
+        if len(shape) != 2:
+            raise _dev_restrict("a %d-D array; the matrix must be 2-D" % len(shape))
+        es = _DT_SIZE[dt]
+        if cai.get("strides") is None:
+            strides = (shape[1], 1)
+        else:
+            sb = tuple(int(v) for v in cai["strides"])
+            if any(v % es for v in sb):
+                raise _dev_restrict("strides %s are not multiples of the %d-byte element" % (sb, es))
+            strides = tuple(v // es for v in sb)
+        ptr = int(cai["data"][0])
+        idx = getattr(getattr(x, "device", None), "id", None)
+        if device is not None and isinstance(idx, int) and idx != int(device):
+            raise _dev_restrict("the array lives on device %d, the handle on device %d" % (idx, int(device)))
+        st = cai.get("stream") if int(cai.get("version", 0)) >= 3 else None
+        if st is not None and int(st) != 1:
+            stream = int(st)
+    if shape[0] < 1 or shape[1] < 1:
+        raise _dev_restrict("an empty %d x %d array" % shape)
+    if strides[0] < 1 or strides[1] < 1:
+        raise _dev_restrict("strides %s (in elements): zero (broadcast / expand) and negative strides are not accepted; make the array "
+                            "contiguous first" % (strides,))
+    return DevMatrix(ptr, dt, strides[0], strides[1]), x, shape, stream
+
+
+def _tensor_module(x):
+    """The already imported tensor library of a tensor (sys.modules lookup: nothing is imported here), or None."""
+    import sys
+    root = (type(x).__module__ or "").split(".")[0]
+    return sys.modules.get(root) if root == "torch" else None
+
+
+def _stream_of(x, stream):
+    """hipStream_t (int or None) for a call on x: an explicit stream (an int, or an object with cuda_stream), else the tensor library's
+    current stream of x's device."""
+    if stream is not None:
+        return int(getattr(stream, "cuda_stream", stream)) or None
+    mod = _tensor_module(x) if x is not None and _is_tensor_like(x) else None
+    if mod is None:
+        return None
+    return int(mod.cuda.current_stream(x.device).cuda_stream) or None
 
 
 def _vec3(v):
@@ -447,6 +573,7 @@ class Handle:
         self._lib = load()
         self._h = C.c_void_p()
         _check(self._lib.nnlm_create(C.byref(self._h), int(device), int(precision)))
+        self.device = int(device)
         self.n = self.m = self.k = 0
 
     def close(self):
@@ -500,6 +627,43 @@ class Handle:
             raise NnlmError(ERR_ARG, "the hold-out pattern has fewer row indices than its last column pointer")
         self._ck(self._lib.nnlm_set_matrix_holdout(self._h, _dp(A), n, m, _lp(ptr), _ip(idx)))
         self.n, self.m = n, m
+
+    def set_matrix_device(self, x, stream=None):
+        """set_matrix for a matrix in device memory (see dev_matrix): no copy through the host, any of fp64 / fp32 / fp16 / bf16, any
+        non-overlapping strides.  stream: the hipStream_t (or an object with cuda_stream) that produced x; None = the tensor library's
+        current stream for x's device (a tensor), the interface's own stream (__cuda_array_interface__ version 3) or the default stream."""
+        d, keep, (n, m), st = dev_matrix(x, self.device)
+        st = _stream_of(x, stream) if (stream is not None or st is None) else st
+        self._ck(self._lib.nnlm_set_matrix_device(self._h, C.byref(d), n, m, C.c_void_p(st)))
+        self.n, self.m = n, m
+        del keep
+
+    def set_factors_device(self, k, W=None, H=None, Wm=None, Hm=None, stream=None):
+        """set_factors with W (n x k) and H (k x m) in device memory; None = zeros; the masks are host arrays."""
+        k = int(k)
+        dW = dev_matrix(W, self.device) if W is not None else None
+        dH = dev_matrix(H, self.device) if H is not None else None
+        for d, shp, nm in ((dW, (self.n, k), "W"), (dH, (k, self.m), "H")):
+            if d is not None and d[2] != shp:
+                raise NnlmError(ERR_ARG, f"{nm} has shape {d[2]}, rank {k} needs {shp}")
+        first = W if W is not None else H
+        st = _stream_of(first, stream)
+        self.k = k
+        self._batch = False
+        self._ck(self._lib.nnlm_set_factors_device(self._h, k, C.byref(dW[0]) if dW else None, C.byref(dH[0]) if dH else None,
+                                                   _ip(_lgl(Wm, (self.n, k))), _ip(_lgl(Hm, (k, self.m))), C.c_void_p(st)))
+
+    def get_factors_device(self, W_out, H_out, stream=None):
+        """The current factors into the caller's device buffers (fp64 or fp32; n x k and k x m; either may be None).  Asynchronous: the
+        caller's stream is made to wait for the export."""
+        dW = dev_matrix(W_out, self.device) if W_out is not None else None
+        dH = dev_matrix(H_out, self.device) if H_out is not None else None
+        for d, shp, nm in ((dW, (self.n, self.k), "W_out"), (dH, (self.k, self.m), "H_out")):
+            if d is not None and d[2] != shp:
+                raise NnlmError(ERR_ARG, f"{nm} has shape {d[2]}, the factors need {shp}")
+        first = W_out if W_out is not None else H_out
+        st = _stream_of(first, stream)
+        self._ck(self._lib.nnlm_get_factors_device(self._h, C.byref(dW[0]) if dW else None, C.byref(dH[0]) if dH else None, C.c_void_p(st)))
 
     def holdout_errors(self):
         """(mse, mkl) arrays over the held-out entries: one value per batch member, or one for solo factors."""
@@ -616,7 +780,8 @@ class Handle:
 
     def get_info(self, key):
         """cus, sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
-        matrix_nnz (-1 for a dense matrix), matrix_bytes."""
+        matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
+        column / a row of a dense matrix)."""
         v = C.c_double(0)
         self._ck(self._lib.nnlm_get_info(self._h, key.encode(), C.byref(v)))
         return v.value

@@ -348,11 +348,17 @@ def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="m
 
 def finish_nnmf(out, ctx, run_time=None):
     """Result decoration of nnmf(), R/nnmf.R:184-224."""
-    res = NnmfResult(W=np.array(out["W"]), H=np.array(out["H"]), mse=np.asarray(out["mse_error"]).ravel(),
+    on_device = _lib.is_device_array(out["W"])  # (nnmf() on a tensor in device memory: W and H stay tensors of that device)
+    res = NnmfResult(W=out["W"] if on_device else np.array(out["W"]), H=out["H"] if on_device else np.array(out["H"]),
+                     mse=np.asarray(out["mse_error"]).ravel(),
                      mkl=np.asarray(out["mkl_error"]).ravel(), target_loss=np.asarray(out["target_error"]).ravel(),
                      average_epochs=np.asarray(out["average_epoch"]).ravel(), n_iteration=int(out["n_iteration"]))
     W_norm = ctx["W_norm"]
-    if W_norm > 0:
+    if W_norm > 0 and on_device:  # the same scaling with the tensor's own operators (a diagonal product is a scaling of columns / rows)
+        W, H = res["W"], res["H"]
+        scale = (W ** W_norm).sum(0) ** (1.0 / W_norm) if np.isfinite(W_norm) else W.max(0).values
+        res["W"], res["H"] = W * (1.0 / scale)[None, :], scale[:, None] * H
+    elif W_norm > 0:
         if np.isfinite(W_norm):
             scale = np.sum(res["W"] ** W_norm, axis=0) ** (1.0 / W_norm)
         else:
@@ -368,6 +374,100 @@ def finish_nnmf(out, ctx, run_time=None):
     return res
 
 
+# ------------------------------------------------------------------------------------------------
+# A in device memory
+# ------------------------------------------------------------------------------------------------
+def _refuse_device(x, who, name):
+    """The entries that stage their matrix on the host say so by name when handed device memory."""
+    if _lib.is_device_array(x):
+        raise NnlmStop("%s: %s lives in device memory; this entry takes host arrays only (nnmf() and nnmf_batch() accept a device "
+                       "matrix) -- copy it to the host first." % (who, name))
+
+
+def _device_index(A):
+    idx = getattr(getattr(A, "device", None), "index", None)
+    if idx is None:
+        idx = getattr(getattr(A, "device", None), "id", None)
+    return int(idx) if isinstance(idx, (int, np.integer)) else int(os.environ.get("NNLM_DEVICE", "0") or 0)
+
+
+def _device_matrix(A, h):
+    """_nnmf_matrix for a matrix in device memory: ingested into the handle h (nnlm_set_matrix_device), its shape, and check_k's bound
+    from the handle's counts of observed entries -- every NON-FINITE entry counts as missing here (the fit's own rule); the host route
+    counts NaN only, so a matrix with +-Inf entries can get a smaller bound here."""
+    h.set_matrix_device(A)
+    n, m = h.n, h.m
+    min_k = min(n, m)
+    if h.matrix_info()["any_missing"]:
+        min_k = min(min_k, int(h.get_info("matrix_min_row_observed")), int(h.get_info("matrix_min_col_observed")))
+    return dict(A=A, n=n, m=m, min_k=min_k)
+
+
+def _host_factor_entries(init, who):
+    """init entries that are tensors in device memory, as host fp64 arrays (k (n + m) elements: the one small copy of the device route;
+    the stacking of W / W0 / W1 and the checks of reformat_input stay one piece of host code)."""
+    if init is None:
+        return None
+    out = dict(init)
+    for key, v in out.items():
+        if _lib.is_device_array(v):
+            if not callable(getattr(v, "cpu", None)):
+                raise NnlmStop("%s: init$%s lives in device memory but is not a tensor (no cpu()); pass it as a host array." % (who, key))
+            out[key] = np.asarray(v.detach().cpu().double().numpy() if callable(getattr(v, "detach", None)) else v.cpu(), dtype=np.float64)
+    return out
+
+
+def _default_init(W, H, Wm, Hm, n, m, K, g):
+    """What nnmf() leaves empty, c_nnmf draws through unif_rand (src/nnmf.cpp:82-98): 0.01 U(0,1), W row by row first, then H
+    column-major, masked entries drawn and zeroed."""
+    if not np.size(W):
+        W = 0.01 * g.random(n * K).reshape((n, K))
+        if np.size(Wm):
+            W[np.asarray(Wm, dtype=bool).reshape(n, K)] = 0.0
+    if not np.size(H):
+        H = 0.01 * g.random(K * m).reshape((K, m), order="F")
+        if np.size(Hm):
+            H[np.asarray(Hm, dtype=bool).reshape(K, m)] = 0.0
+    return W, H
+
+
+def _tensor_lib(A):
+    """The tensor library of A when A is one of its tensors (imported here only: the package itself never imports it), else None."""
+    if (type(A).__module__ or "").split(".")[0] != "torch":
+        return None
+    import torch
+    return torch
+
+
+def _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
+                 show_warning, inner_max_iter, inner_rel_tol, rng, absent):
+    """nnmf() on a matrix in device memory: ingest, factors, run and export on one Handle; A never visits the host."""
+    torch = _tensor_lib(A)
+    g = rng or np.random.default_rng()
+    t0 = time.perf_counter()
+    with _lib.Handle(_device_index(A), _env_precision()) as h:
+        mat = _device_matrix(A, h)
+        args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, _host_factor_entries(init, "nnmf"), mask, W_norm, check_k, max_iter,
+                                     rel_tol, n_threads, trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, matrix=mat,
+                                     absent=absent)
+        ctx["init"] = init
+        n, m, K = mat["n"], mat["m"], args[1]
+        Wm, Hm = args[4], args[5]
+        W, H = _default_init(args[2], args[3], Wm, Hm, n, m, K, g)
+        cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
+        h.set_factors(K, W, H, Wm, Hm)
+        # (alpha, beta, max_iter, rel_tol | verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace: n_threads has no place)
+        out = h.run(*args[6:10], *args[11:], callbacks=cb)
+        if torch is not None:
+            Wo = torch.empty((n, K), dtype=torch.float64, device=A.device)
+            Ho = torch.empty((K, m), dtype=torch.float64, device=A.device)
+            h.get_factors_device(Wo, Ho)
+            out["W"], out["H"] = Wo, Ho
+        else:
+            out["W"], out["H"] = h.get_factors()
+    return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
+
+
 def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
          check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=0, show_warning=True,
          inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero"):
@@ -376,7 +476,18 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     ``verbose`` defaults to 0 here (R: 1 = progress bar); ``rng`` seeds the default random init (R uses its global RNG).
     ``absent`` (sparse A only): "zero" -- absent entries are zeros; "missing" -- they are missing and the fit runs over the stored
     entries only, as the reference does for NA (a score matrix such as movies x customers; square loss, k <= 64).
+
+    ``A`` may live in device memory: a torch tensor on the GPU (fp64, fp32, fp16 or bf16; any non-overlapping strides) or any object with
+    ``__cuda_array_interface__``.  It is then ingested where it is -- no copy through the host -- and fitted in the arithmetic mode
+    NNLM_PRECISION names.  For a torch tensor W and H come back as fp64 tensors on A's device (W_norm applied there) and the traces as
+    numpy arrays; for another producer W and H come back as numpy arrays.  With the same seeded ``rng`` the fit is the host route's.
+    init entries and known profiles may be host arrays or tensors of that device (the latter are copied to the host, k (n + m) elements,
+    stacked there and uploaded with the other factors); masks are host arrays.  check_k with missing entries:
+    this route counts every non-finite entry (NaN, +-Inf) as missing, as the fit does; the host route counts NaN only.
     """
+    if _lib.is_device_array(A):
+        return _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
+                            show_warning, inner_max_iter, inner_rel_tol, rng, absent)
     args, ctx = prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads,
                              trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent)
     g = rng or np.random.default_rng()
@@ -432,7 +543,10 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
     if sum(ks) > _lib.BATCH_MAX:
         raise unsupported("the ranks sum to %d; a batch holds at most %d" % (sum(ks), _lib.BATCH_MAX))
-    shape = A.shape if isinstance(A, np.ndarray) else np.shape(A)
+    on_device = _lib.is_device_array(A)
+    shape = tuple(A.shape) if isinstance(A, np.ndarray) or on_device else np.shape(A)
+    if on_device and init is not None:
+        init = [_host_factor_entries(x, "nnmf_batch") for x in init]
     if init is not None and len(shape) == 2:
         n, m = shape
         for b, x in enumerate(init):
@@ -443,22 +557,45 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
     opts = dict(nnmf_options)
     opts.setdefault("verbose", 0)
     g = rng or np.random.default_rng()
+    h = None
+    if on_device:  # one ingest shared by all members; the handle then runs the batch (what nnlm_c_nnmf_batch does around a host A)
+        h = _lib.Handle(_device_index(A), _env_precision())
+    try:
+        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h)
+    finally:
+        if h is not None:
+            h.close()
+
+
+def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
+    """nnmf_batch behind its argument checks; h: the handle of a device A (None for a host A)."""
+    B = len(ks)
     prep, Ws, Hs, mat = [], [], [], None
+    if h is not None:
+        mat = _device_matrix(A, h)
+        if h.matrix_info()["any_missing"]:
+            raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
     for b in range(B):  # member after member, each consuming the generator as nnmf() would
         # (A is checked and converted by the first member's call only: every member shares that one fp64 copy)
         args, ctx, mat = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
-        if b == 0 and not np.isfinite(mat["A"]).all():
+        if b == 0 and h is None and not np.isfinite(mat["A"]).all():
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
         n, m = mat["n"], mat["m"]
-        W, H = args[2], args[3]
-        # (what nnmf() leaves empty, c_nnmf draws through unif_rand: 0.01 U(0,1), W row by row first, then H column-major)
-        Ws.append(W if np.size(W) else 0.01 * g.random(n * ks[b]).reshape((n, ks[b])))
-        Hs.append(H if np.size(H) else 0.01 * g.random(ks[b] * m).reshape((ks[b], m), order="F"))
+        W, H = _default_init(args[2], args[3], (), (), n, m, ks[b], g)
+        Ws.append(W)
+        Hs.append(H)
         prep.append((args, ctx))
     a0 = prep[0][0]
     cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+    if h is None:
+        outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+    else:
+        h.set_factors_batch(ks, Ws, Hs)
+        outs = h.run_batch(*a0[6:10], *a0[11:], callbacks=cb)
+        torch = _tensor_lib(A)
+        for o, (W, H) in zip(outs, h.get_factors_batch()):
+            o["W"], o["H"] = (W, H) if torch is None else (torch.from_numpy(W).to(A.device), torch.from_numpy(H).to(A.device))
     run_time = time.perf_counter() - t0
     res = [finish_nnmf(o, p[1], run_time=run_time) for o, p in zip(outs, prep)]
     best = int(np.argmin([r["target_loss"][-1] if len(r["target_loss"]) else np.inf for r in res]))
@@ -539,6 +676,7 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
     if is_sparse(A):
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    _refuse_device(A, "nnmf_cv", "A")  # (the hold-out pattern is applied in the upload's host staging pass)
     batches = _pack_batches(ks)
     mat = _nnmf_matrix(A, "mse")
     if not np.isfinite(mat["A"]).all():
@@ -612,6 +750,8 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
     absent = _absent_arg(absent, y, "y")
+    _refuse_device(x, "nnlm", "x")
+    _refuse_device(y, "nnlm", "y")
     x = np.asarray(x)
     y_sparse = is_sparse(y)
     yv = _sparse_input(y, "y", loss, absent) if y_sparse else np.asarray(y)
@@ -699,6 +839,9 @@ def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=
     method = method or object["options"]["method"]
     loss = loss or object["options"]["loss"]
     solver = _nnlm or nnlm
+    _refuse_device(newdata, "predict_nnmf", "newdata")
+    for key in ("W", "H"):
+        _refuse_device(object[key], "predict_nnmf", "object$" + key)
     if which != "A" and _absent_arg(absent, newdata, "newdata") == "missing":  # (which = "A" solves nothing: `absent` is not used)
         kw["absent"] = "missing"
     if which != "A" and is_sparse(newdata):  # (passed on to nnlm() as it is: duck-typed there)

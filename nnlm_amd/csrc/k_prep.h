@@ -10,13 +10,23 @@
 #define PREP_BLOCK 256
 #define PREP_GRID_Y 64
 
-// src: chunk of `cols` columns of the caller's matrix (column-major, leading dimension n).
+// Source element types of the pass: the host upload stages fp64; a matrix that already lives in device memory (k_ingest.h) is read in
+// its own type.  fp16 / bf16 travel as their 16 bits; every type widens to fp64 exactly.
+struct nnlm_f16 { uint16_t bits; };
+struct nnlm_bf16 { uint16_t bits; };
+__device__ static inline double prep_load(const double *p) { return *p; }
+__device__ static inline double prep_load(const float *p) { return (double)*p; }
+__device__ static inline double prep_load(const nnlm_f16 *p) { return (double)__builtin_bit_cast(_Float16, p->bits); }
+__device__ static inline double prep_load(const nnlm_bf16 *p) { return (double)__builtin_bit_cast(float, (uint32_t)p->bits << 16); }
+
+// src: chunk of `cols` columns of the caller's matrix: element (i, jj) at src[jj * ld + i] (the host upload: column-major, ld = n), or at
+// src[jj * ld + i * rs] (GATHER: a device matrix of general strides, correct but uncoalesced).
 // dst: A_dev (column j0+jj of the chunk lands at (j0+jj)*npad).  miss: bit i%32 of word [j][i/32] set <=> A[i,j] is not finite.
 // partial: [gridDim.y*gridDim.x][3] = {finite count, sum((a+eps)log(a+eps)-a), finite entries beyond the range of T} per block.
 // (T = float: a finite |a| > FLT_MAX would become +-Inf in the resident copy -- a "missing" value the bit matrix does not know.  The
 //  reference's fp64 takes such a matrix; the fp32-operand mode refuses it, nnlm_set_matrix.)
-template <typename T>
-__global__ __launch_bounds__(PREP_BLOCK) void prep_convert_kernel(const double *__restrict__ src, int n, int cols, int j0,
+template <typename T, typename S = double, bool GATHER = false>
+__global__ __launch_bounds__(PREP_BLOCK) void prep_convert_kernel(const S *__restrict__ src, size_t ld, size_t rs, int n, int cols, int j0,
                                                                   T *__restrict__ dst, int npad,
                                                                   uint32_t *__restrict__ miss,
                                                                   double *__restrict__ partial)
@@ -29,7 +39,7 @@ __global__ __launch_bounds__(PREP_BLOCK) void prep_convert_kernel(const double *
         double v = 0.0;
         bool fin = true; // padding rows count as "not missing" and are excluded from the sums below
         if (i < n) {
-            v = src[(size_t)jj * n + i];
+            v = prep_load(src + ((size_t)jj * ld + (GATHER ? (size_t)i * rs : (size_t)i)));
             fin = isfinite(v);
             if (fin) {
                 cnt += 1.0;

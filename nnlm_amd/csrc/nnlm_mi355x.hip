@@ -15,6 +15,7 @@
 #include "k_errors.h"
 #include "k_generic.h"
 #include "k_gram.h"
+#include "k_ingest.h"
 #include "k_kl.h"
 #include "k_missing.h"
 #include "k_prep.h"
@@ -28,6 +29,7 @@
 #include <rccl/rccl.h>
 
 #include <atomic>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -42,7 +44,7 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_COUNT };
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -52,9 +54,9 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  block of a sparse A (sums over the non-zeros, the two Grams and the factors' sums)
 //  "batch_errors": the error block of a batched factorisation (errors_batch_kernel + its reduction: one pass over A for all members);
 //  "batch_pen": its per-member penalty sums; "sp_gram": the per-column Grams of a sparse A whose absent entries are missing (sp_gram_kernel
-//  + its fix-up, both half-steps)
+//  + its fix-up, both half-steps); "ingest": the ingest kernels of nnlm_set_matrix_device (k_ingest.h), without the common tail
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram"};
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -94,6 +96,7 @@ struct nnlm_handle {
     size_t pack_tail = 0;       // doubles behind the k x cpr slab in the packed payload of the current half-step (KP * KP Gram partial sums, or 0)
     unsigned *fixed_maxw = nullptr; // word holding max|fixed factor| of the half-step in progress (split-fp16 copies)
     double n_non_missing = 0.0, kl_const = 0.0;
+    int min_obs[2] = {-2, -2};  // fewest observed entries of a column / of a row (nnlm_get_info; observed_min_kernel on first query), -2 = not yet
 
     // factors
     int k = 0, NKQ = 0, KP = 0, KP8 = 0;
@@ -748,6 +751,7 @@ static void free_matrix(nnlm_handle *h)
     h->ho_nnz = 0;
     h->holdout = false;
     h->x16 = x16_enabled(h->prec); // (a sparse matrix turned it off)
+    h->min_obs[0] = h->min_obs[1] = -2;
     h->n = h->m = 0;
 }
 
@@ -804,13 +808,11 @@ extern "C" void nnlm_destroy(nnlm_handle *h)
 // ---------------------------------------------------------------------------------------------
 // matrix upload
 // ---------------------------------------------------------------------------------------------
-// nnlm_set_matrix and nnlm_set_matrix_holdout: one upload.  ho_colptr / ho_rowidx (validated by the caller, NULL for a plain upload):
-// the held-out pattern.  Every chunk of columns then passes through a host staging buffer in which A is checked to be finite and the
-// pattern's entries are replaced by NaN before the DMA -- prep_convert_kernel sees exactly what it sees for a matrix that arrived with
-// NaN there, so the resident state is that upload's bit for bit, and no second n x m array exists anywhere.  ho_val[e]: the values taken out.
-static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const long long *ho_colptr, const int *ho_rowidx, double *ho_val)
+// The upload in three parts, shared by the host route (set_matrix_impl) and the device route (nnlm_set_matrix_device):
+// matrix_alloc -- the resident buffers, zeroed; a fill -- the host chunk loop below or the device ingest (k_ingest.h), each leaving A,
+// miss and the three sums of the prep pass; matrix_finish -- everything that follows from them.
+static int matrix_alloc(nnlm_handle *h, int n, int m)
 {
-    const bool ho = ho_colptr != nullptr;
     HIPCHK(h, hipSetDevice(h->device));
     free_factors(h);
     free_matrix(h);
@@ -831,6 +833,21 @@ static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const 
     const size_t prep_blocks = (size_t)gx * PREP_GRID_Y;
     h->partials_elems = 3 * (err_blocks > 2 * prep_blocks ? err_blocks : 2 * prep_blocks) + 64; // (two slots of prep partial sums)
     HIPCHK(h, hipMalloc(&h->partials, h->partials_elems * sizeof(double)));
+    return NNLM_OK;
+}
+
+static int matrix_finish(nnlm_handle *h, double cnt, double klc, double over);
+
+// nnlm_set_matrix and nnlm_set_matrix_holdout: one upload.  ho_colptr / ho_rowidx (validated by the caller, NULL for a plain upload):
+// the held-out pattern.  Every chunk of columns then passes through a host staging buffer in which A is checked to be finite and the
+// pattern's entries are replaced by NaN before the DMA -- prep_convert_kernel sees exactly what it sees for a matrix that arrived with
+// NaN there, so the resident state is that upload's bit for bit, and no second n x m array exists anywhere.  ho_val[e]: the values taken out.
+static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const long long *ho_colptr, const int *ho_rowidx, double *ho_val)
+{
+    const bool ho = ho_colptr != nullptr;
+    if (const int rc_alloc = matrix_alloc(h, n, m)) return rc_alloc;
+    const int gx = h->npad / PREP_BLOCK;
+    const size_t prep_blocks = (size_t)gx * PREP_GRID_Y;
 
     // Upload: the caller's matrix is pageable host memory (R's heap, a numpy array).  hipMemcpy from pageable memory stages through
     // ONE runtime thread (4.3 GB/s measured: 0.37 s of a 0.7 s nnmf() call of 500 iterations at config 2).  Here: chunks of whole
@@ -946,9 +963,9 @@ static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const 
         dim3 grid(gx, PREP_GRID_Y);
         double *part = h->partials + (size_t)slot * 3 * prep_blocks;
         if (h->prec == NNLM_PREC_F64)
-            prep_convert_kernel<double><<<grid, PREP_BLOCK, 0, h->stream>>>(stage[slot], n, cols, j0, (double *)h->A, h->npad, h->miss, part);
+            prep_convert_kernel<double><<<grid, PREP_BLOCK, 0, h->stream>>>(stage[slot], (size_t)n, (size_t)1, n, cols, j0, (double *)h->A, h->npad, h->miss, part);
         else
-            prep_convert_kernel<float><<<grid, PREP_BLOCK, 0, h->stream>>>(stage[slot], n, cols, j0, (float *)h->A, h->npad, h->miss, part);
+            prep_convert_kernel<float><<<grid, PREP_BLOCK, 0, h->stream>>>(stage[slot], (size_t)n, (size_t)1, n, cols, j0, (float *)h->A, h->npad, h->miss, part);
         e = hipMemcpyAsync(hp[slot], part, 3 * prep_blocks * sizeof(double), hipMemcpyDeviceToHost, h->stream);
         if (e == hipSuccess) e = hipEventRecord(ev_done[slot], h->stream);
         if (e != hipSuccess) { rc = fail(h, NNLM_ERR_HIP, "prep pass failed: %s", hipGetErrorString(e)); break; }
@@ -970,6 +987,14 @@ static int set_matrix_impl(nnlm_handle *h, const double *A, int n, int m, const 
         if (ho) free_matrix(h);
         return rc;
     }
+    return matrix_finish(h, cnt, klc, over);
+}
+
+// The common tail of an upload: cnt / klc / over = the prep pass's sums over the whole matrix (finite entries, the constant KL part, finite
+// entries beyond the range of the fp32 resident copy).
+static int matrix_finish(nnlm_handle *h, double cnt, double klc, double over)
+{
+    const int n = h->n, m = h->m;
     if (over > 0.0) {
         free_matrix(h);
         return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f finite entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
@@ -1018,6 +1043,177 @@ extern "C" int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m)
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_set_matrix: handle is NULL");
     if (!A || n <= 0 || m <= 0) return fail(h, NNLM_ERR_ARG, "nnlm_set_matrix: A must be a non-empty n x m matrix (n=%d, m=%d)", n, m);
     return set_matrix_impl(h, A, n, m, nullptr, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------
+// matrices and factors in device memory
+// ---------------------------------------------------------------------------------------------
+static size_t dt_size(int dt) { return dt == NNLM_DT_F64 ? 8 : (dt == NNLM_DT_F32 ? 4 : 2); }
+
+// The handle's matrix and factor allocations, which a caller's buffer may not be (base = start of the allocation the caller's pointer
+// lies in).  Best effort: the matrix, its copies and bit matrices, the factor masters, operand copies and masks -- not every workspace --,
+// and only where hipMemGetAddressRange can name the allocation.
+static bool owns_allocation(const nnlm_handle *h, const void *base)
+{
+    const void *mine[] = {h->A, h->AT, h->miss, h->missT, h->A16, h->A16T, h->partials, h->W64b[0], h->W64b[1], h->Wopb[0], h->Wopb[1], h->H64,
+                          h->Hkq, h->Wmask, h->Hmask, h->Y16, h->W16c, h->H16c, h->Cx, h->red, h->gslabs, h->sg_slabs, h->What, h->What64,
+                          h->sp_cptr, h->sp_rptr, h->sp_ridx, h->sp_cidx, h->sp_cval, h->sp_rval, h->sp_Y, h->bG, h->ho_val};
+    for (const void *p : mine)
+        if (p && p == base) return true;
+    return false;
+}
+
+// Everything that can be known about a descriptor before a kernel touches its pointer: rows x cols elements, `name` = the argument.
+static int dev_matrix_check(nnlm_handle *h, const char *who, const char *name, const nnlm_dev_matrix *d, int rows, int cols, bool output)
+{
+    if (!d->ptr) return fail(h, NNLM_ERR_ARG, "%s: %s.ptr is NULL", who, name);
+    if (d->dtype < NNLM_DT_F64 || d->dtype > NNLM_DT_BF16) return fail(h, NNLM_ERR_ARG, "%s: %s.dtype = %d is not one of NNLM_DT_F64 .. NNLM_DT_BF16", who, name, d->dtype);
+    if (output && d->dtype > NNLM_DT_F32)
+        return fail(h, NNLM_ERR_ARG, "%s: %s.dtype = %d: the output types are NNLM_DT_F64 and NNLM_DT_F32 (F16 / BF16 are input types only)", who, name, d->dtype);
+    if (d->row_stride < 1 || d->col_stride < 1)
+        return fail(h, NNLM_ERR_ARG, "%s: the strides of %s must be positive (row_stride = %lld, col_stride = %lld): broadcast and reversed views are "
+                                     "not accepted", who, name, d->row_stride, d->col_stride);
+    const bool col_major = d->col_stride / rows >= d->row_stride && d->col_stride >= (long long)rows * d->row_stride;
+    const bool row_major = d->row_stride / cols >= d->col_stride && d->row_stride >= (long long)cols * d->col_stride;
+    if (!col_major && !row_major)
+        return fail(h, NNLM_ERR_ARG, "%s: the layout of %s overlaps itself (%d x %d, row_stride = %lld, col_stride = %lld): one stride must span "
+                                     "the whole extent of the other dimension", who, name, rows, cols, d->row_stride, d->col_stride);
+    const size_t es = dt_size(d->dtype);
+    if ((uintptr_t)d->ptr % es) return fail(h, NNLM_ERR_ARG, "%s: %s.ptr is not aligned to its %zu-byte elements", who, name, es);
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, d->ptr);
+    (void)hipGetLastError(); // (the query leaves a sticky error behind for a pointer the runtime does not know)
+    if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+        return fail(h, NNLM_ERR_ARG, "%s: %s.ptr is not device (or managed) memory -- a host pointer?", who, name);
+    if (at.type == hipMemoryTypeDevice && at.device != h->device)
+        return fail(h, NNLM_ERR_ARG, "%s: %s lives on device %d, the handle on device %d", who, name, at.device, h->device);
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(d->ptr)) == hipSuccess) {
+        const size_t span = ((size_t)(rows - 1) * (size_t)d->row_stride + (size_t)(cols - 1) * (size_t)d->col_stride + 1) * es;
+        if ((const char *)d->ptr + span > (const char *)base + size)
+            return fail(h, NNLM_ERR_ARG, "%s: %s (%d x %d with its strides) reaches %zu bytes past the end of its allocation", who, name, rows, cols,
+                        (size_t)(((const char *)d->ptr + span) - ((const char *)base + size)));
+        if (owns_allocation(h, base)) return fail(h, NNLM_ERR_ARG, "%s: %s aliases a buffer of the handle itself", who, name);
+    } else
+        (void)hipGetLastError();
+    return NNLM_OK;
+}
+
+// `waiter` continues behind everything enqueued on `producer` so far: an event, no host wait
+static int stream_after(nnlm_handle *h, hipStream_t waiter, hipStream_t producer)
+{
+    hipEvent_t ev = nullptr;
+    HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, producer);
+    if (e == hipSuccess) e = hipStreamWaitEvent(waiter, ev, 0);
+    hipEventDestroy(ev); // (released by the runtime once the recorded work has passed it)
+    if (e != hipSuccess) return fail(h, NNLM_ERR_HIP, "stream ordering (event record / wait) failed: %s", hipGetErrorString(e));
+    return NNLM_OK;
+}
+
+// The device fill of an upload: A in the caller's type S and strides -> h->A (T), h->miss and the prep pass's three sums.
+//   row_stride == 1: ingest_cols_kernel over the host route's column chunks and (gx, 64) grid; the per-block partial sums of all chunks come
+//                    back in one copy and are added chunk by chunk, block by block -- the host route's order, hence its kl_const bit for bit;
+//   col_stride == 1: ingest_rows_kernel (the transposition through LDS);
+//   otherwise:       ingest_gather_kernel over the same chunks.
+template <typename S, typename T>
+static int ingest_fill(nnlm_handle *h, const nnlm_dev_matrix *d, double sums[3])
+{
+    const int n = h->n, m = h->m;
+    const S *src = (const S *)d->ptr;
+    T *dst = (T *)h->A;
+    const bool rows_route = d->col_stride == 1 && d->row_stride != 1;
+    const int tiles_j = (m + INGEST_TILE - 1) / INGEST_TILE;
+    const dim3 grid_r(h->npad / INGEST_TILE, tiles_j < INGEST_GRID_Y ? tiles_j : INGEST_GRID_Y);
+    int cols_per_chunk = (int)(((size_t)64 << 20) / ((size_t)n * 8)); // (the host route's chunks: set_matrix_impl)
+    if (cols_per_chunk < 1) cols_per_chunk = 1;
+    if (cols_per_chunk > m) cols_per_chunk = m;
+    const int gx = h->npad / PREP_BLOCK;
+    const size_t prep_blocks = (size_t)gx * PREP_GRID_Y;
+    const size_t chunks = ((size_t)m + cols_per_chunk - 1) / cols_per_chunk;
+    const size_t blocks = rows_route ? (size_t)grid_r.x * grid_r.y : chunks * prep_blocks;
+    double *part = nullptr;
+    HIPCHK(h, hipMalloc(&part, 3 * blocks * sizeof(double)));
+    if (rows_route) {
+        ProfScope ps(h, P_INGEST);
+        const int vec = ((uintptr_t)src % 16 == 0 && ((size_t)d->row_stride * sizeof(S)) % 16 == 0) ? 1 : 0;
+        ingest_rows_kernel<S, T><<<grid_r, 256, 0, h->stream>>>(src, (size_t)d->row_stride, vec, n, m, dst, h->npad, h->miss, part);
+    } else {
+        ProfScope ps(h, P_INGEST);
+        const dim3 grid(gx, PREP_GRID_Y);
+        size_t c = 0;
+        for (int j0 = 0; j0 < m; j0 += cols_per_chunk, c++) {
+            const int cols = (m - j0 < cols_per_chunk) ? m - j0 : cols_per_chunk;
+            const S *s0 = src + (size_t)j0 * (size_t)d->col_stride;
+            double *pc = part + 3 * c * prep_blocks;
+            if (d->row_stride == 1) // ingest_cols_kernel<S, T>
+                prep_convert_kernel<T, S, false><<<grid, PREP_BLOCK, 0, h->stream>>>(s0, (size_t)d->col_stride, (size_t)1, n, cols, j0, dst, h->npad, h->miss, pc);
+            else // ingest_gather_kernel<S, T>
+                prep_convert_kernel<T, S, true><<<grid, PREP_BLOCK, 0, h->stream>>>(s0, (size_t)d->col_stride, (size_t)d->row_stride, n, cols, j0, dst, h->npad, h->miss, pc);
+        }
+    }
+    std::vector<double> hp;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) {
+        try {
+            hp.resize(3 * blocks);
+        } catch (...) {
+            hipStreamSynchronize(h->stream);
+            hipFree(part);
+            return fail(h, NNLM_ERR_HIP, "nnlm_set_matrix_device: host buffer for %zu partial sums", 3 * blocks);
+        }
+        e = hipMemcpyAsync(hp.data(), part, 3 * blocks * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    }
+    const hipError_t e2 = hipStreamSynchronize(h->stream);
+    hipFree(part);
+    if (e != hipSuccess || e2 != hipSuccess) return fail(h, NNLM_ERR_HIP, "ingest pass failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+    double cnt = 0.0, klc = 0.0, over = 0.0;
+    for (size_t q = 0; q < blocks; q++) {
+        cnt += hp[3 * q];
+        klc += hp[3 * q + 1];
+        over += hp[3 * q + 2];
+    }
+    sums[0] = cnt, sums[1] = klc, sums[2] = over;
+    return NNLM_OK;
+}
+
+// f(S{}) for the source type of a descriptor
+template <typename F>
+static int with_dtype(int dtype, F &&f)
+{
+    switch (dtype) {
+    case NNLM_DT_F64: return f(double{});
+    case NNLM_DT_F32: return f(float{});
+    case NNLM_DT_F16: return f(nnlm_f16{});
+    default: return f(nnlm_bf16{});
+    }
+}
+
+extern "C" int nnlm_set_matrix_device(nnlm_handle *h, const nnlm_dev_matrix *A, int n, int m, void *stream)
+{
+    const char *who = "nnlm_set_matrix_device";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!A || n <= 0 || m <= 0) return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix (n=%d, m=%d)", who, n, m);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = dev_matrix_check(h, who, "A", A, n, m, false);
+    if (rc != NNLM_OK) return rc;
+    if ((rc = matrix_alloc(h, n, m)) != NNLM_OK) return rc;
+    if ((rc = stream_after(h, h->stream, (hipStream_t)stream)) != NNLM_OK) { // the caller's stream produced A
+        free_matrix(h);
+        return rc;
+    }
+    double sums[3] = {0.0, 0.0, 0.0};
+    rc = with_dtype(A->dtype, [&](auto s) {
+        typedef decltype(s) S;
+        return h->prec == NNLM_PREC_F64 ? ingest_fill<S, double>(h, A, sums) : ingest_fill<S, float>(h, A, sums);
+    });
+    if (rc != NNLM_OK) {
+        free_matrix(h);
+        return rc;
+    }
+    return matrix_finish(h, sums[0], sums[1], sums[2]);
 }
 
 // Dense finite A with a hold-out pattern (include/nnlm_mi355x.h)
@@ -1399,8 +1595,10 @@ static void pack_mask_cols(const int *mask, int k, int ncols, bool transposed_in
         }
 }
 
+// Setting factors in three parts, shared by the host route (set_factors_impl) and the device route (nnlm_set_factors_device):
+// factors_alloc -- cache invalidation, buffers and workspaces of rank k; a fill of W64 / H64 / Wop; factors_masks.
 // row_pad: zero rows behind the KP rows of the masters W64b / H64 (a batched factorisation reads up to 63 rows past a member's last)
-static int set_factors_impl(nnlm_handle *h, int k, const double *W, const double *H, const int *Wm, const int *Hm, int row_pad)
+static int factors_alloc(nnlm_handle *h, int k, int row_pad)
 {
     HIPCHK(h, hipSetDevice(h->device));
     sync_all(h);
@@ -1466,6 +1664,29 @@ static int set_factors_impl(nnlm_handle *h, int k, const double *W, const double
     h->sg_which = h->sg_other = -1;
     h->sw_active = 0;
     HIPCHK(h, hipMemset(h->sweeps, 0, 2 * sizeof(unsigned long long)));
+    return NNLM_OK;
+}
+
+static int factors_masks(nnlm_handle *h, int k, const int *Wm, const int *Hm)
+{
+    const int n = h->n, m = h->m, npad = h->npad, mpad = h->mpad;
+    std::vector<unsigned long long> mk;
+    h->has_wmask = Wm != nullptr;
+    h->has_hmask = Hm != nullptr;
+    if (Wm) {
+        pack_mask_cols(Wm, k, n, true, n, mk, npad, h->MW);
+        HIPCHK(h, hipMemcpy(h->Wmask, mk.data(), (size_t)npad * h->MW * 8, hipMemcpyHostToDevice));
+    }
+    if (Hm) {
+        pack_mask_cols(Hm, k, m, false, k, mk, mpad, h->MW);
+        HIPCHK(h, hipMemcpy(h->Hmask, mk.data(), (size_t)mpad * h->MW * 8, hipMemcpyHostToDevice));
+    }
+    return NNLM_OK;
+}
+
+static int set_factors_impl(nnlm_handle *h, int k, const double *W, const double *H, const int *Wm, const int *Hm, int row_pad)
+{
+    if (const int rc = factors_alloc(h, k, row_pad)) return rc;
     const int KP = h->KP, n = h->n, m = h->m, npad = h->npad, mpad = h->mpad;
     // host-side repack into the padded resident layouts (k*(n+m) elements: negligible)
     std::vector<double> w64((size_t)KP * npad, 0.0), h64((size_t)KP * mpad, 0.0);
@@ -1482,18 +1703,7 @@ static int set_factors_impl(nnlm_handle *h, int k, const double *W, const double
         for (size_t e = 0; e < wop.size(); e++) wop[e] = (float)w64[e];
         HIPCHK(h, hipMemcpy(h->Wop, wop.data(), wop.size() * 4, hipMemcpyHostToDevice));
     }
-    std::vector<unsigned long long> mk;
-    h->has_wmask = Wm != nullptr;
-    h->has_hmask = Hm != nullptr;
-    if (Wm) {
-        pack_mask_cols(Wm, k, n, true, n, mk, npad, h->MW);
-        HIPCHK(h, hipMemcpy(h->Wmask, mk.data(), (size_t)npad * h->MW * 8, hipMemcpyHostToDevice));
-    }
-    if (Hm) {
-        pack_mask_cols(Hm, k, m, false, k, mk, mpad, h->MW);
-        HIPCHK(h, hipMemcpy(h->Hmask, mk.data(), (size_t)mpad * h->MW * 8, hipMemcpyHostToDevice));
-    }
-    return NNLM_OK;
+    return factors_masks(h, k, Wm, Hm);
 }
 
 extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, const double *H, const int *Wm, const int *Hm)
@@ -1524,6 +1734,94 @@ extern "C" int nnlm_get_factors(nnlm_handle *h, double *W, double *H)
         for (int j = 0; j < m; j++)
             for (int q = 0; q < k; q++) H[(size_t)j * k + q] = h64[(size_t)q * mpad + j];
     }
+    return NNLM_OK;
+}
+
+// Factors from device memory: W n x k, H k x m in the caller's type and strides (NULL = zeros); masks are host arrays.
+extern "C" int nnlm_set_factors_device(nnlm_handle *h, unsigned k_, const nnlm_dev_matrix *W, const nnlm_dev_matrix *H, const int *Wm, const int *Hm,
+                                       void *stream)
+{
+    const char *who = "nnlm_set_factors_device";
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "%s: set the matrix first", who);
+    const int k = (int)k_;
+    if (k < 1) return fail(h, NNLM_ERR_ARG, "%s: rank k must be >= 1", who);
+    if (h->sparse && h->sp_missing && k > NNLM_KQ_MAX)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%s: rank %d on a sparse matrix whose absent entries are missing: the rank is at most %d", who, k, NNLM_KQ_MAX);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = NNLM_OK;
+    if (W && (rc = dev_matrix_check(h, who, "W", W, h->n, k, false)) != NNLM_OK) return rc;
+    if (H && (rc = dev_matrix_check(h, who, "H", H, k, h->m, false)) != NNLM_OK) return rc;
+    if ((rc = factors_alloc(h, k, 0)) != NNLM_OK) return rc;
+    if ((rc = stream_after(h, h->stream, (hipStream_t)stream)) != NNLM_OK) return rc; // the caller's stream produced W and H
+    float *wop = h->prec == NNLM_PREC_F64 ? nullptr : (float *)h->Wop;
+    dim3 gw(h->npad / 256, h->KP), gh((h->mpad + 255) / 256, h->KP);
+    // W n x k: (c = i, q) at ptr[i row_stride + q col_stride]; H k x m: (c = j, q) at ptr[q row_stride + j col_stride]
+    with_dtype(W ? W->dtype : NNLM_DT_F64, [&](auto s) {
+        typedef decltype(s) S;
+        factor_ingest_kernel<S><<<gw, 256, 0, h->stream>>>(W ? (const S *)W->ptr : nullptr, W ? W->row_stride : 0, W ? W->col_stride : 0, h->n, k, h->W64, wop, h->npad);
+        return 0;
+    });
+    with_dtype(H ? H->dtype : NNLM_DT_F64, [&](auto s) {
+        typedef decltype(s) S;
+        factor_ingest_kernel<S><<<gh, 256, 0, h->stream>>>(H ? (const S *)H->ptr : nullptr, H ? H->col_stride : 0, H ? H->row_stride : 0, h->m, k, h->H64, nullptr, h->mpad);
+        return 0;
+    });
+    LAUNCHCHK(h);
+    HIPCHK(h, hipStreamSynchronize(h->stream)); // (where nnlm_set_factors' copies wait: the caller's buffers are free again on return)
+    return factors_masks(h, k, Wm, Hm);
+}
+
+// The current factors into the caller's device buffers (F64 or F32, any non-overlapping strides; NULL = not wanted).  No host wait: the
+// export runs on the handle's stream behind the caller's earlier work, and the caller's stream continues behind the export.
+extern "C" int nnlm_get_factors_device(nnlm_handle *h, const nnlm_dev_matrix *W, const nnlm_dev_matrix *H, void *stream)
+{
+    const char *who = "nnlm_get_factors_device";
+    if (!h || !h->W64) return fail(h, NNLM_ERR_ARG, "%s: no factors set", who);
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = NNLM_OK;
+    if (W && (rc = dev_matrix_check(h, who, "W", W, h->n, h->k, true)) != NNLM_OK) return rc;
+    if (H && (rc = dev_matrix_check(h, who, "H", H, h->k, h->m, true)) != NNLM_OK) return rc;
+    if ((rc = stream_after(h, h->stream, h->stream_e)) != NNLM_OK) return rc;
+    if ((rc = stream_after(h, h->stream, (hipStream_t)stream)) != NNLM_OK) return rc; // the caller's earlier use of the buffers
+    if (W) {
+        dim3 g((h->n + 255) / 256, h->k);
+        if (W->dtype == NNLM_DT_F64) factor_export_kernel<double><<<g, 256, 0, h->stream>>>(h->W64, h->npad, h->n, (double *)W->ptr, W->row_stride, W->col_stride);
+        else factor_export_kernel<float><<<g, 256, 0, h->stream>>>(h->W64, h->npad, h->n, (float *)W->ptr, W->row_stride, W->col_stride);
+    }
+    if (H) {
+        dim3 g((h->m + 255) / 256, h->k);
+        if (H->dtype == NNLM_DT_F64) factor_export_kernel<double><<<g, 256, 0, h->stream>>>(h->H64, h->mpad, h->m, (double *)H->ptr, H->col_stride, H->row_stride);
+        else factor_export_kernel<float><<<g, 256, 0, h->stream>>>(h->H64, h->mpad, h->m, (float *)H->ptr, H->col_stride, H->row_stride);
+    }
+    LAUNCHCHK(h);
+    return stream_after(h, (hipStream_t)stream, h->stream);
+}
+
+// nnlm_get_info "matrix_min_col_observed" / "matrix_min_row_observed": on first query, cached with the matrix
+static int observed_min(nnlm_handle *h, int which, double *value)
+{
+    if (h->sparse || !h->A) {
+        *value = -1.0;
+        return NNLM_OK;
+    }
+    if (h->min_obs[0] == -2) {
+        if (!h->any_missing) h->min_obs[0] = h->n, h->min_obs[1] = h->m;
+        else {
+            HIPCHK(h, hipSetDevice(h->device));
+            int *out = nullptr, init[2] = {INT_MAX, INT_MAX}, res[2] = {0, 0};
+            HIPCHK(h, hipMalloc(&out, sizeof init));
+            hipError_t e = hipMemcpyAsync(out, init, sizeof init, hipMemcpyHostToDevice, h->stream);
+            observed_min_kernel<<<(h->m + 3) / 4, 256, 0, h->stream>>>(h->miss, h->m, h->npad / 32, h->n, out);
+            observed_min_kernel<<<(h->n + 3) / 4, 256, 0, h->stream>>>(h->missT, h->n, h->mpad / 32, h->m, out + 1);
+            if (e == hipSuccess) e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(res, out, sizeof res, hipMemcpyDeviceToHost, h->stream);
+            const hipError_t e2 = hipStreamSynchronize(h->stream);
+            hipFree(out);
+            if (e != hipSuccess || e2 != hipSuccess) return fail(h, NNLM_ERR_HIP, "observed_min_kernel failed: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+            h->min_obs[0] = res[0], h->min_obs[1] = res[1];
+        }
+    }
+    *value = h->min_obs[which];
     return NNLM_OK;
 }
 
@@ -3297,6 +3595,8 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
     else if (strcmp(key, "matrix_holdout") == 0) *value = h->holdout ? (double)h->ho_nnz : -1.0;
     else if (strcmp(key, "matrix_bytes") == 0) *value = matrix_bytes(h);
+    else if (strcmp(key, "matrix_min_col_observed") == 0) return observed_min(h, 0, value);
+    else if (strcmp(key, "matrix_min_row_observed") == 0) return observed_min(h, 1, value);
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
     else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
