@@ -186,6 +186,27 @@ int nnlm_set_matrix_holdout(nnlm_handle *h, const double *A, int n, int m, const
  * - a + wh, for the B members of a batch (arrays of length B) or the solo factors (length 1).  fp64 sums in a fixed order, no
  * atomics; synchronises.  An empty hold-out set gives NaN for both; NNLM_ERR_ARG on a handle without a hold-out set. */
 int nnlm_holdout_errors(nnlm_handle *h, double *mse, double *mkl);
+/* ------------------------------------------------------------------------------------------
+ * Scores of the current factors without forming W H.  Both entries run on a handle that holds a matrix (any kind: it gives n and m)
+ * and solo factors; both read the fp64 masters of the factors, so a score is the same in both arithmetic modes, at any rank (beyond 64
+ * included); both synchronise.  Their workspaces live for the call and are processed in rounds: nothing n x m or n_lines x n sized is
+ * allocated.  NNLM_ERR_UNSUPPORTED: a handle with batched factors or a communicator.  NNLM_ERR_ARG: no matrix or no factors set.
+ * ---------------------------------------------------------------------------------------- */
+/* out[e] = sum_q W[rows[e], q] * H[q, cols[e]], fp64, q ascending.  rows / cols: host int32, 0-based, count >= 0 (count = 0 succeeds and
+ * writes nothing).  NNLM_ERR_ARG names an index out of range. */
+int nnlm_predict_entries(nnlm_handle *h, long long count, const int *rows, const int *cols, double *out);
+/* by = 0: for every listed column j, the n_top rows i with the largest (W H)[i, j]; by = 1: for every listed row i, the n_top columns.
+ * lines: host int32[n_lines] (NULL = all lines of that side, n_lines ignored).  exclude = 1: entries STORED in the resident sparse
+ * matrix (either absent semantics) are not candidates.  idx_out: int32[n_lines][n_top], score_out: double[n_lines][n_top].
+ * Results come in descending score order and EQUAL SCORES IN ASCENDING INDEX ORDER: (score descending, index ascending) is a total order,
+ * so the result is a function of the scores alone, and the bits of a score are a function of (i, j, W, H) alone -- neither depends on
+ * the lines asked for, the device's size or how the candidates were sliced.  A line with fewer than n_top candidates is padded with index
+ * -1 and score NaN; a NaN score is never selected.  1 <= n_top <= 128.
+ * NNLM_ERR_UNSUPPORTED: n_top > 128; exclude = 1 on a handle whose matrix is not sparse.  NNLM_ERR_ARG: a line out of range, n_top < 1,
+ * by / exclude outside {0, 1}.  nnlm_profile_get names: "topn", "topn_merge" ("predict_entries" for the entry above);
+ * nnlm_get_info "topn_slices": candidate slices of the last launch. */
+int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, long long n_lines, int exclude, int *idx_out, double *score_out);
+
 /* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag.  Sparse A: n m and 0, and kl_const counts
  * the zeros ((n m - nnz) eps log eps); absent entries missing (nnlm_set_matrix_csc_missing): nnz and (nnz < n m). */
 int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const);

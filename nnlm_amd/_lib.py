@@ -38,7 +38,10 @@ EXPORTS = [
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
     "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
+    "nnlm_predict_entries", "nnlm_top_n",
 ]
+TOPN_MAX = 128  # largest n_top of nnlm_top_n
+BY = {"column": 0, "row": 1}
 
 
 class NnlmError(RuntimeError):
@@ -184,6 +187,10 @@ def load():
     lib.nnlm_set_factors_device.argtypes = [vp, C.c_uint, dmp, dmp, ip, ip, vp]
     lib.nnlm_get_factors_device.restype = C.c_int
     lib.nnlm_get_factors_device.argtypes = [vp, dmp, dmp, vp]
+    lib.nnlm_predict_entries.restype = C.c_int
+    lib.nnlm_predict_entries.argtypes = [vp, C.c_longlong, ip, ip, dp]
+    lib.nnlm_top_n.restype = C.c_int
+    lib.nnlm_top_n.argtypes = [vp, C.c_int, C.c_int, ip, C.c_longlong, C.c_int, ip, dp]
     _lib = lib
     return lib
 
@@ -229,6 +236,25 @@ def _csc_arrays(indptr, indices, data):
     (nnlm_set_matrix_csc checks it: canonicalisation is the caller's, see api.as_csc)."""
     return (np.ascontiguousarray(indptr, dtype=np.int64), np.ascontiguousarray(indices, dtype=np.int32),
             np.ascontiguousarray(data, dtype=np.float64))
+
+
+def index_array(x, name):
+    """A one-dimensional array of integers as contiguous int32 (ValueError for any other dtype, a value beyond int32 or another shape);
+    the range against n / m is the library's check."""
+    a = np.asarray(x)
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be a one-dimensional array of integers (got shape {a.shape})")
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must hold integers (got dtype {a.dtype})")
+    if a.size and (int(a.max()) > np.iinfo(np.int32).max or int(a.min()) < np.iinfo(np.int32).min):
+        raise ValueError(f"{name} holds an index beyond 32 bits")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def by_code(by):
+    if by not in BY:
+        raise ValueError(f"by must be 'column' or 'row' (got {by!r})")
+    return BY[by]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -671,6 +697,27 @@ class Handle:
         mse, mkl = np.zeros(B), np.zeros(B)
         self._ck(self._lib.nnlm_holdout_errors(self._h, _dp(mse), _dp(mkl)))
         return mse, mkl
+
+    def predict_entries(self, rows, cols):
+        """(W H)[rows[e], cols[e]] of the current factors as a float64 array; W H is never formed."""
+        r, c = index_array(rows, "rows"), index_array(cols, "cols")
+        if r.size != c.size:
+            raise ValueError(f"rows and cols must have the same length (got {r.size} and {c.size})")
+        out = np.zeros(r.size)
+        self._ck(self._lib.nnlm_predict_entries(self._h, r.size, _ip(r), _ip(c), _dp(out)))
+        return out
+
+    def top_n(self, n_top, by="column", lines=None, exclude=False):
+        """(idx int32 [L, n_top], score float64 [L, n_top]): per listed column (by = "column": the best rows) or row (by = "row": the
+        best columns) of W H, best first, equal scores by ascending index, (-1, NaN) behind a line with fewer candidates.  lines = None:
+        every line of that side.  exclude: the entries stored in the handle's sparse matrix are not candidates."""
+        code, n_top = by_code(by), int(n_top)
+        ln = None if lines is None else index_array(lines, "lines")
+        L = (self.m if code == 0 else self.n) if ln is None else ln.size
+        width = min(max(n_top, 0), TOPN_MAX)  # (an n_top out of range is the library's refusal: nothing is written then)
+        idx, score = np.full((L, width), -1, dtype=np.int32), np.full((L, width), np.nan)
+        self._ck(self._lib.nnlm_top_n(self._h, code, n_top, _ip(ln), L, int(bool(exclude)), _ip(idx), _dp(score)))
+        return idx, score
 
     def matrix_info(self):
         nn, am, kc = C.c_double(0), C.c_int(0), C.c_double(0)

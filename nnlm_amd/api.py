@@ -864,3 +864,80 @@ def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=
         out["coefficients"] = np.asarray(out["coefficients"]).T
         return out
     return solver(object["W"], nd, method=method, loss=loss, **kw)
+
+
+# ------------------------------------------------------------------------------------------------
+# scores of a fit without forming W H (nnlm_predict_entries / nnlm_top_n)
+# ------------------------------------------------------------------------------------------------
+def _fit_factors(fit, who):
+    """Host W (n x k) and H (k x m) of an nnmf() result, checked against each other."""
+    for key in ("W", "H"):
+        _refuse_device(fit[key], who, "fit$" + key)
+    W, H = np.asarray(fit["W"], dtype=np.float64), np.asarray(fit["H"], dtype=np.float64)
+    if W.ndim != 2 or H.ndim != 2 or W.shape[1] != H.shape[0] or W.shape[1] < 1:
+        raise NnlmStop("%s: fit must hold W (n x k) and H (k x m) of one rank k >= 1 (got %s and %s)." % (who, W.shape, H.shape))
+    return W, H
+
+
+def _index_arg(x, name, limit):
+    try:
+        a = _lib.index_array(x, name)
+    except ValueError as e:
+        raise NnlmStop(str(e)) from None
+    if a.size and (a.min() < 0 or a.max() >= limit):
+        raise NnlmStop("%s holds an index out of range (0 .. %d)." % (name, limit - 1))
+    return a
+
+
+def _scoring_handle(W, H, pattern, precision):
+    """A handle that knows n, m and the factors.  Its matrix is the cheapest the library takes: a sparse one with the given stored
+    pattern (values 1; only the pattern is ever read) -- the EMPTY n x m pattern when there is none, m + 1 column pointers."""
+    n, m = W.shape[0], H.shape[1]
+    h = _lib.Handle(int(os.environ.get("NNLM_DEVICE", "0") or 0), _env_precision() if precision is None else precision)
+    try:
+        if pattern is None:
+            h.set_matrix_csc(np.zeros(m + 1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0), (n, m))
+        else:
+            h.set_matrix_csc(pattern.indptr, pattern.indices, np.ones(pattern.indices.size), (n, m))
+        h.set_factors(W.shape[1], W, H)
+    except BaseException:
+        h.close()
+        raise
+    return h
+
+
+def predict_entries(fit, rows, cols, precision=None):
+    """(W H)[rows[e], cols[e]] of an nnmf() result as a float64 array, computed on the device from the factors alone: W H is never
+    formed.  rows / cols: integer arrays of equal length, 0-based.  The scores are fp64 sums in both arithmetic modes (``precision``:
+    nnlm_amd.PREC_F32 / PREC_F64, default NNLM_PRECISION's)."""
+    W, H = _fit_factors(fit, "predict_entries")
+    r, c = _index_arg(rows, "rows", W.shape[0]), _index_arg(cols, "cols", H.shape[1])
+    if r.size != c.size:
+        raise NnlmStop("rows and cols must have the same length (got %d and %d)." % (r.size, c.size))
+    with _scoring_handle(W, H, None, precision) as h:
+        return h.predict_entries(r, c)
+
+
+def top_n(fit, n_top, by="column", lines=None, seen=None):
+    """The n_top best-scoring rows of every listed column of W H (by = "column") or columns of every listed row (by = "row"), from the
+    factors alone: (idx int32 [L, n_top], score float64 [L, n_top]), best first, equal scores by ascending index, (-1, NaN) behind a line
+    with fewer candidates.  lines = None: every line of that side.  ``seen``: an object with tocsc() of the shape of W H -- typically the
+    training matrix -- whose STORED entries are not candidates (stored zeros included); without it nothing is excluded."""
+    W, H = _fit_factors(fit, "top_n")
+    n, m = W.shape[0], H.shape[1]
+    if by not in _lib.BY:
+        raise NnlmStop("by must be 'column' or 'row' (got %r)." % (by,))
+    n_top = int(n_top)
+    if not 1 <= n_top <= _lib.TOPN_MAX:
+        raise NnlmStop("n_top must be in 1 .. %d (got %d)." % (_lib.TOPN_MAX, n_top))
+    ln = None if lines is None else _index_arg(lines, "lines", m if by == "column" else n)
+    pattern = None
+    if seen is not None:
+        _refuse_device(seen, "top_n", "seen")
+        if not is_sparse(seen):
+            raise NnlmStop("seen must be a sparse matrix (an object with tocsc()): its stored entries are what is excluded.")
+        if tuple(int(v) for v in seen.shape) != (n, m):
+            raise NnlmStop("Dimension of seen %s does not match the fit (%d x %d)." % (tuple(seen.shape), n, m))
+        pattern = as_csc(seen)
+    with _scoring_handle(W, H, pattern, None) as h:
+        return h.top_n(n_top, by=by, lines=ln, exclude=pattern is not None)

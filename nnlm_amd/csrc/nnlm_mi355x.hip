@@ -24,6 +24,7 @@
 #include "k_xprod.h"
 #include "k_xprod16.h"
 #include "tu_sweepq.h"
+#include "tu_topn.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>
@@ -44,7 +45,7 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_COUNT };
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -55,8 +56,10 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  "batch_errors": the error block of a batched factorisation (errors_batch_kernel + its reduction: one pass over A for all members);
 //  "batch_pen": its per-member penalty sums; "sp_gram": the per-column Grams of a sparse A whose absent entries are missing (sp_gram_kernel
 //  + its fix-up, both half-steps); "ingest": the ingest kernels of nnlm_set_matrix_device (k_ingest.h), without the common tail
+//  "topn" / "topn_merge" / "predict_entries": topn_kernel, topn_merge_kernel and predict_entries_kernel alone (k_topn.h; the row copies
+//  and the transfers around them are not in it)
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest"};
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -221,6 +224,8 @@ struct nnlm_handle {
     long long *ho_cptr = nullptr; // [m + 1]
     int *ho_ridx = nullptr, *ho_cidx = nullptr;
     void *ho_val = nullptr;
+
+    int topn_slices = 0; // candidate slices of the last topn_kernel launch (nnlm_get_info "topn_slices")
 
     // profiling
     bool prof = false;
@@ -3602,6 +3607,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
     else if (strcmp(key, "sp_workers") == 0) *value = (h->sparse && h->KP > 0) ? nnlm_sp_workers(h->nnz, h->KP, h->cus_device) : 0;
     else if (strcmp(key, "sp_gram_workers") == 0) *value = h->spg_workers;
+    else if (strcmp(key, "topn_slices") == 0) *value = h->topn_slices;
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
 }
@@ -4281,6 +4287,195 @@ extern "C" int nnlm_holdout_errors(nnlm_handle *h, double *mse, double *mkl)
     if (e != hipSuccess) return fail(h, NNLM_ERR_HIP, "nnlm_holdout_errors failed: %s", hipGetErrorString(e));
     sync_all(h);
     for (int b = 0; b < B; b++) mse[b] = out[2 * b] / (double)nnz, mkl[b] = out[2 * b + 1] / (double)nnz;
+    return NNLM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// scores of the current factors without W H (k_topn.h)
+// ---------------------------------------------------------------------------------------------
+// Device buffers that live for one call
+struct CallBufs {
+    std::vector<void *> p;
+    template <typename T> hipError_t get(T **out, size_t count)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) p.push_back(q);
+        *out = (T *)q;
+        return e;
+    }
+    ~CallBufs()
+    {
+        for (void *q : p) hipFree(q);
+    }
+};
+
+// what both entries ask of the handle; fills K4 and the row copies Wrow [n][K4], Hrow [m][K4] (enqueued on the handle's stream)
+static int score_prepare(nnlm_handle *h, const char *who, CallBufs &bufs, int &K4, double *&Wrow, double *&Hrow)
+{
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (h->bB) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the handle holds the factors of a batch; scores are read from solo factors (nnlm_set_factors)", who);
+    if (h->sharded || h->comm) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the handle has a communicator; scores are read on one GPU", who);
+    if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "%s: no matrix set", who);
+    if (!h->W64 || !h->H64) return fail(h, NNLM_ERR_ARG, "%s: no factors set", who);
+    HIPCHK(h, hipSetDevice(h->device));
+    g_attr_err = hipSuccess;
+    K4 = 4 * ((h->k + 3) / 4);
+    HIPCHK(h, bufs.get(&Wrow, (size_t)h->n * K4));
+    HIPCHK(h, bufs.get(&Hrow, (size_t)h->m * K4));
+    factor_rows_kernel<double><<<(h->n + 255) / 256, 256, 0, h->stream>>>(h->W64, h->npad, h->n, K4, Wrow, h->k);
+    factor_rows_kernel<double><<<(h->m + 255) / 256, 256, 0, h->stream>>>(h->H64, h->mpad, h->m, K4, Hrow, h->k);
+    HIPCHK(h, hipGetLastError());
+    return NNLM_OK;
+}
+
+// a failure between the first launch and the end of the call: the stream is drained before the call's buffers go
+static int score_fail(nnlm_handle *h, const char *who, hipError_t e)
+{
+    (void)hipStreamSynchronize(h->stream);
+    return fail(h, NNLM_ERR_HIP, "%s failed: %s", who, hipGetErrorString(e));
+}
+
+extern "C" int nnlm_predict_entries(nnlm_handle *h, long long count, const int *rows, const int *cols, double *out)
+{
+    const char *who = "nnlm_predict_entries";
+    if (h && count < 0) return fail(h, NNLM_ERR_ARG, "%s: count = %lld", who, count);
+    if (h && count > 0 && (!rows || !cols || !out)) return fail(h, NNLM_ERR_ARG, "%s: rows, cols and out must not be NULL", who);
+    if (h && has_matrix(h))
+        for (long long e = 0; e < count; e++) {
+            if (rows[e] < 0 || rows[e] >= h->n) return fail(h, NNLM_ERR_ARG, "%s: rows[%lld] = %d is out of range (n = %d)", who, e, rows[e], h->n);
+            if (cols[e] < 0 || cols[e] >= h->m) return fail(h, NNLM_ERR_ARG, "%s: cols[%lld] = %d is out of range (m = %d)", who, e, cols[e], h->m);
+        }
+    CallBufs bufs;
+    int K4 = 0;
+    double *Wrow = nullptr, *Hrow = nullptr;
+    if (const int rc = score_prepare(h, who, bufs, K4, Wrow, Hrow); rc != NNLM_OK) {
+        if (h && h->stream) (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    hipStream_t st = h->stream;
+    const long long CH = 1LL << 22; // entries per round: 64 MB of indices and results
+    int *rd = nullptr, *cd = nullptr;
+    double *od = nullptr;
+    const size_t chn = (size_t)(count < CH ? count : CH);
+    hipError_t e = bufs.get(&rd, chn);
+    if (e == hipSuccess) e = bufs.get(&cd, chn);
+    if (e == hipSuccess) e = bufs.get(&od, chn);
+    for (long long e0 = 0; e0 < count && e == hipSuccess; e0 += CH) {
+        const long long ne = count - e0 < CH ? count - e0 : CH;
+        e = hipMemcpyAsync(rd, rows + e0, (size_t)ne * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(cd, cols + e0, (size_t)ne * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) break;
+        {
+            ProfScope ps(h, P_PREDICT_ENTRIES);
+            nnlm_tu_predict_entries(rd, cd, ne, Wrow, Hrow, K4, h->k, od, st);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out + e0, od, (size_t)ne * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // (the round's buffers are reused)
+    }
+    if (e != hipSuccess) return score_fail(h, who, e);
+    sync_all(h);
+    return NNLM_OK;
+}
+
+// candidate slices of a launch over `ngroups` groups of 16 lines: enough wavefronts to fill the device (8 per CU), slices of at least 1024
+// candidates, at most one per lane of topn_merge_kernel; the slice length is a multiple of the 16-candidate tile
+static void topn_slicing(int ngroups, int ncand, int cus, int &nslices, int &slice_len)
+{
+    const long long target = 8LL * (cus > 0 ? cus : 256);
+    long long ns = (target + ngroups - 1) / ngroups;
+    const long long most = ((long long)ncand + 1023) / 1024;
+    if (ns > most) ns = most;
+    if (ns > TOPN_MAX_SLICES) ns = TOPN_MAX_SLICES;
+    if (ns < 1) ns = 1;
+    slice_len = (int)((((long long)ncand + ns - 1) / ns + 15) / 16 * 16);
+    nslices = (ncand + slice_len - 1) / slice_len;
+}
+
+extern "C" int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, long long n_lines, int exclude, int *idx_out, double *score_out)
+{
+    const char *who = "nnlm_top_n";
+    if (h) {
+        if (by != 0 && by != 1) return fail(h, NNLM_ERR_ARG, "%s: by = %d (0: per column, 1: per row)", who, by);
+        if (exclude != 0 && exclude != 1) return fail(h, NNLM_ERR_ARG, "%s: exclude = %d (0 or 1)", who, exclude);
+        if (n_top < 1) return fail(h, NNLM_ERR_ARG, "%s: n_top = %d (1 .. %d)", who, n_top, TOPN_MAX);
+        if (n_top > TOPN_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: n_top = %d, at most %d are selected", who, n_top, TOPN_MAX);
+        if (lines && n_lines < 0) return fail(h, NNLM_ERR_ARG, "%s: n_lines = %lld", who, n_lines);
+        if (!idx_out || !score_out) return fail(h, NNLM_ERR_ARG, "%s: idx_out and score_out must not be NULL", who);
+        if (exclude && has_matrix(h) && !h->sparse)
+            return fail(h, NNLM_ERR_UNSUPPORTED, "%s: exclude = 1 needs a sparse matrix on the handle (its stored entries are what is excluded)", who);
+        if (lines && has_matrix(h)) {
+            const int side = by == 0 ? h->m : h->n;
+            for (long long l = 0; l < n_lines; l++)
+                if (lines[l] < 0 || lines[l] >= side)
+                    return fail(h, NNLM_ERR_ARG, "%s: lines[%lld] = %d is out of range (%s = %d)", who, l, lines[l], by == 0 ? "m" : "n", side);
+        }
+    }
+    CallBufs bufs;
+    int K4 = 0;
+    double *Wrow = nullptr, *Hrow = nullptr;
+    if (const int rc = score_prepare(h, who, bufs, K4, Wrow, Hrow); rc != NNLM_OK) {
+        if (h && h->stream) (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    hipStream_t st = h->stream;
+    const long long L = lines ? n_lines : (by == 0 ? h->m : h->n);
+    const int LCH = 16384; // lines per round (a multiple of the 64 lines of a full workgroup)
+    TopnArgs a{};
+    a.Crow = by == 0 ? Wrow : Hrow;
+    a.Lrow = by == 0 ? Hrow : Wrow;
+    a.ncand = by == 0 ? h->n : h->m;
+    a.K4 = K4;
+    a.ntop = n_top;
+    a.cap = nnlm_topn_cap(n_top);
+    if (exclude) {
+        a.xptr = by == 0 ? h->sp_cptr : h->sp_rptr;
+        a.xidx = by == 0 ? h->sp_ridx : h->sp_cidx;
+    }
+    const int nw = nnlm_topn_waves(n_top);
+    size_t most_lists = 0; // partial lists of the largest round
+    for (long long l0 = 0; l0 < L; l0 += LCH) {
+        const int nl = (int)(L - l0 < LCH ? L - l0 : LCH);
+        int ns, sl;
+        topn_slicing((nl + 15) / 16, a.ncand, h->cus, ns, sl);
+        if ((size_t)nl * ns > most_lists) most_lists = (size_t)nl * ns;
+    }
+    const size_t chl = (size_t)(L < LCH ? L : LCH);
+    int *ld = nullptr, *id = nullptr;
+    double *sd = nullptr;
+    hipError_t e = bufs.get(&a.part_s, most_lists * n_top);
+    if (e == hipSuccess) e = bufs.get(&a.part_i, most_lists * n_top);
+    if (e == hipSuccess) e = bufs.get(&id, chl * n_top);
+    if (e == hipSuccess) e = bufs.get(&sd, chl * n_top);
+    if (e == hipSuccess && lines) e = bufs.get(&ld, chl);
+    for (long long l0 = 0; l0 < L && e == hipSuccess; l0 += LCH) {
+        const int nl = (int)(L - l0 < LCH ? L - l0 : LCH);
+        a.line0 = (int)l0;
+        a.nlines = nl;
+        a.lines = nullptr;
+        if (lines) {
+            e = hipMemcpyAsync(ld, lines + l0, (size_t)nl * sizeof(int), hipMemcpyHostToDevice, st);
+            if (e != hipSuccess) break;
+            a.lines = ld;
+        }
+        topn_slicing((nl + 15) / 16, a.ncand, h->cus, a.nslices, a.slice_len);
+        h->topn_slices = a.nslices;
+        {
+            ProfScope ps(h, P_TOPN);
+            nnlm_tu_topn(a, nw, st);
+        }
+        {
+            ProfScope ps(h, P_TOPN_MERGE);
+            nnlm_tu_topn_merge(a, id, sd, st);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(idx_out + (size_t)l0 * n_top, id, (size_t)nl * n_top * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(score_out + (size_t)l0 * n_top, sd, (size_t)nl * n_top * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st); // (the round's buffers are reused)
+    }
+    if (e != hipSuccess) return score_fail(h, who, e);
+    sync_all(h);
     return NNLM_OK;
 }
 
