@@ -779,10 +779,6 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : (NT == 1024 ? 4 : 1))) void kl
             }
         }
     }
-#pragma unroll
-    for (int c = 0; c < C; c++)
-#pragma unroll
-        for (int e = 0; e < EPT4; e++) y[c][e] = y[c][e] + tiny;
 #if KLT_TIMING
     // T[i] += cycles since the previous mark: 0 prologue / loop overhead, 1 top of the step (row wait, LDS reads of the coordinate), 2 pass A,
     // 3 wave totals, 4 barrier, 5 scalar part, 6 pass B, 7 epilogue
@@ -868,11 +864,15 @@ __global__ __launch_bounds__(NT, (NT == 256 ? 2 : (NT == 1024 ? 4 : 1))) void kl
                     const f32x4 w = wq[e & 1];
 #pragma unroll
                     for (int c = 0; c < C; c++) {
+                        // the reference's quotient is by y + 1e-16 (:97, :141), and it matters: a state that has returned to EXACTLY 0 (a clamped
+                        // coordinate whose x w was representable, every other w of the row 0) meets w = 0 or b = 0 here, and 0 * rcp(0) is NaN --
+                        // the clamp below then zeroes a live coordinate (SCD) or NaN reaches the factor (Lee).  Two packed adds per four elements.
+                        const f32x4 yt = y[c][e] + tiny;
                         f32x4 r;
-                        r[0] = __builtin_amdgcn_rcpf(__builtin_fabsf(y[c][e][0]));
-                        r[1] = __builtin_amdgcn_rcpf(__builtin_fabsf(y[c][e][1]));
-                        r[2] = __builtin_amdgcn_rcpf(__builtin_fabsf(y[c][e][2]));
-                        r[3] = __builtin_amdgcn_rcpf(__builtin_fabsf(y[c][e][3]));
+                        r[0] = __builtin_amdgcn_rcpf(__builtin_fabsf(yt[0]));
+                        r[1] = __builtin_amdgcn_rcpf(__builtin_fabsf(yt[1]));
+                        r[2] = __builtin_amdgcn_rcpf(__builtin_fabsf(yt[2]));
+                        r[3] = __builtin_amdgcn_rcpf(__builtin_fabsf(yt[3]));
                         if constexpr (METHOD == 4) {
                             acc[c][0] = __builtin_elementwise_fma(w, b[c][e] * r, acc[c][0]); // Wt.row(k) * (Aj / (wh + eps)), :141
                         } else {
