@@ -371,8 +371,10 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * counts), "sweep_form_w" / "sweep_form_h" (SCD sweep of the last W / H half-step: 0 plain sweep_scd_q_kernel, 1 persistent
  * sweep_scd_qw_kernel -- both strict fp64 --, 2 sweep_scd_f_kernel, 3 sweep_row_kernel (fp32-operand mode: 3 while the launch is one
  * round of four-column wavefronts, at most 32 columns per CU), -1 none yet), "sweep_groups_w" /
- * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "kl_form_w" / "kl_form_h" (KL solver of the
- * last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
+ * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "lee_lanes_w" / "lee_lanes_h" and
+ * "lee_regs_w" / "lee_regs_h" (Lee's multiplicative updates at ranks up to 64: lanes per column L -- 4, 2 or 1, chosen from the END column
+ * of the launch -- and coordinate registers per lane R of the sweep_ls_kernel<R, L, 2> launch of the last W / H half-step, -1 none
+ * yet), "kl_form_w" / "kl_form_h" (KL solver of the last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
  * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
  * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies),
  * "matrix_min_col_observed" / "matrix_min_row_observed" (dense matrix: the fewest observed -- finite -- entries of any column / any row,

@@ -827,6 +827,7 @@ class Handle:
 
     def get_info(self, key):
         """cus, sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
+        lee_lanes_w / lee_lanes_h and lee_regs_w / lee_regs_h (L and R of the last sweep_ls_kernel<R, L, 2> launch, -1 none yet),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
         column / a row of a dense matrix)."""
         v = C.c_double(0)

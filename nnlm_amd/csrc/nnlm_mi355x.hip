@@ -80,6 +80,7 @@ struct nnlm_handle {
     int kl_form[2] = {-1, -1}; // per half-step: its last KL solver launch (0 tile kernel on the GEMM's states, 1 tile kernel on its own states, 2 strict register kernel, 3 streaming)
     int sweep_form[2] = {-1, -1}, sweep_groups[2] = {0, 0}; // per half-step (0: W, 1: H): form of its last SCD sweep launch (0 plain, 1 persistent) and
                                                              // column groups per workgroup (nnlm_get_info)
+    int lee_lanes[2] = {-1, -1}, lee_regs[2] = {-1, -1};    // per half-step: L and R of its last sweep_ls_kernel<R, L, 2> launch (nnlm_get_info)
     int prec = NNLM_PREC_F32;
     hipStream_t stream = nullptr;   // main: cross products, solvers
     hipStream_t stream_e = nullptr; // error block, concurrent with the (speculative) next W half-step
@@ -2174,9 +2175,12 @@ static int launch_sweep(nnlm_handle *h, int method, const SweepArgs &a)
     // Lee's multiplicative updates: sweep_ls_kernel, L lanes per column
     const int L = sweep_lanes_per_column(a.ncols);
     const int rneed = (h->k + L - 1) / L;
-    if (L == 4) launch_sweep_l<2, 4>((rneed + 1) / 2, method, a, h->stream);      // R = 2..16, k <= 64
-    else if (L == 2) launch_sweep_l<4, 2>((rneed + 3) / 4, method, a, h->stream); // R = 4..32
-    else launch_sweep_l<8, 1>((rneed + 7) / 8, method, a, h->stream);             // R = 8..64
+    const int step = 8 / L, idx = (rneed + step - 1) / step; // R = step * idx
+    h->lee_lanes[h->cur_which] = L;
+    h->lee_regs[h->cur_which] = step * idx;
+    if (L == 4) launch_sweep_l<2, 4>(idx, method, a, h->stream);      // R = 2..16, k <= 64
+    else if (L == 2) launch_sweep_l<4, 2>(idx, method, a, h->stream); // R = 4..32
+    else launch_sweep_l<8, 1>(idx, method, a, h->stream);             // R = 8..64
     return NNLM_OK;
 }
 
@@ -3595,6 +3599,10 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sweep_form_h") == 0) *value = h->sweep_form[1];
     else if (strcmp(key, "sweep_groups_w") == 0) *value = h->sweep_groups[0];
     else if (strcmp(key, "sweep_groups_h") == 0) *value = h->sweep_groups[1];
+    else if (strcmp(key, "lee_lanes_w") == 0) *value = h->lee_lanes[0]; // (sweep_ls_kernel<R, L, 2> of the last Lee half-step)
+    else if (strcmp(key, "lee_lanes_h") == 0) *value = h->lee_lanes[1];
+    else if (strcmp(key, "lee_regs_w") == 0) *value = h->lee_regs[0];
+    else if (strcmp(key, "lee_regs_h") == 0) *value = h->lee_regs[1];
     else if (strcmp(key, "kl_form_w") == 0) *value = h->kl_form[0];
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
     else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
