@@ -98,6 +98,16 @@ int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int *rowidx, co
                     double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
                     int *n_trace, unsigned *n_iteration, int *warned,
                     const nnlm_callbacks *cb);
+/* nnlm_c_nnmf_csc through nnlm_set_matrix_csc_kl: the same arguments, all four methods (KL loss: k <= 64, stored values >= 0). */
+int nnlm_c_nnmf_csc_kl(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k,
+                       const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                       const double alpha[3], const double beta[3],
+                       unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning,
+                       unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                       double *W_out, double *H_out,
+                       double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                       int *n_trace, unsigned *n_iteration, int *warned,
+                       const nnlm_callbacks *cb);
 /* nnlm_c_nnmf_csc with the absent entries of A missing (see nnlm_set_matrix_csc_missing); same arguments.  Methods 1 and 2, k <= 64. */
 int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k,
                             const double *W_init, const double *H_init, const int *Wm, const int *Hm,
@@ -124,6 +134,11 @@ int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long long *ycolp
                     const double alpha[3], const int *mask, const double *beta0,
                     unsigned max_iter, double rel_tol, int n_threads, int method,
                     double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
+/* nnlm_c_nnlm_csc through nnlm_set_matrix_csc_kl: the same arguments, all four methods (KL loss: p <= 64, stored values >= 0). */
+int nnlm_c_nnlm_csc_kl(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                       const double alpha[3], const int *mask, const double *beta0,
+                       unsigned max_iter, double rel_tol, int n_threads, int method,
+                       double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
 /* nnlm_c_nnlm_csc with the absent entries of y missing (the recommender's fold-in of new columns); same arguments.  Methods 1 and 2,
  * p <= 64. */
 int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
@@ -163,6 +178,15 @@ int nnlm_set_matrix(nnlm_handle *h, const double *A, int n, int m);
  * nnlm_errors work for methods 1 and 2 (square loss), at any rank, with masks; methods 3 and 4 (KL loss), nnlm_comm_init and
  * nnlm_debug_partial return NNLM_ERR_UNSUPPORTED.  nnlm_errors' KL sum leaves out the zeros' -eps log(wh + eps), at most 3.7e-15 each. */
 int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* nnlm_set_matrix_csc for count data that is to be fitted with KL loss: the same arguments, contract and validation, and one more rule --
+ * every stored value is >= 0 (NNLM_ERR_ARG names the first negative one).  The handle is the sparse handle nnlm_set_matrix_csc leaves
+ * (absent entries are zeros; methods 1 and 2, the traces, nnlm_top_n's exclusion and nnlm_get_info behave bit for bit as there) and
+ * ALSO runs methods 3 and 4 in nnlm_half_step, nnlm_iterate and nnlm_run: scd_kl_update / lee_kl_update over the stored entries of each
+ * line (a zero entry of A adds an exact 0 to every sum of those loops but the column sums of the fixed factor), O(nnz k) per half-step,
+ * nothing n x m sized -- at most one state value per stored entry besides the matrix.  Masks, known profiles, all three penalties, any
+ * inner_max_iter, both arithmetic modes (state fp32 / fp64).  Rank <= 64 for methods 3 and 4 (NNLM_ERR_UNSUPPORTED beyond);
+ * nnlm_comm_init and the batch entries return NNLM_ERR_UNSUPPORTED.  Two runs give bit-identical results.  nnlm_get_info: "sparse_kl". */
+int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
 /* The same CSC contract and validation as nnlm_set_matrix_csc, but absent entries are MISSING (a score matrix: movies x customers): every
  * stored entry is an observation, an explicitly stored zero included, and the factorisation fits the stored entries only -- the
  * reference's update_with_missing() (src/update_with_missing.cpp:58-139) on the matrix with NA at the absent entries, without anything
@@ -311,7 +335,8 @@ int nnlm_c_nnmf_holdout_batch(const double *A, int n, int m, const long long *co
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",
  * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack";
- * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block), "sp_gram" (per-column Grams when absent entries are missing);
+ * sparse A: "spmm_h" (W^T A), "spmm_w" (A H^T), "sp_errors" (error block), "sp_gram" (per-column Grams when absent entries are missing), "spkl_copy" (KL loss: row copy and column sums of the
+ * fixed factor), "spkl_solve_h" / "spkl_solve_w" (KL loss: the per-line solvers, starting states included);
  * batched factorisation: "batch_errors" (the one pass over A of a
  * trace iteration), "batch_pen" (the members' penalty sums). */
 int nnlm_profile_enable(nnlm_handle *h, int on);
@@ -382,7 +407,10 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * "matrix_absent_missing" (1 after nnlm_set_matrix_csc_missing, else 0), "sp_gram_chunks" / "sp_gram_bytes" (column chunks of the last
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),
- * "sp_gram_workers" (sp_gram_kernel workers of the last half-step whose absent entries are missing, summed over its column chunks). */
+ * "sp_gram_workers" (sp_gram_kernel workers of the last half-step whose absent entries are missing, summed over its column chunks),
+ * "sparse_kl" (1 after nnlm_set_matrix_csc_kl, else 0), "sparse_kl_form_w" / "sparse_kl_form_h" (KL solver forms of the last W / H half-step on
+ * such a handle: bit 0 = sp_kl_solve_kernel ran, a wavefront per line of at most "sparse_kl_short_max" stored entries; bit 1 =
+ * sp_kl_solve_long_kernel ran, a workgroup per longer line; -1 none yet). */
 int nnlm_get_info(nnlm_handle *h, const char *key, double *value);
 
 #ifdef __cplusplus

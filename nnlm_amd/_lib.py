@@ -35,6 +35,7 @@ EXPORTS = [
     "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
+    "nnlm_set_matrix_csc_kl", "nnlm_c_nnmf_csc_kl", "nnlm_c_nnlm_csc_kl",
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
     "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
@@ -106,6 +107,8 @@ def load():
     for name in ("nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc", "nnlm_set_matrix_csc"):  # absent entries missing: the same arguments
         getattr(lib, name + "_missing").restype = C.c_int
         getattr(lib, name + "_missing").argtypes = getattr(lib, name).argtypes
+        getattr(lib, name + "_kl").restype = C.c_int  # (absent entries zeros, KL loss too: the same arguments)
+        getattr(lib, name + "_kl").argtypes = getattr(lib, name).argtypes
     lib.nnlm_create.restype = C.c_int
     lib.nnlm_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     lib.nnlm_destroy.restype = None
@@ -558,6 +561,13 @@ def c_nnmf_csc_missing(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, bet
                      n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
 
 
+def c_nnmf_csc_kl(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+                  inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_csc through nnlm_set_matrix_csc_kl: all four methods (KL loss over the stored entries; k <= 64, stored values >= 0)."""
+    return _nnmf_csc(load().nnlm_c_nnmf_csc_kl, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol,
+                     n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
+
+
 def _nnmf_csc(entry, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
               inner_max_iter, inner_rel_tol, method, trace, callbacks):
     n, m = (int(v) for v in shape)
@@ -575,6 +585,12 @@ def c_nnlm_csc(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_
 def c_nnlm_csc_missing(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
     """c_nnlm_csc with the absent entries of y missing (the recommender's fold-in of new columns); p <= 64."""
     return _nnlm_csc(load().nnlm_c_nnlm_csc_missing, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol,
+                     n_threads, method, callbacks)
+
+
+def c_nnlm_csc_kl(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks=None):
+    """c_nnlm_csc through nnlm_set_matrix_csc_kl: all four methods (KL loss over the stored entries; p <= 64, stored values >= 0)."""
+    return _nnlm_csc(load().nnlm_c_nnlm_csc_kl, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol,
                      n_threads, method, callbacks)
 
 
@@ -632,6 +648,13 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_kl(self, indptr, indices, data, shape):
+        """set_matrix_csc for KL loss: stored values >= 0; the handle also runs methods 3 and 4 (over the stored entries, rank <= 64)."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc_kl(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
         self.n, self.m = n, m
 
     def set_matrix_csc_missing(self, indptr, indices, data, shape):

@@ -76,10 +76,16 @@ def csc_toarray(c):
     return out
 
 
-def _sparse_input(A, name, loss, absent="zero"):
-    """Sparse argument of nnmf() / nnlm(): canonical CSC; square loss only; no non-finite stored values.  absent = "zero": absent entries
-    are zeros; "missing": they are missing and every stored entry (an explicit zero included) is an observation."""
-    if loss == "mkl":
+_SPARSE_KL_MISSING = "sparse_kl = True cannot be combined with absent = 'missing': the sparse KL solvers treat absent entries as zeros."
+
+
+def _sparse_input(A, name, loss, absent="zero", sparse_kl=False):
+    """Sparse argument of nnmf() / nnlm(): canonical CSC; square loss only unless sparse_kl; no non-finite stored values.  absent = "zero":
+    absent entries are zeros; "missing": they are missing and every stored entry (an explicit zero included) is an observation.
+    sparse_kl (absent = "zero" only): loss = 'mkl' is accepted, and then no stored value may be negative."""
+    if sparse_kl and absent == "missing":
+        raise NnlmStop(_SPARSE_KL_MISSING)
+    if loss == "mkl" and not sparse_kl:
         raise NnlmStop("Sparse %s is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'." % name)
     c = as_csc(A)
     if not np.all(np.isfinite(c.data)):
@@ -88,6 +94,8 @@ def _sparse_input(A, name, loss, absent="zero"):
                            "the structure." % name)
         raise NnlmStop("Sparse %s must not contain NA / non-finite values: absent entries are zeros, not missing; use a dense matrix for "
                        "missing values." % name)
+    if sparse_kl and loss == "mkl" and np.any(c.data < 0):
+        raise NnlmStop("Sparse %s must not store negative values with loss = 'mkl' (sparse_kl = True): KL loss needs non-negative data." % name)
     return c
 
 
@@ -300,21 +308,26 @@ def _nnmf_matrix(A, loss):
 
 def prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
                  check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
-                 inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero"):
+                 inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False):
     """Argument normalisation of nnmf(), R/nnmf.R:142-183 -> (17-tuple for c_nnmf, context dict)."""
     args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace,
-                                 verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent=absent)
+                                 verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent=absent, sparse_kl=sparse_kl)
     return args, ctx
 
 
 def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
                   check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=1, show_warning=True,
-                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None, matrix=None, absent="zero"):
+                  inner_max_iter=None, inner_rel_tol=1e-9, rng=None, matrix=None, absent="zero", sparse_kl=False):
     """prepare_nnmf, also returning the checked matrix; `matrix` = what an earlier call returned for the same A (nnmf_batch: the
     members share one checked, converted A)."""
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
     absent = _absent_arg(absent, A, "A")
+    if sparse_kl and absent == "missing":
+        raise NnlmStop(_SPARSE_KL_MISSING)
+    if sparse_kl and loss == "mkl" and matrix is None and is_sparse(A):  # the opt-in door: KL loss on a sparse A (absent entries zeros)
+        c = _sparse_input(A, "A", loss, sparse_kl=True)
+        matrix = dict(A=c, n=c.shape[0], m=c.shape[1], min_k=min(c.shape))
     if inner_max_iter is None:
         inner_max_iter = 50 if loss == "mse" else 1  # R/nnmf.R:139
     if trace is None:
@@ -342,7 +355,8 @@ def _prepare_nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="m
             int(n_threads), verbose, bool(show_warning), int(inner_max_iter), float(inner_rel_tol), code, int(trace))
     ctx = dict(method=method, loss=loss, alpha=alpha, beta=beta, init=init, mask=mask, n_threads=n_threads, trace=trace,
                verbose=verbose, max_iter=max_iter, rel_tol=rel_tol, inner_max_iter=inner_max_iter,
-               inner_rel_tol=inner_rel_tol, W_norm=W_norm, absent=absent)
+               inner_rel_tol=inner_rel_tol, W_norm=W_norm, absent=absent,
+               sparse_kl=bool(sparse_kl) and loss == "mkl" and isinstance(A, CSC))  # (the call goes through the *_csc_kl entries)
     return args, ctx, mat
 
 
@@ -470,12 +484,14 @@ def _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, m
 
 def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
          check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=0, show_warning=True,
-         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero"):
+         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False):
     """Non-negative matrix factorisation A ~ W H on the MI355X (drop-in for R's NNLM::nnmf, R/nnmf.R:135-225).
 
     ``verbose`` defaults to 0 here (R: 1 = progress bar); ``rng`` seeds the default random init (R uses its global RNG).
     ``absent`` (sparse A only): "zero" -- absent entries are zeros; "missing" -- they are missing and the fit runs over the stored
     entries only, as the reference does for NA (a score matrix such as movies x customers; square loss, k <= 64).
+    ``sparse_kl`` (sparse A, absent = "zero"): True admits loss = 'mkl' on a sparse A (count data; stored values >= 0, k <= 64): the KL
+    solvers then run over the stored entries only.  The default refuses loss = 'mkl' on a sparse A, as before.
 
     ``A`` may live in device memory: a torch tensor on the GPU (fp64, fp32, fp16 or bf16; any non-overlapping strides) or any object with
     ``__cuda_array_interface__``.  It is then ingested where it is -- no copy through the host -- and fitted in the arithmetic mode
@@ -489,12 +505,12 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
         return _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
                             show_warning, inner_max_iter, inner_rel_tol, rng, absent)
     args, ctx = prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads,
-                             trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent)
+                             trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random(), print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
     t0 = time.perf_counter()
     if isinstance(args[0], CSC):
-        entry = _lib.c_nnmf_csc_missing if ctx["absent"] == "missing" else _lib.c_nnmf_csc
+        entry = _lib.c_nnmf_csc_missing if ctx["absent"] == "missing" else (_lib.c_nnmf_csc_kl if ctx["sparse_kl"] else _lib.c_nnmf_csc)
         out = entry(*args[0], *args[1:], callbacks=cb)
     else:
         out = _lib.c_nnmf(*args, callbacks=cb)
@@ -745,7 +761,7 @@ def _rcond(x):
 
 
 def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, check_x=True, max_iter=10000,
-                 rel_tol=1e-12, n_threads=1, show_warning=True, absent="zero"):
+                 rel_tol=1e-12, n_threads=1, show_warning=True, absent="zero", sparse_kl=False):
     """Argument normalisation of nnlm(), R/nnlm.R:75-120 -> (9-tuple for c_nnlm, context)."""
     method = _match_arg(method, ("scd", "lee"), "method")
     loss = _match_arg(loss, ("mse", "mkl"), "loss")
@@ -754,9 +770,9 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
     _refuse_device(y, "nnlm", "y")
     x = np.asarray(x)
     y_sparse = is_sparse(y)
-    yv = _sparse_input(y, "y", loss, absent) if y_sparse else np.asarray(y)
+    yv = _sparse_input(y, "y", loss, absent, sparse_kl) if y_sparse else np.asarray(y)
     with np.errstate(invalid="ignore"):
-        if show_warning and loss == "mkl" and (np.any(x < 0) or np.any(yv < 0)):
+        if show_warning and loss == "mkl" and (np.any(x < 0) or (not y_sparse and np.any(yv < 0))):  # (a sparse y with loss 'mkl' holds no negative value)
             warnings.warn("x or y have negative values. One should instead use method == 'mse'.", RuntimeWarning, stacklevel=3)
     is_y_vector = (not y_sparse) and yv.ndim == 1
     ym = yv if y_sparse else _as_matrix(yv)  # (sparse y: canonical CSC, args[1])
@@ -791,7 +807,8 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
         init_m = (~mask_m).astype(np.float64)  # masked entries fixed to 0, R/nnlm.R:110-112
     code = get_method_code(method, loss)
     args = (x, ym, alpha, mask_m, init_m, int(max_iter), float(rel_tol), int(n_threads), code)
-    ctx = dict(method=method, loss=loss, max_iter=max_iter, rel_tol=rel_tol, is_y_vector=is_y_vector, alpha=alpha, x=x, y=ym, absent=absent)
+    ctx = dict(method=method, loss=loss, max_iter=max_iter, rel_tol=rel_tol, is_y_vector=is_y_vector, alpha=alpha, x=x, y=ym, absent=absent,
+               sparse_kl=bool(sparse_kl) and loss == "mkl" and y_sparse)
     return args, ctx
 
 
@@ -817,16 +834,17 @@ def finish_nnlm(sol, ctx):
 
 
 def nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, check_x=True, max_iter=10000,
-         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None, absent="zero"):
+         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None, absent="zero", sparse_kl=False):
     """Non-negative linear model y ~ x beta on the MI355X (drop-in for R's NNLM::nnlm, R/nnlm.R:70-145).
 
     ``absent`` (sparse y only): "zero" -- absent entries are zeros; "missing" -- they are missing, each column of beta is fitted to the
-    stored entries of its column of y only (square loss, at most 64 columns of x)."""
-    args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning, absent)
+    stored entries of its column of y only (square loss, at most 64 columns of x).
+    ``sparse_kl`` (sparse y, absent = "zero"): True admits loss = 'mkl' (stored values >= 0, at most 64 columns of x); see nnmf()."""
+    args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning, absent, sparse_kl)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random())
     if isinstance(args[1], CSC):
-        entry = _lib.c_nnlm_csc_missing if ctx["absent"] == "missing" else _lib.c_nnlm_csc
+        entry = _lib.c_nnlm_csc_missing if ctx["absent"] == "missing" else (_lib.c_nnlm_csc_kl if ctx["sparse_kl"] else _lib.c_nnlm_csc)
         return finish_nnlm(entry(args[0], *args[1], *args[2:], callbacks=cb), ctx)
     return finish_nnlm(_lib.c_nnlm(*args, callbacks=cb), ctx)
 

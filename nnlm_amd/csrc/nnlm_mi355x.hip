@@ -45,7 +45,8 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES, P_COUNT };
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES,
+              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -58,8 +59,11 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  + its fix-up, both half-steps); "ingest": the ingest kernels of nnlm_set_matrix_device (k_ingest.h), without the common tail
 //  "topn" / "topn_merge" / "predict_entries": topn_kernel, topn_merge_kernel and predict_entries_kernel alone (k_topn.h; the row copies
 //  and the transfers around them are not in it)
+//  "spkl_copy": the row copy and the column sums of the fixed factor of a KL half-step on a sparse A; "spkl_solve_h" / "spkl_solve_w": its
+//  solver launches (k_sparse_kl.h: starting states in the prologue, short and long form)
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries"};
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries",
+                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -157,6 +161,13 @@ struct nnlm_handle {
     // of each column (segoff) and the list of the long columns.  Per orientation and budget: the column chunks whose Grams are held at
     // once; the buffer they share (freed with the factors)
     bool sp_missing = false;
+    // sparse A loaded for KL loss (nnlm_set_matrix_csc_kl, k_sparse_kl.h): a sparse handle whose methods 3 and 4 run.  Per orientation (0: rows
+    // of A for the W half-step, 1: columns for the H half-step) the lines of more than SPKL_SHORT_MAX stored entries, on the device
+    bool sp_kl = false;
+    int *spkl_longc[2] = {nullptr, nullptr};
+    int spkl_nlong[2] = {0, 0}, spkl_nshort[2] = {0, 0};
+    void *spkl_state = nullptr;     // [nnz] states of the long lines' entries (mode's type), on first use
+    int spkl_form[2] = {-1, -1};    // per half-step: forms of its last KL launch (bit 0 short, bit 1 long; nnlm_get_info)
     std::vector<long long> spg_hptr[2];
     long long *spg_segoff[2] = {nullptr, nullptr};
     int *spg_longc[2] = {nullptr, nullptr};
@@ -746,6 +757,15 @@ static void free_matrix(nnlm_handle *h)
         h->spg_plan_cap[o] = 0;
     }
     h->sp_missing = false;
+    for (int o = 0; o < 2; o++) {
+        hipFree(h->spkl_longc[o]);
+        h->spkl_longc[o] = nullptr;
+        h->spkl_nlong[o] = h->spkl_nshort[o] = 0;
+        h->spkl_form[o] = -1;
+    }
+    hipFree(h->spkl_state);
+    h->spkl_state = nullptr;
+    h->sp_kl = false;
     h->nnz = 0;
     hipFree(h->ho_cptr);
     hipFree(h->ho_ridx);
@@ -1326,9 +1346,24 @@ static int spg_layout(nnlm_handle *h, int o, const long long *ptr, int ncols)
     return NNLM_OK;
 }
 
+// Sparse A for KL loss (k_sparse_kl.h): the lines of orientation o that the long form takes
+static int spkl_layout(nnlm_handle *h, int o, const long long *ptr, int ncols)
+{
+    std::vector<int> lc;
+    const long long lim = nnlm_spkl_short_max();
+    for (int c = 0; c < ncols; c++)
+        if (ptr[c + 1] - ptr[c] > lim) lc.push_back(c);
+    h->spkl_nlong[o] = (int)lc.size();
+    h->spkl_nshort[o] = ncols - (int)lc.size();
+    HIPCHK(h, hipMalloc(&h->spkl_longc[o], (lc.size() + 1) * 4));
+    if (!lc.empty()) HIPCHK(h, hipMemcpy(h->spkl_longc[o], lc.data(), lc.size() * 4, hipMemcpyHostToDevice));
+    h->sp_bytes += (lc.size() + 1) * 4;
+    return NNLM_OK;
+}
+
 // nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is
 static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing,
-                               const char *who)
+                               const char *who, bool kl = false)
 {
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
     if (n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix with colptr[m + 1] (n=%d, m=%d)", who, n, m);
@@ -1353,6 +1388,8 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
                                                               "(leave a missing entry out of the structure)"
                                                             : "%s: entry %lld (row %d, column %d) is not finite; a sparse matrix has no missing entries "
                                                               "(use nnlm_set_matrix for NA data)", who, e, i, j);
+            if (kl && v < 0.0)
+                return fail(h, NNLM_ERR_ARG, "%s: entry %lld (row %d, column %d) is negative (%g); KL loss needs non-negative data", who, e, i, j, v);
             rptr[(size_t)i + 1]++;
             if (std::fabs(v) > 3.4028234663852886e38) over += 1.0;
             const double fv = std::fabs((double)(float)v);
@@ -1415,6 +1452,15 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
         }
         return NNLM_OK;
     }
+    if (kl) {
+        h->sp_kl = true;
+        int rl = spkl_layout(h, 1, colptr, m);
+        if (rl == NNLM_OK) rl = spkl_layout(h, 0, rptr.data(), n);
+        if (rl != NNLM_OK) {
+            free_matrix(h);
+            return rl;
+        }
+    }
     h->n_non_missing = (double)n * (double)m;
     h->any_missing = false;
     // the zeros add (n m - nnz) eps log eps
@@ -1430,6 +1476,11 @@ extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long
 extern "C" int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
 {
     return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, true, "nnlm_set_matrix_csc_missing");
+}
+
+extern "C" int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_kl", true);
 }
 
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
@@ -2850,11 +2901,61 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
     return NNLM_OK;
 }
 
+static int spkl_rank_refusal(nnlm_handle *h, const char *who)
+{
+    return fail(h, NNLM_ERR_UNSUPPORTED, "%s: rank %d with KL loss on a sparse matrix: the sparse KL solvers take ranks up to %d (use a dense matrix)", who,
+                h->k, NNLM_KQ_MAX);
+}
+
+// KL half-step on a sparse A loaded by nnlm_set_matrix_csc_kl (k_sparse_kl.h; update(), src/update_with_missing.cpp:27,47-49, on the
+// stored entries): the row copy and the column sums of the fixed factor, then the per-line solvers -- the short form over all lines (it
+// leaves out the long ones), the long form over the list made when the matrix was set.  Nothing n x m sized; one T per stored entry
+// (spkl_state) when the orientation has a long line.
+static int half_step_sparse_kl(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+                               bool speculative)
+{
+    if (h->k > NNLM_KQ_MAX) return spkl_rank_refusal(h, "half_step");
+    const int o = s.which;
+    const bool f64 = h->prec == NNLM_PREC_F64;
+    int rc = ensure_klsw(h);
+    if (rc != NNLM_OK) return rc;
+    if (h->spkl_nlong[o] > 0 && !h->spkl_state) HIPCHK(h, hipMalloc(&h->spkl_state, (size_t)h->nnz * (f64 ? 8 : 4) + 64));
+    {
+        ProfScope ps(h, P_SPKL_COPY);
+        if (f64) factor_rows_kernel<double><<<(s.p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->KP, (double *)h->sp_Y);
+        else factor_rows_kernel<float><<<(s.p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->KP, (float *)h->sp_Y);
+        kl_sumw_kernel<<<h->k, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->klsw);
+    }
+    SpKlArgs a;
+    a.ptr = s.sp_ptr; a.idx = s.sp_idx; a.val = s.sp_val;
+    a.Y = h->sp_Y;
+    a.KP = h->KP; a.ncols = s.ncols; a.k = h->k;
+    a.X = s.X; a.Xout = s.Xout; a.ldx = s.ldc;
+    a.sumw = h->klsw;
+    a.r0 = reg[0]; a.r1 = reg[1]; a.r2 = reg[2];
+    a.mask = s.mask; a.mw = h->MW;
+    a.max_iter = inner_max_iter; a.rel_tol = inner_rel_tol;
+    a.op = s.op; a.op_mode = s.op_mode; a.op_ld = s.op_ld;
+    a.sweeps = sweep_counter(h, speculative);
+    a.state = h->spkl_state;
+    a.longc = h->spkl_longc[o];
+    a.nlong = h->spkl_nlong[o];
+    {
+        ProfScope ps(h, o == 1 ? P_SPKL_H : P_SPKL_W);
+        nnlm_tu_sp_kl(a, method, f64, h->spkl_nshort[o], h->stream);
+    }
+    h->spkl_form[o] = (h->spkl_nshort[o] > 0 ? 1 : 0) | (h->spkl_nlong[o] > 0 ? 2 : 0);
+    LAUNCHCHK(h);
+    if (s.which == 0 && !speculative) swap_w(h);
+    return NNLM_OK;
+}
+
 // Square-loss half-step on a sparse A (k_sparse.h): the Gram of the fixed factor (launch_gram), the SpMM (sp_cross) into ONE slab of Cx,
 // then the solvers of the dense path unchanged (half_step_solve; rank > 64: the generic Gram and sweep).  Absent entries missing (and some
 // absent): half_step_sparse_missing.
 static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
 {
+    if (method >= 3 && h->sp_kl) return half_step_sparse_kl(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
     if (method >= 3)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     // (every entry stored: the reference's update(), src/update_with_missing.cpp:3-55 -- the shared Gram of the zero semantics)
@@ -3552,6 +3653,9 @@ extern "C" int nnlm_comm_init(nnlm_handle *h, const char id[NNLM_COMM_ID_BYTES],
 {
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_comm_init: handle is NULL");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, NNLM_ERR_ARG, "nnlm_comm_init: bad rank %d of %d", rank, nranks);
+    if (h->sparse && h->sp_kl)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl); the sparse KL "
+                                             "path is single-GPU only");
     if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a sparse matrix; the sparse path is single-GPU only");
     if (h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a matrix with a hold-out set; that path is single-GPU only");
     HIPCHK(h, hipSetDevice(h->device));
@@ -3611,6 +3715,10 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "matrix_min_col_observed") == 0) return observed_min(h, 0, value);
     else if (strcmp(key, "matrix_min_row_observed") == 0) return observed_min(h, 1, value);
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
+    else if (strcmp(key, "sparse_kl") == 0) *value = (h->sparse && h->sp_kl) ? 1.0 : 0.0;
+    else if (strcmp(key, "sparse_kl_form_w") == 0) *value = h->spkl_form[0];
+    else if (strcmp(key, "sparse_kl_form_h") == 0) *value = h->spkl_form[1];
+    else if (strcmp(key, "sparse_kl_short_max") == 0) *value = nnlm_spkl_short_max();
     else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
     else if (strcmp(key, "sp_workers") == 0) *value = (h->sparse && h->KP > 0) ? nnlm_sp_workers(h->nnz, h->KP, h->cus_device) : 0;
@@ -3815,8 +3923,9 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                 n_trace, n_iteration, warned, cb};
     int rc = L.check("nnlm_run");
     if (rc != NNLM_OK) return rc;
-    if (h->sparse && method >= 3)
+    if (h->sparse && method >= 3 && !h->sp_kl)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
+    if (h->sparse && method >= 3 && h->k > NNLM_KQ_MAX) return spkl_rank_refusal(h, "nnlm_run");
     HIPCHK(h, hipSetDevice(h->device));
 #define CHK(x)                  \
     do {                        \
@@ -3938,6 +4047,9 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
 // ---------------------------------------------------------------------------------------------
 static int batch_refusal(nnlm_handle *h, const char *who)
 {
+    if (h->sparse && h->sp_kl)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl) is not supported by the batched factorisation "
+                                             "(dense A, square loss only)", who);
     if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
     if (h->any_missing && !h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
     if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the batched factorisation runs on one GPU (no communicator)", who);
@@ -4640,6 +4752,19 @@ extern "C" int nnlm_c_nnmf_csc(int n, int m, const long long *colptr, const int 
                        trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
+extern "C" int nnlm_c_nnmf_csc_kl(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
+                                  const double *H_init, const int *Wm, const int *Hm, const double alpha[3], const double beta[3], unsigned max_iter,
+                                  double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                                  int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                                  double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                                  const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    return c_nnmf_body("nnlm_c_nnmf_csc_kl", colptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc_kl(h, n, m, colptr, rowidx, x); }, n, m, k,
+                       W_init, H_init, Wm, Hm, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
+                       trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+}
+
 extern "C" int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned k, const double *W_init,
                                        const double *H_init, const int *Wm, const int *Hm, const double alpha[3], const double beta[3],
                                        unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter,
@@ -4697,6 +4822,15 @@ extern "C" int nnlm_c_nnlm_csc(const double *x, int n, int p, int q, const long 
     (void)n_threads;
     return c_nnlm_body("nnlm_c_nnlm_csc", ycolptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc(h, n, q, ycolptr, yrowidx, yx); }, x, n, p,
                        q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
+}
+
+extern "C" int nnlm_c_nnlm_csc_kl(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                                  const double alpha[3], const int *mask, const double *beta0, unsigned max_iter, double rel_tol, int n_threads,
+                                  int method, double *coefficient, int *n_iteration, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    return c_nnlm_body("nnlm_c_nnlm_csc_kl", ycolptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc_kl(h, n, q, ycolptr, yrowidx, yx); }, x, n,
+                       p, q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
 }
 
 extern "C" int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,

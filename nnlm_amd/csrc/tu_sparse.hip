@@ -1,7 +1,8 @@
-// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_na.h), see tu_sweepq.h.
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_na.h, k_sparse_kl.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
 #include "k_sparse_na.h"
+#include "k_sparse_kl.h"
 
 // Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
 // launched once per 64 coordinates)
@@ -106,3 +107,22 @@ void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int
     }
 }
 void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st) { sp_err_final_missing_kernel<<<1, 64, 0, st>>>(s, out); }
+
+// ---- KL loss, absent entries zeros (k_sparse_kl.h) ----
+int nnlm_spkl_short_max(void) { return SPKL_SHORT_MAX; }
+
+template <int METHOD, typename T> static void launch_sp_kl(const SpKlArgs &a, int nshort, hipStream_t st)
+{
+    if (nshort > 0) sp_kl_solve_kernel<METHOD, T><<<(a.ncols + 3) / 4, 256, 0, st>>>(a);
+    if (a.nlong > 0) sp_kl_solve_long_kernel<METHOD, T><<<a.nlong, 256, 0, st>>>(a);
+}
+void nnlm_tu_sp_kl(const SpKlArgs &a, int method, bool f64, int nshort, hipStream_t st)
+{
+    if (method == 3) {
+        if (f64) launch_sp_kl<3, double>(a, nshort, st);
+        else launch_sp_kl<3, float>(a, nshort, st);
+    } else {
+        if (f64) launch_sp_kl<4, double>(a, nshort, st);
+        else launch_sp_kl<4, float>(a, nshort, st);
+    }
+}

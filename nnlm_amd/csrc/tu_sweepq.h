@@ -64,3 +64,31 @@ void nnlm_tu_sp_gram(const SpGramArgs &a, int NKQ, bool f64, hipStream_t st);
 void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int KP, hipStream_t st);
 // out[0] = S1, out[1] = S3 + S2 (sum of squares, KL sum over the stored entries)
 void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st);
+
+// Sparse A, KL loss (k_sparse_kl.h, tu_sparse.hip): scd_kl_update / lee_kl_update over the stored entries of the lines [0, ncols)
+struct SpKlArgs {
+    const long long *ptr;  // [ncols + 1] CSC (H half-step) / CSR (W half-step)
+    const int *idx;        // [nnz] row of the fixed factor of each stored entry
+    const void *val;       // [nnz] T
+    const void *Y;         // [rows][KP] T, row-major fixed factor
+    int KP, ncols, k;      // k <= 64
+    const double *X;       // [KP][ldx] master of the factor solved, read
+    double *Xout;          // same layout, written (may alias X)
+    int ldx;
+    const double *sumw;    // [k] column sums of the fixed factor
+    double r0, r1, r2;
+    const unsigned long long *mask; // [ncols][mw] or NULL
+    int mw;
+    unsigned max_iter;
+    double rel_tol;
+    void *op;              // fp32 operand copy of the factor solved [KP][op_ld] (op_mode 1: the fp32-operand mode's W), or none
+    int op_mode, op_ld;
+    unsigned long long *sweeps;
+    void *state;           // [nnz] T: states of the long lines' entries (long form)
+    const int *longc;      // the lines the long form takes
+    int nlong;
+};
+// the longest line the short form (a wavefront per line) takes
+int nnlm_spkl_short_max(void);
+// method 3 (SCD) or 4 (Lee); short form over all lines (it skips the long ones) when nshort > 0, long form over a.longc when a.nlong > 0
+void nnlm_tu_sp_kl(const SpKlArgs &a, int method, bool f64, int nshort, hipStream_t st);
