@@ -187,6 +187,13 @@ int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, c
  * inner_max_iter, both arithmetic modes (state fp32 / fp64).  Rank <= 64 for methods 3 and 4 (NNLM_ERR_UNSUPPORTED beyond);
  * nnlm_comm_init and the batch entries return NNLM_ERR_UNSUPPORTED.  Two runs give bit-identical results.  nnlm_get_info: "sparse_kl". */
 int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* nnlm_set_matrix_csc for restarts and rank sweeps: the same arguments, contract, validation and resident layout (absent entries are
+ * zeros).  The handle is the sparse handle nnlm_set_matrix_csc leaves -- nnlm_set_factors, nnlm_half_step, nnlm_iterate, nnlm_run,
+ * nnlm_errors, nnlm_top_n and nnlm_predict_entries behave bit for bit as there -- and ALSO accepts nnlm_set_factors_batch,
+ * nnlm_run_batch and nnlm_get_factors_batch: per half-step ONE SpMM over the non-zeros at the stacked rank, per trace iteration ONE
+ * walk over the non-zeros for the error sums of all members.  The batch's own limits hold (methods 1 and 2, rank sum <= 64, no
+ * communicator).  A handle loaded by any other sparse entry refuses the batch entries as before.  nnlm_get_info: "sparse_batch". */
+int nnlm_set_matrix_csc_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
 /* The same CSC contract and validation as nnlm_set_matrix_csc, but absent entries are MISSING (a score matrix: movies x customers): every
  * stored entry is an observation, an explicitly stored zero included, and the factorisation fits the stored entries only -- the
  * reference's update_with_missing() (src/update_with_missing.cpp:58-139) on the matrix with NA at the absent entries, without anything
@@ -323,6 +330,15 @@ int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, const unsigned 
                       double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch, int *n_trace,
                       unsigned *n_iteration, int *warned, const nnlm_callbacks *cb);
 
+/* nnlm_c_nnmf_batch on a sparse A (canonical CSC, absent entries zeros; loaded by nnlm_set_matrix_csc_batch); the arguments after x
+ * are those of nnlm_c_nnmf_batch after m, the default inits are drawn in the same order. */
+int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned B, const unsigned *k,
+                          const double *W_init, const double *H_init, const double alpha[3], const double beta[3], unsigned max_iter,
+                          double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                          int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                          double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                          const nnlm_callbacks *cb);
+
 /* nnlm_c_nnmf_batch on A with the pattern (colptr, rowidx) held out (nnlm_set_matrix_holdout), + holdout_mse[B], holdout_mkl[B]:
  * nnlm_holdout_errors of the final factors. */
 int nnlm_c_nnmf_holdout_batch(const double *A, int n, int m, const long long *colptr, const int *rowidx, unsigned B, const unsigned *k,
@@ -408,7 +424,8 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),
  * "sp_gram_workers" (sp_gram_kernel workers of the last half-step whose absent entries are missing, summed over its column chunks),
- * "sparse_kl" (1 after nnlm_set_matrix_csc_kl, else 0), "sparse_kl_form_w" / "sparse_kl_form_h" (KL solver forms of the last W / H half-step on
+ * "sparse_batch" (1 after nnlm_set_matrix_csc_batch, else 0), "sp_batch_waves" (wavefronts of one sp_batch_errors_kernel launch on the
+ * resident sparse matrix -- a function of its non-zeros and the CU count only --, 0 without one), "sparse_kl" (1 after nnlm_set_matrix_csc_kl, else 0), "sparse_kl_form_w" / "sparse_kl_form_h" (KL solver forms of the last W / H half-step on
  * such a handle: bit 0 = sp_kl_solve_kernel ran, a wavefront per line of at most "sparse_kl_short_max" stored entries; bit 1 =
  * sp_kl_solve_long_kernel ran, a workgroup per longer line; -1 none yet). */
 int nnlm_get_info(nnlm_handle *h, const char *key, double *value);

@@ -40,6 +40,7 @@ EXPORTS = [
     "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
     "nnlm_predict_entries", "nnlm_top_n",
+    "nnlm_set_matrix_csc_batch", "nnlm_c_nnmf_csc_batch",
 ]
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
 BY = {"column": 0, "row": 1}
@@ -176,6 +177,10 @@ def load():
     lib.nnlm_c_nnmf_batch.restype = C.c_int
     lib.nnlm_c_nnmf_batch.argtypes = [dp, C.c_int, C.c_int, C.c_uint, up, dp, dp, dp, dp, C.c_uint, C.c_double, C.c_int, C.c_int, C.c_int,
                                       C.c_uint, C.c_double, C.c_int, C.c_uint, dp, dp, dp, dp, dp, dp, ip, up, ip, C.POINTER(Callbacks)]
+    lib.nnlm_c_nnmf_csc_batch.restype = C.c_int
+    lib.nnlm_c_nnmf_csc_batch.argtypes = [C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnmf_batch.argtypes[3:]
+    lib.nnlm_set_matrix_csc_batch.restype = C.c_int
+    lib.nnlm_set_matrix_csc_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes
     lib.nnlm_set_matrix_holdout.restype = C.c_int
     lib.nnlm_set_matrix_holdout.argtypes = [vp, dp, C.c_int, C.c_int, lp, ip]
     lib.nnlm_holdout_errors.restype = C.c_int
@@ -487,13 +492,26 @@ def c_nnmf_holdout_batch(A, indptr, indices, ks, W, H, alpha, beta, max_iter, re
                         method, trace, callbacks, _holdout=(ptr, idx))
 
 
+def c_nnmf_csc_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+                     inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_batch on a sparse A given as canonical CSC arrays (indptr[m+1], indices, data) of shape (n, m), absent entries zeros
+    (nnlm_c_nnmf_csc_batch): one SpMM per half-step and one walk over the non-zeros per trace iteration for all members."""
+    n, m = (int(v) for v in shape)
+    ptr, idx, val = _csc_arrays(indptr, indices, data)
+    return c_nnmf_batch(None, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol,
+                        method, trace, callbacks, _csc=(n, m, ptr, idx, val))
+
+
 def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
-                 trace, callbacks=None, _holdout=None):
+                 trace, callbacks=None, _holdout=None, _csc=None):
     """Batched c_nnmf (nnlm_c_nnmf_batch): member b has rank ks[b] and starts from W[b] (n x k_b), H[b] (k_b x m) -- either list may
     be None for the library's default init.  Returns one c_nnmf-style dict per member."""
     lib = load()
-    A = _f64(A)
-    n, m = A.shape
+    if _csc is None:
+        A = _f64(A)
+        n, m = A.shape
+    else:
+        n, m = _csc[:2]
     ks = _batch_ranks(ks)
     Wc = _batch_blocks(W, [(n, int(k)) for k in ks], "W")
     Hc = _batch_blocks(H, [(int(k), m) for k in ks], "H")
@@ -509,7 +527,9 @@ def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose
             int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace),
             n_it.ctypes.data_as(C.POINTER(C.c_uint)), _ip(warned)]
     cbp = C.byref(callbacks) if callbacks is not None else None
-    if _holdout is None:
+    if _csc is not None:
+        rc = lib.nnlm_c_nnmf_csc_batch(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), *args, cbp)
+    elif _holdout is None:
         rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, *args, cbp)
     else:
         hmse, hmkl = np.zeros(B), np.zeros(B)
@@ -648,6 +668,13 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_batch(self, indptr, indices, data, shape):
+        """set_matrix_csc for restarts and rank sweeps: the same sparse handle, which also accepts set_factors_batch / run_batch."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc_batch(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
         self.n, self.m = n, m
 
     def set_matrix_csc_kl(self, indptr, indices, data, shape):

@@ -530,7 +530,7 @@ def _batch_rank_list(k, nrun):
     return ks
 
 
-def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
+def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_options):
     """Several nnmf() runs of one dense matrix at once: random restarts (nrun) and rank sweeps (k a sequence) share every pass over A.
 
     Member list: each rank of ``k`` gets ``nrun`` members, rank after rank (k = [2, 3], nrun = 2 -> ranks 2, 2, 3, 3).  ``init`` is None
@@ -541,7 +541,12 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
 
     Square loss only, dense A without missing entries, no masks or known profiles, ranks summing to at most 64: anything else raises
     NnlmError with code NNLM_ERR_UNSUPPORTED; a bad k list or an init that does not match it, NNLM_ERR_ARG.
+
+    ``sparse_batch`` = True admits a sparse A (an object with tocsc(); absent entries are zeros): it is made canonical once for all
+    members, every half-step is one SpMM over the non-zeros at the stacked rank and every trace iteration one walk over them.  The other
+    limits stay, and absent = 'missing' is refused.  With a dense A the flag changes nothing; the default refuses a sparse A as before.
     """
+    sparse_batch = bool(sparse_batch)
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
     if init is not None:
@@ -555,8 +560,11 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, **nnmf_options):
         raise unsupported("known profiles (W0 / H0) are not supported by the batched factorisation")
     if _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss") != "mse":
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
-    if is_sparse(A):
+    if is_sparse(A) and not sparse_batch:
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    if is_sparse(A) and _match_arg(nnmf_options.get("absent", "zero"), ("zero", "missing"), "absent") == "missing":
+        raise unsupported("absent = 'missing' is not supported by the batched factorisation of a sparse A (sparse_batch = True): "
+                          "absent entries are zeros")
     if sum(ks) > _lib.BATCH_MAX:
         raise unsupported("the ranks sum to %d; a batch holds at most %d" % (sum(ks), _lib.BATCH_MAX))
     on_device = _lib.is_device_array(A)
@@ -591,10 +599,13 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
         mat = _device_matrix(A, h)
         if h.matrix_info()["any_missing"]:
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
+    elif is_sparse(A):  # (sparse_batch = True: canonical CSC once for all members; check_k's bound is min(n, m))
+        c = _sparse_input(A, "A", "mse")
+        mat = dict(A=c, n=c.shape[0], m=c.shape[1], min_k=min(c.shape))
     for b in range(B):  # member after member, each consuming the generator as nnmf() would
         # (A is checked and converted by the first member's call only: every member shares that one fp64 copy)
         args, ctx, mat = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
-        if b == 0 and h is None and not np.isfinite(mat["A"]).all():
+        if b == 0 and h is None and not isinstance(mat["A"], CSC) and not np.isfinite(mat["A"]).all():
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
         n, m = mat["n"], mat["m"]
         W, H = _default_init(args[2], args[3], (), (), n, m, ks[b], g)
@@ -604,7 +615,9 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
     a0 = prep[0][0]
     cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    if h is None:
+    if isinstance(a0[0], CSC):
+        outs = _lib.c_nnmf_csc_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+    elif h is None:
         outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     else:
         h.set_factors_batch(ks, Ws, Hs)

@@ -46,7 +46,7 @@ static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
               P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES,
-              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_COUNT };
+              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -61,9 +61,11 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  and the transfers around them are not in it)
 //  "spkl_copy": the row copy and the column sums of the fixed factor of a KL half-step on a sparse A; "spkl_solve_h" / "spkl_solve_w": its
 //  solver launches (k_sparse_kl.h: starting states in the prologue, short and long form)
+//  "sp_batch_errors": the error block of a batched factorisation on a sparse A (k_sparse_batch.h: the row copies, the stacked Grams and
+//  coordinate sums, ONE sp_batch_errors_kernel launch over the non-zeros for all members, its reduction and the closing kernel)
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
                                           "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries",
-                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w"};
+                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -164,6 +166,9 @@ struct nnlm_handle {
     // sparse A loaded for KL loss (nnlm_set_matrix_csc_kl, k_sparse_kl.h): a sparse handle whose methods 3 and 4 run.  Per orientation (0: rows
     // of A for the W half-step, 1: columns for the H half-step) the lines of more than SPKL_SHORT_MAX stored entries, on the device
     bool sp_kl = false;
+    // sparse A loaded for the batched factorisation (nnlm_set_matrix_csc_batch): the ordinary sparse handle (absent entries zeros) that
+    // nnlm_set_factors_batch / nnlm_run_batch also accept (batch_refusal)
+    bool sp_batch = false;
     int *spkl_longc[2] = {nullptr, nullptr};
     int spkl_nlong[2] = {0, 0}, spkl_nshort[2] = {0, 0};
     void *spkl_state = nullptr;     // [nnz] states of the long lines' entries (mode's type), on first use
@@ -228,6 +233,8 @@ struct nnlm_handle {
     double *bpart = nullptr;                // partial sums of the batched error block / penalties
     size_t bpart_elems = 0;
     double *bres = nullptr;                 // [8 bB]: {sum sq, sum KL} per member, then 3 W and 3 H penalty sums per member
+    double *bsp_Hrow = nullptr;             // sparse A: [m][KP] fp64 rows of H (the rows of W: sp_Wrow), error block
+    double *bsp_part = nullptr;             // sparse A: [3 bB][workgroups] partial sums of sp_batch_errors_kernel, then [3 bB] their sums
 
     // hold-out set (nnlm_set_matrix_holdout): the resident matrix is A with NA at the pattern (the dense NA layout
     // above); the held-out entries themselves stay here as a CSC -- values in the mode's type, the column of every entry beside its row
@@ -642,8 +649,10 @@ static void free_batch(nnlm_handle *h)
     hipFree(h->bsweeps);
     hipFree(h->bpart);
     hipFree(h->bres);
+    hipFree(h->bsp_Hrow);
+    hipFree(h->bsp_part);
     h->boff_dev = nullptr;
-    h->bG = h->bpart = h->bres = nullptr;
+    h->bG = h->bpart = h->bres = h->bsp_Hrow = h->bsp_part = nullptr;
     h->bsweeps = nullptr;
     h->bpart_elems = 0;
     h->bB = 0;
@@ -766,6 +775,7 @@ static void free_matrix(nnlm_handle *h)
     hipFree(h->spkl_state);
     h->spkl_state = nullptr;
     h->sp_kl = false;
+    h->sp_batch = false;
     h->nnz = 0;
     hipFree(h->ho_cptr);
     hipFree(h->ho_ridx);
@@ -1481,6 +1491,15 @@ extern "C" int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const l
 extern "C" int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
 {
     return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_kl", true);
+}
+
+// The sparse handle of nnlm_set_matrix_csc (same arguments, checks and resident layout; absent entries are zeros) that the batch entries
+// also accept: the flag is all that differs
+extern "C" int nnlm_set_matrix_csc_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    const int rc = set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_batch");
+    if (rc == NNLM_OK) h->sp_batch = true;
+    return rc;
 }
 
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
@@ -3716,6 +3735,8 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "matrix_min_row_observed") == 0) return observed_min(h, 1, value);
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
     else if (strcmp(key, "sparse_kl") == 0) *value = (h->sparse && h->sp_kl) ? 1.0 : 0.0;
+    else if (strcmp(key, "sparse_batch") == 0) *value = (h->sparse && h->sp_batch) ? 1.0 : 0.0;
+    else if (strcmp(key, "sp_batch_waves") == 0) *value = h->sparse ? nnlm_spb_waves(h->nnz, h->cus) : 0;
     else if (strcmp(key, "sparse_kl_form_w") == 0) *value = h->spkl_form[0];
     else if (strcmp(key, "sparse_kl_form_h") == 0) *value = h->spkl_form[1];
     else if (strcmp(key, "sparse_kl_short_max") == 0) *value = nnlm_spkl_short_max();
@@ -4040,17 +4061,21 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
 }
 
 // ---------------------------------------------------------------------------------------------
-// batched factorisation: B independent square-loss models of one dense matrix, ranks k_b with sum <= 64, stacked
+// batched factorisation: B independent square-loss models of one dense matrix (or, DESIGN section 4.18, of a sparse
+// one loaded by nnlm_set_matrix_csc_batch: the cross product is then sp_cross, the error block k_sparse_batch.h), ranks k_b with sum <= 64, stacked
 // in the factor buffers.  Per half-step ONE cross product of A with the stacked fixed factor (rows off_b .. off_b + k_b - 1 of its
 // slabs are member b's), then per active member the Gram of ITS rows of the fixed factor and the existing sweep on its row block of
 // Cx / X (pointer offsets; every sweep kernel reads and writes rows q < a.k only).  Per trace iteration one errors_batch_kernel pass.
 // ---------------------------------------------------------------------------------------------
+static_assert(SPB_BATCH_MAX == BATCH_MAX, "sp_batch_errors_kernel keeps one LDS slot per member");
 static int batch_refusal(nnlm_handle *h, const char *who)
 {
     if (h->sparse && h->sp_kl)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl) is not supported by the batched factorisation "
                                              "(dense A, square loss only)", who);
-    if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
+    // (the door: a sparse matrix loaded by nnlm_set_matrix_csc_batch -- absent entries zeros, square loss -- passes)
+    if (h->sparse && !(h->sp_batch && !h->sp_missing))
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
     if (h->any_missing && !h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
     if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the batched factorisation runs on one GPU (no communicator)", who);
     return NNLM_OK;
@@ -4110,6 +4135,11 @@ extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned
     HIPCHK(h, hipMemset(h->bsweeps, 0, B * sizeof(unsigned long long)));
     HIPCHK(h, hipMalloc(&h->bpart, h->bpart_elems * 8));
     HIPCHK(h, hipMalloc(&h->bres, (size_t)8 * B * 8));
+    if (h->sparse) { // error block (k_sparse_batch.h): the row copy of H beside sp_Wrow, the partial sums of the kernel and their sums
+        const size_t nblk = (size_t)(nnlm_spb_waves(h->nnz, h->cus) + 3) / 4;
+        HIPCHK(h, hipMalloc(&h->bsp_Hrow, (size_t)h->mpad * h->KP * 8));
+        HIPCHK(h, hipMalloc(&h->bsp_part, ((size_t)3 * B * nblk + 3 * B) * 8));
+    }
     return NNLM_OK;
 }
 
@@ -4146,7 +4176,8 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     h->sg_request = false;
     h->fuse_err = false;
     h->cur_which = which;
-    const HalfPlan p = plan_half(h, which, 0, 1);
+    HalfPlan p = plan_half(h, which, 0, 1);
+    if (h->sparse) p.S = 1; // (one slab: the SpMM has no split-K)
     // Hold-out handle with a non-empty set: A has missing entries, every column solves with a Gram of its own.  The
     // cross product below needs nothing new (A holds 0 at a missing entry); the NA workspaces: the row copy for the stacked KP (at least
     // any member's), ONE buffer of per-column Grams sized for the largest member -- the members run one after another on this stream
@@ -4162,12 +4193,15 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     }
     // 1. one cross product for all members: split-fp16 copy of the whole stacked factor (ONE scale, max over all members), then the
     //    A-streaming kernel exactly as a rank-K solo half-step launches it
-    if (h->x16) prepare_factor16(h, s);
+    // Sparse A (nnlm_set_matrix_csc_batch): the SpMM at the stacked KP -- one walk over the CSC / CSR, every row of the fixed factor
+    // gathered once at the stacked width; lane = coordinate, so a member's rows of the slab do not depend on its neighbours
+    if (h->sparse) sp_cross(h, s);
+    else if (h->x16) prepare_factor16(h, s);
     else if (which == 0) {
         int rca = ensure_AT(h);
         if (rca != NNLM_OK) return rca;
     }
-    {
+    if (!h->sparse) {
         // (strict mode: always the whole-tile instantiation, never the VALU tail rows of launch_xprod_nkq -- every row of the slabs is then
         //  formed by the same MFMA sequence wherever its member sits, and a member's result does not depend on its neighbours)
         ProfScope ps(h, s.prof_xprod);
@@ -4238,7 +4272,33 @@ static int batch_errors(nnlm_handle *h, unsigned long long amask, bool need_pen,
 {
     const int B = h->bB;
     hipStream_t st = h->stream;
-    {
+    if (h->sparse) {
+        // Sparse A (k_sparse_batch.h): fp64 row copies of the stacked W and H; ONE launch over the non-zeros for the three sums of every
+        // member; the zeros' share from the Grams of the stacked factors (gram_partial_kernel at the stacked KP: an entry of the Gram is
+        // a sum over the columns of the products of ITS two rows in a fixed order, so a member's diagonal block depends on neither its
+        // position nor its neighbours) and one launch per factor for the sums of all coordinates; one kernel closes all members
+        ProfScope ps(h, P_SP_BATCH_ERRORS, st);
+        const int KP = h->KP, n = h->n, m = h->m;
+        double *G = h->sp_eG, *sums = G + (size_t)2 * KP * KP;
+        factor_rows_kernel<double><<<(n + 255) / 256, 256, 0, st>>>(h->W64, h->npad, n, KP, h->sp_Wrow);
+        factor_rows_kernel<double><<<(m + 255) / 256, 256, 0, st>>>(h->H64, h->mpad, m, KP, h->bsp_Hrow);
+        for (int f = 0; f < 2; f++) {
+            const double *X = f == 0 ? h->W64 : h->H64;
+            const int ld = f == 0 ? h->npad : h->mpad, cols = f == 0 ? n : m;
+            const int nb = launch_gram_partial(h, X, ld, 0, cols, h->sp_eslabs, nullptr, st);
+            gram_reduce_kernel<<<(KP * KP + 255) / 256, 256, 0, st>>>(h->sp_eslabs, nb, KP, G + (size_t)f * KP * KP);
+            const int rb = (cols + 2047) / 2048;
+            nnlm_tu_sp_rowsums(X, ld, cols, KP, h->sp_epart, rb, st);
+            reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)rb, KP, sums + (size_t)f * KP);
+        }
+        // (the split over the non-zeros: nnz and the CU count -- the test hook's, nnlm_debug_set_cus -- decide it, not B or KP)
+        const int nwaves = nnlm_spb_waves(h->nnz, h->cus), nblk = (nwaves + 3) / 4;
+        double *S = h->bsp_part + (size_t)3 * B * nblk;
+        nnlm_tu_sp_batch_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, nnlm_spb_chunk(h->nnz, nwaves), nwaves,
+                                h->sp_Wrow, h->bsp_Hrow, KP, h->boff_dev, B, amask, h->bsp_part, st);
+        batch_reduce_kernel<<<3 * B, 256, 0, st>>>(h->bsp_part, nblk, S);
+        nnlm_tu_sp_batch_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->boff_dev, B, KP, amask, h->bres, st);
+    } else {
         ProfScope ps(h, P_BATCH_ERRORS, st);
         const int nit = h->npad / 64, mt = (h->m + 63) / 64;
         const int nch = mt < 1 ? 1 : (mt < (1024 + nit - 1) / nit ? mt : (1024 + nit - 1) / nit);
@@ -4659,6 +4719,35 @@ extern "C" int nnlm_c_nnmf_batch(const double *A, int n, int m, unsigned B, cons
     if (rc != NNLM_OK) return rc;
     OneShot os;
     rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix(h, A, n, m); });
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
+    std::vector<double> Wi, Hi;
+    default_factors(cb, n, m, B, k, nullptr, nullptr, &W_init, &H_init, Wi, Hi);
+    CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
+    CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
+    CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    return NNLM_OK;
+}
+
+// nnlm_c_nnmf_batch on a sparse A (canonical CSC, absent entries zeros): the matrix goes through nnlm_set_matrix_csc_batch
+extern "C" int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned B, const unsigned *k,
+                                     const double *W_init, const double *H_init, const double alpha[3], const double beta[3], unsigned max_iter,
+                                     double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                                     int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                                     double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                                     const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (any_null(colptr, k, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned))
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_batch: NULL argument");
+    int rc = batch_ranks(nullptr, "nnlm_c_nnmf_csc_batch", "members", B, k, [&] {
+        return (method >= 3 && method <= 4) ? fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_csc_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method)
+                                            : NNLM_OK;
+    });
+    if (rc != NNLM_OK) return rc;
+    OneShot os;
+    rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix_csc_batch(h, n, m, colptr, rowidx, x); });
     if (rc != NNLM_OK) return rc;
     nnlm_handle *h = os.h;
     std::vector<double> Wi, Hi;

@@ -1,6 +1,7 @@
-// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_na.h, k_sparse_kl.h), see tu_sweepq.h.
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_kl.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
+#include "k_sparse_batch.h"
 #include "k_sparse_na.h"
 #include "k_sparse_kl.h"
 
@@ -69,6 +70,43 @@ void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, c
                           hipStream_t st)
 {
     sp_err_final_kernel<<<1, 256, 0, st>>>(s, GW, GH, wsum, hsum, k, KP, out);
+}
+
+// ---- batched factorisation (k_sparse_batch.h) ----
+// Wavefronts of sp_batch_errors_kernel: one per 64 x SPB_TILE non-zeros (rounded up), at most 16 per CU; nnlm_spb_chunk then gives each
+// whole rows of 64, so the shares are not tiles (nnz = 257: two wavefronts, 192 + 65).  A function of nnz and the CU count only: the
+// sums of a member do not depend on how many members or coordinates the batch holds.
+int nnlm_spb_waves(long long nnz, int cus)
+{
+    long long waves = (nnz + 64LL * SPB_TILE - 1) / (64LL * SPB_TILE);
+    const long long cap = 16LL * (cus > 0 ? cus : 256);
+    if (waves > cap) waves = cap;
+    if (waves < 1) waves = 1;
+    return (int)waves;
+}
+// a wavefront's share of the non-zeros: whole rows of 64 (its lanes' reads stay aligned)
+long long nnlm_spb_chunk(long long nnz, int nwaves)
+{
+    const long long c = (nnz + nwaves - 1) / nwaves;
+    return c < 1 ? 64 : (c + 63) / 64 * 64;
+}
+// partial: [3 B][nblk], nblk = (nwaves + 3) / 4 workgroups
+void nnlm_tu_sp_batch_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nwaves,
+                             const double *Wrow, const double *Hrow, int KP, const int *off, int B, unsigned long long amask, double *partial,
+                             hipStream_t st)
+{
+    const int nblk = (nwaves + 3) / 4;
+    if (f64)
+        sp_batch_errors_kernel<double><<<nblk, 256, 0, st>>>(ptr, idx, (const double *)val, ncols, nnz, chunk, nwaves, Wrow, Hrow, KP, off, B, amask,
+                                                             partial, nblk);
+    else
+        sp_batch_errors_kernel<float><<<nblk, 256, 0, st>>>(ptr, idx, (const float *)val, ncols, nnz, chunk, nwaves, Wrow, Hrow, KP, off, B, amask,
+                                                            partial, nblk);
+}
+void nnlm_tu_sp_batch_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, const int *off, int B, int KP,
+                            unsigned long long amask, double *out, hipStream_t st)
+{
+    sp_batch_final_kernel<<<B, 256, 0, st>>>(s, GW, GH, wsum, hsum, off, KP, amask, out);
 }
 
 // ---- absent entries missing (k_sparse_na.h) ----

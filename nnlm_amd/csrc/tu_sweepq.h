@@ -43,6 +43,18 @@ void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *part
 // out[0] = sum of squares, out[1] = KL sum over all n x m entries from s = {S1, S2, S3}, the Grams and the factors' sums (k_sparse.h)
 void nnlm_tu_sp_err_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP, double *out,
                           hipStream_t st);
+// Batched factorisation on a sparse A (k_sparse_batch.h): the three sums over the non-zeros of every member b < B with bit b of amask
+// set, off [B + 1] (device) the members' first coordinates in the row copies Wrow [n][KP], Hrow [m][KP]; nwaves wavefronts of chunk
+// non-zeros each (nnlm_spb_waves, nnlm_spb_chunk: functions of nnz and the CU count only); partial [3 B][(nwaves + 3) / 4]
+void nnlm_tu_sp_batch_errors(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk, int nwaves,
+                             const double *Wrow, const double *Hrow, int KP, const int *off, int B, unsigned long long amask, double *partial,
+                             hipStream_t st);
+#define SPB_BATCH_MAX 64 // members of a batch: BATCH_MAX of k_batch.h (the kernel keeps a slot per member and wavefront in LDS)
+int nnlm_spb_waves(long long nnz, int cus);
+long long nnlm_spb_chunk(long long nnz, int nwaves);
+// out[2 b], out[2 b + 1] = member b's sum of squares and KL sum over all n x m entries from s [3 B], the stacked Grams and coordinate sums
+void nnlm_tu_sp_batch_final(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, const int *off, int B, int KP,
+                            unsigned long long amask, double *out, hipStream_t st);
 
 // Sparse A whose absent entries are missing (k_sparse_na.h, tu_sparse.hip): per-column Grams over the stored rows of columns [c0, c1)
 #define SPG_SEG 2048 // stored entries per segment: a longer column is summed in segments of its own, added in order by the fix-up
