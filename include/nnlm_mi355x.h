@@ -201,8 +201,21 @@ int nnlm_set_matrix_csc_batch(nnlm_handle *h, int n, int m, const long long *col
  * nnlm_debug_alloc_limit) bytes.  nnlm_matrix_info: n_non_missing = nnz, any_missing = (nnz < n m), kl_const over the stored entries;
  * nnlm_errors' sums run over the stored entries.  Works on such a handle: nnlm_half_step, nnlm_iterate, nnlm_run, nnlm_errors, methods 1
  * and 2, both modes, ranks 1..64, masks and known profiles.  NNLM_ERR_UNSUPPORTED: methods 3 and 4, rank > 64 (nnlm_set_factors),
- * nnlm_comm_init, nnlm_debug_partial and the batch entries. */
+ * nnlm_comm_init, nnlm_debug_partial and the batch entries (their door: nnlm_set_matrix_csc_missing_batch). */
 int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* nnlm_set_matrix_csc_missing for restarts, rank sweeps and rank selection: the same contract and validation, with an optional HOLD-OUT
+ * pattern ho_colptr[m + 1] / ho_rowidx[] -- a canonical CSC pattern that must be a subset of the stored pattern; ho_colptr == NULL: no
+ * hold-out set.  Held-out entries leave the stored set on the host before the CSC and the CSR are built; their values stay on the device
+ * (mode's type) for nnlm_holdout_errors.  The handle is then the sparse-missing handle of the TRAINING entries: nnlm_matrix_info, the
+ * segment layout and every solo call are those of nnlm_set_matrix_csc_missing on the training CSC, bit for bit.  It ALSO accepts
+ * nnlm_set_factors_batch, nnlm_run_batch and nnlm_get_factors_batch: per half-step ONE SpMM at the stacked rank and, per column chunk,
+ * ONE launch for the per-column Grams of all members (each bit-equal to the solo Gram at the member's rank); per trace iteration ONE
+ * walk over the stored entries for the error sums of all members.  The batch's own limits hold (methods 1 and 2, rank sum <= 64, no
+ * masks, no communicator).  nnlm_get_info: "matrix_absent_missing" = 1, "sparse_batch" = 1, "matrix_holdout" = the held-out count
+ * (0 is legal; -1 without a pattern), "sp_gram_batch_pairs".  NNLM_ERR_ARG, naming the first offender: a held-out position that is
+ * not stored, a non-canonical pattern, every stored entry held out. */
+int nnlm_set_matrix_csc_missing_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x,
+                                      const long long *ho_colptr, const int *ho_rowidx);
 /* Dense finite A (fp64, column-major) with a HOLD-OUT set: colptr[m + 1] / rowidx[] is a canonical CSC pattern (the validation of
  * nnlm_set_matrix_csc; an empty pattern is legal) of the entries kept out of the fit.  The handle is then in the state nnlm_set_matrix
  * leaves for A with NA at the pattern -- missing bits, 0 in every resident copy, n_non_missing / any_missing / kl_const over the
@@ -215,7 +228,8 @@ int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *c
 int nnlm_set_matrix_holdout(nnlm_handle *h, const double *A, int n, int m, const long long *colptr, const int *rowidx);
 /* Errors of the current factors on the held-out entries: mse[b] = mean (a - wh)^2, mkl[b] = mean (a + eps) log((a + eps) / (wh + eps))
  * - a + wh, for the B members of a batch (arrays of length B) or the solo factors (length 1).  fp64 sums in a fixed order, no
- * atomics; synchronises.  An empty hold-out set gives NaN for both; NNLM_ERR_ARG on a handle without a hold-out set. */
+ * atomics; synchronises.  An empty hold-out set gives NaN for both; NNLM_ERR_ARG on a handle without a hold-out set.  Hold-out sets
+ * come from nnlm_set_matrix_holdout (dense A) and nnlm_set_matrix_csc_missing_batch (sparse A, absent entries missing). */
 int nnlm_holdout_errors(nnlm_handle *h, double *mse, double *mkl);
 /* ------------------------------------------------------------------------------------------
  * Scores of the current factors without forming W H.  Both entries run on a handle that holds a matrix (any kind: it gives n and m)
@@ -308,6 +322,8 @@ int nnlm_sync(nnlm_handle *h);
  * Missing entries are accepted in ONE form: a hold-out handle (nnlm_set_matrix_holdout).  Every member then solves each column with the
  * Gram over that column's observed rows, as a solo missing-value run does, behind the same single cross product; the traces' sums
  * run over the training entries.  A matrix that arrived with NA / NaN / Inf through nnlm_set_matrix stays refused.
+ * A sparse A is accepted through two doors: nnlm_set_matrix_csc_batch (absent entries zeros) and nnlm_set_matrix_csc_missing_batch
+ * (absent entries missing, with or without a hold-out set).
  * ---------------------------------------------------------------------------------------- */
 /* k[B] ranks; W = the members' n x k[b] blocks one after another (column-major each), H = their k[b] x m blocks one after another;
  * NULL = zeros.  Replaces the handle's factors (nnlm_set_factors ends a batch). */
@@ -338,6 +354,17 @@ int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, const int *rowi
                           int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
                           double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
                           const nnlm_callbacks *cb);
+
+/* nnlm_c_nnmf_csc_batch on a sparse A whose absent entries are MISSING (nnlm_set_matrix_csc_missing_batch), with an optional hold-out
+ * pattern ho_colptr / ho_rowidx after x (ho_colptr NULL: none) and holdout_mse[B], holdout_mkl[B] at the end: nnlm_holdout_errors of the
+ * final factors, NaN without a set or with an empty one.  The default inits are drawn in the same order. */
+int nnlm_c_nnmf_csc_missing_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, const long long *ho_colptr,
+                                  const int *ho_rowidx, unsigned B, const unsigned *k, const double *W_init, const double *H_init,
+                                  const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int n_threads, int verbose,
+                                  int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out,
+                                  double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                                  int *n_trace, unsigned *n_iteration, int *warned, double *holdout_mse, double *holdout_mkl,
+                                  const nnlm_callbacks *cb);
 
 /* nnlm_c_nnmf_batch on A with the pattern (colptr, rowidx) held out (nnlm_set_matrix_holdout), + holdout_mse[B], holdout_mkl[B]:
  * nnlm_holdout_errors of the final factors. */
@@ -424,7 +451,9 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),
  * "sp_gram_workers" (sp_gram_kernel workers of the last half-step whose absent entries are missing, summed over its column chunks),
- * "sparse_batch" (1 after nnlm_set_matrix_csc_batch, else 0), "sp_batch_waves" (wavefronts of one sp_batch_errors_kernel launch on the
+ * "sp_gram_batch_pairs" (upper 16 x 16 tile pairs of the stacked Gram that the sp_gram_batch_kernel launches of the last batch half-step
+ * on a handle loaded by nnlm_set_matrix_csc_missing_batch formed: those meeting an ACTIVE member's diagonal block; 0 none yet),
+ * "sparse_batch" (1 after nnlm_set_matrix_csc_batch or nnlm_set_matrix_csc_missing_batch, else 0), "sp_batch_waves" (wavefronts of one sp_batch_errors_kernel launch on the
  * resident sparse matrix -- a function of its non-zeros and the CU count only --, 0 without one), "sparse_kl" (1 after nnlm_set_matrix_csc_kl, else 0), "sparse_kl_form_w" / "sparse_kl_form_h" (KL solver forms of the last W / H half-step on
  * such a handle: bit 0 = sp_kl_solve_kernel ran, a wavefront per line of at most "sparse_kl_short_max" stored entries; bit 1 =
  * sp_kl_solve_long_kernel ran, a workgroup per longer line; -1 none yet). */

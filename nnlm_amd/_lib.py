@@ -41,6 +41,7 @@ EXPORTS = [
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
     "nnlm_predict_entries", "nnlm_top_n",
     "nnlm_set_matrix_csc_batch", "nnlm_c_nnmf_csc_batch",
+    "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
 ]
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
 BY = {"column": 0, "row": 1}
@@ -181,6 +182,11 @@ def load():
     lib.nnlm_c_nnmf_csc_batch.argtypes = [C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnmf_batch.argtypes[3:]
     lib.nnlm_set_matrix_csc_batch.restype = C.c_int
     lib.nnlm_set_matrix_csc_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes
+    lib.nnlm_set_matrix_csc_missing_batch.restype = C.c_int
+    lib.nnlm_set_matrix_csc_missing_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes + [lp, ip]
+    lib.nnlm_c_nnmf_csc_missing_batch.restype = C.c_int
+    lib.nnlm_c_nnmf_csc_missing_batch.argtypes = ([C.c_int, C.c_int, lp, ip, dp, lp, ip] + lib.nnlm_c_nnmf_batch.argtypes[3:-1]
+                                                  + [dp, dp, C.POINTER(Callbacks)])
     lib.nnlm_set_matrix_holdout.restype = C.c_int
     lib.nnlm_set_matrix_holdout.argtypes = [vp, dp, C.c_int, C.c_int, lp, ip]
     lib.nnlm_holdout_errors.restype = C.c_int
@@ -502,8 +508,32 @@ def c_nnmf_csc_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_it
                         method, trace, callbacks, _csc=(n, m, ptr, idx, val))
 
 
+def c_nnmf_csc_missing_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+                             inner_max_iter, inner_rel_tol, method, trace, callbacks=None, holdout=None):
+    """c_nnmf_csc_batch with the absent entries of A MISSING (nnlm_c_nnmf_csc_missing_batch).  holdout: None or a CSC pattern
+    (indptr[m + 1], indices), a subset of the stored pattern, kept out of the fit.  Every member's dict carries holdout_mse and
+    holdout_mkl (NaN without a hold-out set or with an empty one)."""
+    n, m = (int(v) for v in shape)
+    ptr, idx, val = _csc_arrays(indptr, indices, data)
+    ho = _holdout_pattern(holdout, m)
+    return c_nnmf_batch(None, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol,
+                        method, trace, callbacks, _csc=(n, m, ptr, idx, val), _csc_missing=(ho,))
+
+
+def _holdout_pattern(holdout, m):
+    """None, or the (indptr, indices) of a hold-out pattern over m columns in the types of the C ABI."""
+    if holdout is None:
+        return None
+    ptr, idx = _pattern_arrays(*holdout)
+    if ptr.size != m + 1:
+        raise NnlmError(ERR_ARG, f"the hold-out pattern has {ptr.size} column pointers, A has {m} columns")
+    if idx.size < int(ptr[-1]):
+        raise NnlmError(ERR_ARG, "the hold-out pattern has fewer row indices than its last column pointer")
+    return ptr, idx
+
+
 def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
-                 trace, callbacks=None, _holdout=None, _csc=None):
+                 trace, callbacks=None, _holdout=None, _csc=None, _csc_missing=None):
     """Batched c_nnmf (nnlm_c_nnmf_batch): member b has rank ks[b] and starts from W[b] (n x k_b), H[b] (k_b x m) -- either list may
     be None for the library's default init.  Returns one c_nnmf-style dict per member."""
     lib = load()
@@ -527,7 +557,12 @@ def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose
             int(method), int(trace) & 0xFFFFFFFF, _dp(Wo), _dp(Ho), _dp(mse), _dp(mkl), _dp(terr), _dp(ep), _ip(n_trace),
             n_it.ctypes.data_as(C.POINTER(C.c_uint)), _ip(warned)]
     cbp = C.byref(callbacks) if callbacks is not None else None
-    if _csc is not None:
+    if _csc_missing is not None:
+        ho = _csc_missing[0]
+        hmse, hmkl = np.zeros(B), np.zeros(B)
+        rc = lib.nnlm_c_nnmf_csc_missing_batch(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), _lp(ho[0]) if ho else None,
+                                               _ip(ho[1]) if ho else None, *args, _dp(hmse), _dp(hmkl), cbp)
+    elif _csc is not None:
         rc = lib.nnlm_c_nnmf_csc_batch(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), *args, cbp)
     elif _holdout is None:
         rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, *args, cbp)
@@ -538,7 +573,7 @@ def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose
     out = _batch_traces(ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned)
     for o, Wb, Hb in zip(out, *_batch_split(Wo, Ho, ks, n, m)):
         o["W"], o["H"] = Wb, Hb
-    if _holdout is not None:
+    if _holdout is not None or _csc_missing is not None:
         for b, o in enumerate(out):
             o["holdout_mse"], o["holdout_mkl"] = float(hmse[b]), float(hmkl[b])
     return out
@@ -689,6 +724,17 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc_missing(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_missing_batch(self, indptr, indices, data, shape, holdout=None):
+        """set_matrix_csc_missing for restarts, rank sweeps and rank selection: the same sparse-missing handle (of the entries left after
+        taking out the optional hold-out pattern holdout = (indptr[m + 1], indices), a subset of the stored pattern), which also accepts
+        set_factors_batch / run_batch and, with a hold-out set, holdout_errors."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        ho = _holdout_pattern(holdout, m)
+        self._ck(self._lib.nnlm_set_matrix_csc_missing_batch(self._h, n, m, _lp(ptr), _ip(idx), _dp(val), _lp(ho[0]) if ho else None,
+                                                             _ip(ho[1]) if ho else None))
         self.n, self.m = n, m
 
     def set_matrix_holdout(self, A, indptr, indices):

@@ -545,7 +545,13 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     ``sparse_batch`` = True admits a sparse A (an object with tocsc(); absent entries are zeros): it is made canonical once for all
     members, every half-step is one SpMM over the non-zeros at the stacked rank and every trace iteration one walk over them.  The other
     limits stay, and absent = 'missing' is refused.  With a dense A the flag changes nothing; the default refuses a sparse A as before.
+
+    ``sparse_batch`` = "missing" takes a sparse A whose absent entries are MISSING (a score matrix; every stored entry, an explicit zero
+    included, is an observation): per half-step one SpMM and, per column chunk, one launch for the per-column Grams of all members.
+    check_k's bound is the fewest stored entries of a row or a column, as for nnmf(absent = 'missing'); ``absent``, if given with it, must
+    be 'missing'; a dense A is refused.
     """
+    missing_door = _sparse_batch_arg(sparse_batch, "nnmf_batch")
     sparse_batch = bool(sparse_batch)
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
@@ -562,7 +568,10 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
     if is_sparse(A) and not sparse_batch:
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
-    if is_sparse(A) and _match_arg(nnmf_options.get("absent", "zero"), ("zero", "missing"), "absent") == "missing":
+    if missing_door:
+        _missing_door_checks(A, nnmf_options, unsupported)
+        nnmf_options = dict(nnmf_options, absent="missing")
+    elif is_sparse(A) and _match_arg(nnmf_options.get("absent", "zero"), ("zero", "missing"), "absent") == "missing":
         raise unsupported("absent = 'missing' is not supported by the batched factorisation of a sparse A (sparse_batch = True): "
                           "absent entries are zeros")
     if sum(ks) > _lib.BATCH_MAX:
@@ -585,13 +594,33 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     if on_device:  # one ingest shared by all members; the handle then runs the batch (what nnlm_c_nnmf_batch does around a host A)
         h = _lib.Handle(_device_index(A), _env_precision())
     try:
-        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h)
+        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door)
     finally:
         if h is not None:
             h.close()
 
 
-def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
+def _sparse_batch_arg(sparse_batch, who):
+    """True when sparse_batch is the string "missing" (the door of a sparse A whose absent entries are missing); any other string is an
+    argument error, anything else is the flag it has always been."""
+    if isinstance(sparse_batch, str):
+        if sparse_batch != "missing":
+            raise _lib.NnlmError(_lib.ERR_ARG, "%s: sparse_batch must be False, True or 'missing' (got %r)" % (who, sparse_batch))
+        return True
+    return False
+
+
+def _missing_door_checks(A, nnmf_options, unsupported):
+    """sparse_batch = 'missing': a sparse A, and `absent`, if given, 'missing'."""
+    if not is_sparse(A):
+        raise unsupported("sparse_batch = 'missing' needs a sparse A (an object with tocsc()): the missing entries of a dense matrix of "
+                          "the batched factorisation come from a hold-out set only")
+    if _match_arg(nnmf_options.get("absent", "missing"), ("zero", "missing"), "absent") != "missing":
+        raise unsupported("absent = 'zero' contradicts sparse_batch = 'missing' (the batched factorisation of a sparse A whose absent "
+                          "entries are missing); use sparse_batch = True for absent entries that are zeros")
+
+
+def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False):
     """nnmf_batch behind its argument checks; h: the handle of a device A (None for a host A)."""
     B = len(ks)
     prep, Ws, Hs, mat = [], [], [], None
@@ -599,6 +628,8 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
         mat = _device_matrix(A, h)
         if h.matrix_info()["any_missing"]:
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
+    elif missing_door:  # (canonical CSC once for all members; check_k's bound: the fewest stored entries of a line)
+        mat = _nnmf_matrix_missing(A, "mse")
     elif is_sparse(A):  # (sparse_batch = True: canonical CSC once for all members; check_k's bound is min(n, m))
         c = _sparse_input(A, "A", "mse")
         mat = dict(A=c, n=c.shape[0], m=c.shape[1], min_k=min(c.shape))
@@ -615,7 +646,9 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h):
     a0 = prep[0][0]
     cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    if isinstance(a0[0], CSC):
+    if missing_door:
+        outs = _lib.c_nnmf_csc_missing_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+    elif isinstance(a0[0], CSC):
         outs = _lib.c_nnmf_csc_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     elif h is None:
         outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
@@ -676,7 +709,53 @@ def _env_precision():
     return _lib.PREC_F32 if os.environ.get("NNLM_PRECISION") in ("f32", "fp32", "0") else _lib.PREC_F64
 
 
-def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
+def _holdout_pattern_stored(holdout, c, rng):
+    """nnmf_cv's hold-out set on a sparse A whose absent entries are missing, as positions into the stored entries of the canonical CSC c
+    (sorted, unique).  A fraction in (0, 1): round(f nnz) stored entries drawn uniformly without replacement from `rng`; a {"indptr",
+    "indices"} dict (what nnmf_cv returned): that pattern again, which must be canonical and a subset of the stored pattern."""
+    n, m = c.shape
+    nnz = int(c.indices.size)
+    if isinstance(holdout, dict):
+        ptr, idx = np.asarray(holdout["indptr"], dtype=np.int64), np.asarray(holdout["indices"], dtype=np.int64)
+        if ptr.shape != (m + 1,) or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] != idx.size:
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: the hold-out pattern needs indptr of length ncol + 1, non-decreasing from 0 to len(indices)")
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: the hold-out pattern has a row index out of range")
+        hkey = np.repeat(np.arange(m, dtype=np.int64), np.diff(ptr)) * n + idx  # column-major position j n + i
+        if np.any(np.diff(hkey) <= 0):
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: the hold-out pattern is not canonical (row indices strictly increasing within a column)")
+        skey = np.repeat(np.arange(m, dtype=np.int64), np.diff(c.indptr)) * n + np.asarray(c.indices, dtype=np.int64)
+        pos = np.searchsorted(skey, hkey)
+        bad = (pos >= nnz) | (skey[np.minimum(pos, max(nnz - 1, 0))] != hkey) if nnz else np.ones(hkey.size, dtype=bool)
+        if bad.any():
+            e = int(np.flatnonzero(bad)[0])
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: held-out entry %d (row %d, column %d) is not a stored entry of A"
+                                 % (e, int(hkey[e] % n), int(hkey[e] // n)))
+        return pos
+    if np.ndim(holdout) != 0:
+        raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: on a sparse A, holdout must be a fraction in (0, 1) of the stored entries or the holdout "
+                                           "dict of an earlier result")
+    f = float(holdout)
+    if not 0.0 < f < 1.0:
+        raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: holdout must be a fraction in (0, 1) of the stored entries (got %r)" % (holdout,))
+    return np.sort(rng.choice(nnz, size=int(round(f * nnz)), replace=False))
+
+
+def _split_stored(c, pos):
+    """The canonical CSC c without its stored entries at the (sorted) positions pos, and the pattern of those entries:
+    (training CSC, (indptr int64, indices int32))."""
+    n, m = c.shape
+    cols = np.repeat(np.arange(m, dtype=np.int64), np.diff(c.indptr))
+    held = np.zeros(c.indices.size, dtype=bool)
+    held[pos] = True
+    hptr, tptr = np.zeros(m + 1, dtype=np.int64), np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols[held], minlength=m), out=hptr[1:])
+    np.cumsum(np.bincount(cols[~held], minlength=m), out=tptr[1:])
+    train = CSC(tptr, np.ascontiguousarray(c.indices[~held], dtype=np.int32), np.ascontiguousarray(c.data[~held]), (n, m))
+    return train, (hptr, np.ascontiguousarray(c.indices[held], dtype=np.int32))
+
+
+def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, sparse_batch=False, **nnmf_options):
     """Rank selection on held-out entries (the reference's vignette method): a share of the entries of the dense matrix A is kept out
     of the fit, every member (``k`` and ``nrun`` as in nnmf_batch) is fitted on the rest by the batched factorisation, and the member
     whose reconstruction of the held-out entries has the lowest mean squared error is ``best``.
@@ -688,8 +767,15 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
     Refused as by nnmf_batch (NnlmError, NNLM_ERR_UNSUPPORTED): loss = 'mkl', masks, known profiles, a sparse A, an A with non-finite
     entries; a single rank above 64.  The arithmetic mode is NNLM_PRECISION's, as for nnmf().
 
+    ``sparse_batch`` = "missing" takes a sparse A whose absent entries are MISSING (a ratings matrix): ``holdout`` is then a fraction of
+    the STORED entries (round(f nnz) of them, drawn without replacement from ``rng`` before any init) or the ``holdout`` dict of an earlier
+    result (a subset of the stored pattern); check_k's bound is the fewest training entries of a row or a column, as for
+    nnmf(absent = 'missing'); nothing n x m sized is formed.  ``absent``, if given with it, must be 'missing'.  Without the flag a sparse
+    A is refused as before.
+
     Returns a dict: fits (nnmf results with holdout_mse / holdout_mkl added), k (rank per member), holdout_mse, holdout_mkl (arrays),
     best (index of the lowest holdout_mse, the first on ties), holdout ({"indptr", "indices", "shape"}: the pattern used)."""
+    missing_door = _sparse_batch_arg(sparse_batch, "nnmf_cv")
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
     if init is not None:
@@ -703,14 +789,21 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
         raise unsupported("known profiles (W0 / H0) are not supported by the batched factorisation")
     if _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss") != "mse":
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
-    if is_sparse(A):
+    if is_sparse(A) and not missing_door:
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    if missing_door:
+        _missing_door_checks(A, nnmf_options, unsupported)
+        nnmf_options = dict(nnmf_options, absent="missing")
     _refuse_device(A, "nnmf_cv", "A")  # (the hold-out pattern is applied in the upload's host staging pass)
     batches = _pack_batches(ks)
-    mat = _nnmf_matrix(A, "mse")
-    if not np.isfinite(mat["A"]).all():
-        raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation takes missing entries through the "
-                          "hold-out set only")
+    if missing_door:
+        full = _sparse_input(A, "A", "mse", "missing")  # (canonical CSC, once)
+        mat = dict(A=full, n=full.shape[0], m=full.shape[1], min_k=min(full.shape))
+    else:
+        mat = _nnmf_matrix(A, "mse")
+        if not np.isfinite(mat["A"]).all():
+            raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation takes missing entries through the "
+                              "hold-out set only")
     n, m = mat["n"], mat["m"]
     if init is not None:
         for b, x in enumerate(init):
@@ -719,11 +812,21 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
                     raise _lib.NnlmError(_lib.ERR_ARG, "init[%d]['%s'] has shape %s, member %d (rank %d) needs %s"
                                          % (b, key, np.shape(x[key]), b, ks[b], shp))
     g = rng or np.random.default_rng()
-    ptr, idx = _holdout_pattern(holdout, n, m, g)
-    # check.k (R/nnmf.R:157-164) on the training entries: k + 1 of them in every row and column
-    row_obs = m - np.bincount(idx, minlength=n)
-    col_obs = n - np.diff(ptr)
-    mat = dict(mat, min_k=min(mat["min_k"], int(row_obs.min()) - 1, int(col_obs.min()) - 1))
+    if missing_door:
+        pos = _holdout_pattern_stored(holdout, full, g)
+        if full.indices.size and pos.size == full.indices.size:
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_cv: every stored entry of A is held out; nothing is left to fit")
+        train, (ptr, idx) = _split_stored(full, pos)
+        # check.k on the training entries, the bound of nnmf(absent = 'missing'): the fewest stored entries of a row or a column
+        row_obs, col_obs = _stored_counts(train)
+        min_k = min(n, m) if train.indices.size == n * m else min(n, m, int(row_obs.min()), int(col_obs.min()))
+        mat = dict(mat, min_k=min_k)
+    else:
+        ptr, idx = _holdout_pattern(holdout, n, m, g)
+        # check.k (R/nnmf.R:157-164) on the training entries: k + 1 of them in every row and column
+        row_obs = m - np.bincount(idx, minlength=n)
+        col_obs = n - np.diff(ptr)
+        mat = dict(mat, min_k=min(mat["min_k"], int(row_obs.min()) - 1, int(col_obs.min()) - 1))
     opts = dict(nnmf_options)
     opts.setdefault("verbose", 0)
     prep, Ws, Hs = [], [], []
@@ -738,7 +841,10 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, **nnmf_options):
     cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
     fits, hmse, hmkl = [], np.zeros(B), np.zeros(B)
     with _lib.Handle(int(os.environ.get("NNLM_DEVICE", "0") or 0), _env_precision()) as h:
-        h.set_matrix_holdout(mat["A"], ptr, idx)
+        if missing_door:  # (one upload: the stored entries and the pattern; the library takes the held-out ones out)
+            h.set_matrix_csc_missing_batch(*full, holdout=(ptr, idx))
+        else:
+            h.set_matrix_holdout(mat["A"], ptr, idx)
         for b0, b1 in batches:
             t0 = time.perf_counter()
             h.set_factors_batch(ks[b0:b1], Ws[b0:b1], Hs[b0:b1])

@@ -27,7 +27,8 @@
 
 #define SPB_TILE 4 // non-zeros a lane holds in registers across the member loop
 
-template <typename T>
+// MISS (absent entries are missing, nnlm_set_matrix_csc_missing_batch): S2 += wh instead of wh^2, as sp_errors_kernel<T, LW, true>
+template <typename T, bool MISS = false>
 __global__ __launch_bounds__(256) void sp_batch_errors_kernel(const long long *__restrict__ ptr, const int *__restrict__ idx, const T *__restrict__ val,
                                                               int ncols, long long nnz, long long chunk, int nwaves,
                                                               const double *__restrict__ Wrow, const double *__restrict__ Hrow, int KP,
@@ -88,7 +89,8 @@ __global__ __launch_bounds__(256) void sp_batch_errors_kernel(const long long *_
                     const double lg = nnlm_log_pos(wh[u] + NNLM_TINY);
                     if (ok[u]) {
                         s1 = __builtin_fma(r, r, s1);
-                        s2 = __builtin_fma(wh[u], wh[u], s2);
+                        if (MISS) s2 += wh[u];
+                        else s2 = __builtin_fma(wh[u], wh[u], s2);
                         s3 += -(av[u] + NNLM_TINY) * lg;
                     }
                 }
@@ -144,4 +146,13 @@ __global__ __launch_bounds__(256) void sp_batch_final_kernel(const double *__res
         out[2 * mb] = s[3 * mb] + (zeros > 0.0 ? zeros : 0.0);
         out[2 * mb + 1] = s[3 * mb + 2] + SW;
     }
+}
+
+// Absent entries missing: member blockIdx.x * 64 + lane closes as sp_err_final_missing_kernel does (the Grams play no part)
+__global__ void sp_batch_final_missing_kernel(const double *__restrict__ s, int B, unsigned long long amask, double *__restrict__ out)
+{
+    const int mb = blockIdx.x * 64 + threadIdx.x;
+    if (mb >= B || !((amask >> mb) & 1ull)) return;
+    out[2 * mb] = s[3 * mb];
+    out[2 * mb + 1] = s[3 * mb + 2] + s[3 * mb + 1];
 }

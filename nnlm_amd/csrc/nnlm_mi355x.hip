@@ -235,6 +235,8 @@ struct nnlm_handle {
     double *bres = nullptr;                 // [8 bB]: {sum sq, sum KL} per member, then 3 W and 3 H penalty sums per member
     double *bsp_Hrow = nullptr;             // sparse A: [m][KP] fp64 rows of H (the rows of W: sp_Wrow), error block
     double *bsp_part = nullptr;             // sparse A: [3 bB][workgroups] partial sums of sp_batch_errors_kernel, then [3 bB] their sums
+    int bspg_pairs = 0;                     // sparse A, absent = missing: tile pairs the last half-step's sp_gram_batch_kernel launches formed
+                                            // (nnlm_get_info "sp_gram_batch_pairs")
 
     // hold-out set (nnlm_set_matrix_holdout): the resident matrix is A with NA at the pattern (the dense NA layout
     // above); the held-out entries themselves stay here as a CSC -- values in the mode's type, the column of every entry beside its row
@@ -655,6 +657,7 @@ static void free_batch(nnlm_handle *h)
     h->bG = h->bpart = h->bres = h->bsp_Hrow = h->bsp_part = nullptr;
     h->bsweeps = nullptr;
     h->bpart_elems = 0;
+    h->bspg_pairs = 0;
     h->bB = 0;
     h->bk.clear();
     h->boff.clear();
@@ -1371,9 +1374,9 @@ static int spkl_layout(nnlm_handle *h, int o, const long long *ptr, int ncols)
     return NNLM_OK;
 }
 
-// nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is
-static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing,
-                               const char *who, bool kl = false)
+// The CSC contract of the sparse set-matrix entries, checked in the order they have always reported it (first offender named)
+static int csc_check(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing, const char *who,
+                     bool kl)
 {
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
     if (n <= 0 || m <= 0 || !colptr) return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix with colptr[m + 1] (n=%d, m=%d)", who, n, m);
@@ -1384,8 +1387,6 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
     const long long nnz = colptr[m];
     if (nnz > 0 && (!rowidx || !x)) return fail(h, NNLM_ERR_ARG, "%s: rowidx / x is NULL with nnz = %lld", who, nnz);
     if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "%s: nnz = %lld exceeds n * m", who, nnz);
-    std::vector<long long> rptr((size_t)n + 1, 0);
-    double over = 0.0, mx = 0.0, klc = 0.0;
     for (int j = 0; j < m; j++)
         for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
             const int i = rowidx[e];
@@ -1400,6 +1401,23 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
                                                               "(use nnlm_set_matrix for NA data)", who, e, i, j);
             if (kl && v < 0.0)
                 return fail(h, NNLM_ERR_ARG, "%s: entry %lld (row %d, column %d) is negative (%g); KL loss needs non-negative data", who, e, i, j, v);
+        }
+    return NNLM_OK;
+}
+
+// nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is
+static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing,
+                               const char *who, bool kl = false)
+{
+    const int rcc = csc_check(h, n, m, colptr, rowidx, x, absent_missing, who, kl);
+    if (rcc != NNLM_OK) return rcc;
+    const long long nnz = colptr[m];
+    std::vector<long long> rptr((size_t)n + 1, 0);
+    double over = 0.0, mx = 0.0, klc = 0.0;
+    for (int j = 0; j < m; j++)
+        for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
+            const int i = rowidx[e];
+            const double v = x[e];
             rptr[(size_t)i + 1]++;
             if (std::fabs(v) > 3.4028234663852886e38) over += 1.0;
             const double fv = std::fabs((double)(float)v);
@@ -1499,6 +1517,79 @@ extern "C" int nnlm_set_matrix_csc_batch(nnlm_handle *h, int n, int m, const lon
 {
     const int rc = set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_batch");
     if (rc == NNLM_OK) h->sp_batch = true;
+    return rc;
+}
+
+// The sparse-missing handle of nnlm_set_matrix_csc_missing that the batch entries also accept, with an optional
+// hold-out pattern (canonical CSC, a subset of the stored pattern; ho_colptr == NULL: none).  Held-out entries leave the stored set on the
+// host, before the CSC and the CSR are built: the resident matrix IS the plain upload of the training entries.  Their values stay in
+// ho_cptr / ho_ridx / ho_cidx / ho_val (the mode's type), as nnlm_set_matrix_holdout keeps them, for nnlm_holdout_errors.
+extern "C" int nnlm_set_matrix_csc_missing_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x,
+                                                 const long long *ho_colptr, const int *ho_rowidx)
+{
+    const char *who = "nnlm_set_matrix_csc_missing_batch";
+    if (!ho_colptr) {
+        const int rc = set_matrix_csc_impl(h, n, m, colptr, rowidx, x, true, who);
+        if (rc == NNLM_OK) h->sp_batch = true;
+        return rc;
+    }
+    int rc = csc_check(h, n, m, colptr, rowidx, x, true, who, false);
+    if (rc != NNLM_OK) return rc;
+    const long long nnz = colptr[m];
+    if (ho_colptr[0] != 0) return fail(h, NNLM_ERR_ARG, "%s: ho_colptr[0] = %lld, must be 0", who, ho_colptr[0]);
+    for (int j = 0; j < m; j++)
+        if (ho_colptr[j + 1] < ho_colptr[j]) return fail(h, NNLM_ERR_ARG, "%s: ho_colptr decreases at column %d", who, j);
+    const long long hn = ho_colptr[m];
+    if (hn > 0 && !ho_rowidx) return fail(h, NNLM_ERR_ARG, "%s: ho_rowidx is NULL with %lld held-out entries", who, hn);
+    // one merge per column: every held-out row must be a stored row of that column; what is not held out is the training set
+    std::vector<long long> tptr((size_t)m + 1, 0);
+    std::vector<int> tidx, hcol((size_t)hn);
+    std::vector<double> tval, hval((size_t)hn);
+    tidx.reserve((size_t)(nnz > hn ? nnz - hn : 0));
+    tval.reserve(tidx.capacity());
+    for (int j = 0; j < m; j++) {
+        long long e = colptr[j];
+        const long long e1 = colptr[j + 1];
+        for (long long g = ho_colptr[j]; g < ho_colptr[j + 1]; g++) {
+            const int i = ho_rowidx[g];
+            if (i < 0 || i >= n) return fail(h, NNLM_ERR_ARG, "%s: held-out row index %d out of range at entry %lld (column %d)", who, i, g, j);
+            if (g > ho_colptr[j] && i <= ho_rowidx[g - 1])
+                return fail(h, NNLM_ERR_ARG, "%s: held-out row indices of column %d are not strictly increasing (entry %lld)", who, j, g);
+            for (; e < e1 && rowidx[e] < i; e++) tidx.push_back(rowidx[e]), tval.push_back(x[e]);
+            if (e >= e1 || rowidx[e] != i)
+                return fail(h, NNLM_ERR_ARG, "%s: held-out entry %lld (row %d, column %d) is not a stored entry", who, g, i, j);
+            hcol[(size_t)g] = j;
+            hval[(size_t)g] = x[e++];
+        }
+        for (; e < e1; e++) tidx.push_back(rowidx[e]), tval.push_back(x[e]);
+        tptr[(size_t)j + 1] = (long long)tidx.size();
+    }
+    if (nnz > 0 && hn == nnz) return fail(h, NNLM_ERR_ARG, "%s: every stored entry is held out; nothing is left to fit", who);
+    rc = set_matrix_csc_impl(h, n, m, tptr.data(), tidx.data(), tval.data(), true, who);
+    if (rc != NNLM_OK) return rc;
+    h->sp_batch = true;
+    h->holdout = true;
+    h->ho_nnz = hn;
+    const size_t es = esize(h);
+    auto up = [&]() -> int {
+        HIPCHK(h, hipMalloc(&h->ho_cptr, (size_t)(m + 1) * 8));
+        HIPCHK(h, hipMalloc(&h->ho_ridx, (size_t)hn * 4 + 64));
+        HIPCHK(h, hipMalloc(&h->ho_cidx, (size_t)hn * 4 + 64));
+        HIPCHK(h, hipMalloc(&h->ho_val, (size_t)hn * es + 64));
+        HIPCHK(h, hipMemcpy(h->ho_cptr, ho_colptr, (size_t)(m + 1) * 8, hipMemcpyHostToDevice));
+        if (hn > 0) {
+            HIPCHK(h, hipMemcpy(h->ho_ridx, ho_rowidx, (size_t)hn * 4, hipMemcpyHostToDevice));
+            HIPCHK(h, hipMemcpy(h->ho_cidx, hcol.data(), (size_t)hn * 4, hipMemcpyHostToDevice));
+            if (h->prec == NNLM_PREC_F64) HIPCHK(h, hipMemcpy(h->ho_val, hval.data(), (size_t)hn * 8, hipMemcpyHostToDevice));
+            else {
+                std::vector<float> hf(hval.begin(), hval.end());
+                HIPCHK(h, hipMemcpy(h->ho_val, hf.data(), (size_t)hn * 4, hipMemcpyHostToDevice));
+            }
+        }
+        return NNLM_OK;
+    };
+    rc = up();
+    if (rc != NNLM_OK) free_matrix(h);
     return rc;
 }
 
@@ -3744,6 +3835,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
     else if (strcmp(key, "sp_workers") == 0) *value = (h->sparse && h->KP > 0) ? nnlm_sp_workers(h->nnz, h->KP, h->cus_device) : 0;
     else if (strcmp(key, "sp_gram_workers") == 0) *value = h->spg_workers;
+    else if (strcmp(key, "sp_gram_batch_pairs") == 0) *value = h->bspg_pairs;
     else if (strcmp(key, "topn_slices") == 0) *value = h->topn_slices;
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
@@ -4073,10 +4165,11 @@ static int batch_refusal(nnlm_handle *h, const char *who)
     if (h->sparse && h->sp_kl)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl) is not supported by the batched factorisation "
                                              "(dense A, square loss only)", who);
-    // (the door: a sparse matrix loaded by nnlm_set_matrix_csc_batch -- absent entries zeros, square loss -- passes)
-    if (h->sparse && !(h->sp_batch && !h->sp_missing))
+    // (the doors: a sparse matrix loaded by nnlm_set_matrix_csc_batch -- absent entries zeros, square loss -- or by
+    //  nnlm_set_matrix_csc_missing_batch -- absent entries missing -- passes)
+    if (h->sparse && !h->sp_batch)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
-    if (h->any_missing && !h->holdout) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
+    if (h->any_missing && !h->holdout && !h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
     if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: the batched factorisation runs on one GPU (no communicator)", who);
     return NNLM_OK;
 }
@@ -4161,6 +4254,98 @@ extern "C" int nnlm_get_factors_batch(nnlm_handle *h, double *W, double *H)
     return NNLM_OK;
 }
 
+// The tile pairs of sp_gram_batch_kernel (k_sparse_na_batch.h) for the active members of a stack: bit pi (upper pairs ta <= tb, ta-major,
+// NT = KP / 16 tiles a side) is set when the 16 x 16 pair meets some active member's diagonal block [off_b, off_b + k_b)^2; *tiles: the
+// coordinate tiles the set pairs touch
+static unsigned spg_batch_pairs(int NT, const std::vector<int> &off, const std::vector<char> &act, unsigned *tiles)
+{
+    unsigned pairs = 0, tl = 0;
+    int pi = 0;
+    for (int ta = 0; ta < NT; ta++)
+        for (int tb = ta; tb < NT; tb++, pi++)
+            for (size_t b = 0; b + 1 < off.size(); b++) {
+                if (!act[b]) continue;
+                const int lo = off[b], hi = off[b + 1]; // both tiles must hold a coordinate of the member
+                if (lo < 16 * ta + 16 && hi > 16 * ta && lo < 16 * tb + 16 && hi > 16 * tb) pairs |= 1u << pi, tl |= (1u << ta) | (1u << tb);
+            }
+    *tiles = tl;
+    return pairs;
+}
+
+// Steps 2 and 3 of a batch half-step on a sparse A whose absent entries are missing, behind sp_cross at the stacked KP:
+// chunk by chunk ONE sp_gram_batch_kernel launch (+ its fix-up) for the per-column Grams of all active members -- column c's slot holds
+// the members' own padded Grams one after another (goff_b = sum of KP_b'^2 in front of member b) -- then per active member the per-column
+// solver on its row block, exactly as half_step_sparse_missing launches it at rank k_b (Graw = the member's Gram inside the slot,
+// g_stride = the slot).  The Gram workers follow h->cus (the test hook's count): the Grams do not depend on it.
+static int batch_solve_sparse_missing(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+                                      const std::vector<char> &act)
+{
+    const int B = h->bB, o = s.which, KPs = h->KP, NT = h->NKQ;
+    const size_t es = esize(h);
+    std::vector<int> goff(B + 1, 0);
+    for (int b = 0; b < B; b++) {
+        const int kp = 16 * ((h->bk[b] + 15) / 16);
+        goff[b + 1] = goff[b] + kp * kp;
+    }
+    const size_t slot = (size_t)goff[B];
+    int rc = spg_prepare(h, o, slot);
+    if (rc != NNLM_OK) return rc;
+    SpGramBatchArgs g;
+    g.g.ptr = s.sp_ptr;
+    g.g.idx = s.sp_idx;
+    g.g.Y = h->sp_Y;
+    g.g.segoff = h->spg_segoff[o];
+    g.g.G = h->spg_buf; // [chunk columns][slot], then the chunk's segment slots
+    g.slot = slot;
+    g.pairs = spg_batch_pairs(NT, h->boff, act, &g.tiles);
+    for (int i = 0; i < 128; i++) g.tab[i] = i < 64 ? -1 : 0;
+    for (int b = 0; b < B; b++) {
+        if (!act[b]) continue;
+        const int kp = 16 * ((h->bk[b] + 15) / 16), ob = h->boff[b];
+        for (int i = ob; i < h->boff[b + 1]; i++) g.tab[i] = b, g.tab[64 + i] = goff[b] + (i - ob) * kp - ob;
+    }
+    h->bspg_pairs = __builtin_popcount(g.pairs);
+    const std::vector<long long> &hp = h->spg_hptr[o];
+    const int K = h->k, NKQ = h->NKQ, KP8 = h->KP8, MW = h->MW;
+    int workers = 0;
+    for (const SpgChunk &ch : h->spg_plan[o]) {
+        {
+            ProfScope ps(h, P_SP_GRAM);
+            g.g.c0 = ch.c0;
+            g.g.c1 = ch.c1;
+            g.g.seg = h->spg_buf + (size_t)(ch.c1 - ch.c0) * slot;
+            const long long nnz = hp[ch.c1] - hp[ch.c0];
+            g.g.nworkers = nnlm_spg_workers(nnz, h->cus);
+            workers += g.g.nworkers;
+            g.g.chunk = (nnz + g.g.nworkers - 1) / g.g.nworkers;
+            if (g.g.chunk < 1) g.g.chunk = 1;
+            nnlm_tu_sp_gram_batch(g, NT, h->prec == NNLM_PREC_F64, h->stream);
+            nnlm_tu_sp_gram_batch_fixup(g, h->spg_longc[o] + ch.l0, ch.l1 - ch.l0, KPs, h->stream);
+        }
+        ProfScope ps(h, s.prof_sweep);
+        for (int b = 0; b < B; b++) {
+            if (!act[b]) continue;
+            const int kb = h->bk[b], ob = h->boff[b];
+            h->k = kb, h->NKQ = (kb + 15) / 16, h->KP = 16 * h->NKQ, h->KP8 = round_up_i(kb, 8), h->MW = 1;
+            SweepArgs a = sweep_args(h, s, reg, inner_max_iter, inner_rel_tol, h->bsweeps + b);
+            a.Cx = h->Cx + (size_t)ob * s.ldc;
+            a.X = s.X + (size_t)ob * s.ldc;
+            a.Xout = s.Xout + (size_t)ob * s.ldc;
+            if (s.op) a.op = (char *)s.op + (size_t)ob * s.op_ld * es;
+            else a.op_mode = 0;
+            a.col0 = ch.c0;
+            a.ncols = ch.c1;
+            a.Graw = h->spg_buf + goff[b]; // (column col's Gram of this member: + (col - gcol0) * slot)
+            a.gcol0 = ch.c0;
+            launch_colsolve(h, method, a, slot);
+        }
+        h->k = K, h->NKQ = NKQ, h->KP = KPs, h->KP8 = KP8, h->MW = MW;
+    }
+    h->spg_chunks = (int)h->spg_plan[o].size();
+    h->spg_workers = workers;
+    return NNLM_OK;
+}
+
 // One half-step of every active member (act[b] != 0).  W is solved in place (no speculation, so no second buffer): a frozen member's
 // rows are never written.
 static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
@@ -4181,7 +4366,7 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     // Hold-out handle with a non-empty set: A has missing entries, every column solves with a Gram of its own.  The
     // cross product below needs nothing new (A holds 0 at a missing entry); the NA workspaces: the row copy for the stacked KP (at least
     // any member's), ONE buffer of per-column Grams sized for the largest member -- the members run one after another on this stream
-    const bool na = h->any_missing;
+    const bool na = h->any_missing && !h->sparse;
     if (na) {
         int rcw = ensure_yrow(h);
         if (rcw != NNLM_OK) return rcw;
@@ -4210,6 +4395,15 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
             with_nkq(h->NKQ, [&](auto N) {
                 launch_xprod_tn<double, N, 0>(h, (const double *)a_contig(h, s), s.ldy, s.Y, s.ldy, h->Cx, s.ldc, s.slab_stride, p);
             });
+    }
+    // Sparse A whose absent entries are missing (nnlm_set_matrix_csc_missing_batch) with something absent: every column solves with a Gram
+    // over its stored rows.  (Every entry stored: the shared-Gram steps below, as the reference calls update().)
+    if (h->sparse && h->sp_missing && h->any_missing) {
+        const int rcm = batch_solve_sparse_missing(h, s, reg, inner_max_iter, inner_rel_tol, method, act);
+        h->pack_ready = false;
+        if (rcm != NNLM_OK) return rcm;
+        LAUNCHCHK(h);
+        return NNLM_OK;
     }
     // 2. + 3. per member: Gram of its own rows of the fixed factor, then its sweep -- launched as a solo rank-k_b half-step launches them
     const int K = h->k, NKQ = h->NKQ, KP = h->KP, KP8 = h->KP8, MW = h->MW;
@@ -4282,7 +4476,8 @@ static int batch_errors(nnlm_handle *h, unsigned long long amask, bool need_pen,
         double *G = h->sp_eG, *sums = G + (size_t)2 * KP * KP;
         factor_rows_kernel<double><<<(n + 255) / 256, 256, 0, st>>>(h->W64, h->npad, n, KP, h->sp_Wrow);
         factor_rows_kernel<double><<<(m + 255) / 256, 256, 0, st>>>(h->H64, h->mpad, m, KP, h->bsp_Hrow);
-        for (int f = 0; f < 2; f++) {
+        // (absent entries missing: the sums run over the stored entries only, nothing is owed for the others -- no Grams, no coordinate sums)
+        for (int f = 0; f < 2 && !h->sp_missing; f++) {
             const double *X = f == 0 ? h->W64 : h->H64;
             const int ld = f == 0 ? h->npad : h->mpad, cols = f == 0 ? n : m;
             const int nb = launch_gram_partial(h, X, ld, 0, cols, h->sp_eslabs, nullptr, st);
@@ -4294,10 +4489,15 @@ static int batch_errors(nnlm_handle *h, unsigned long long amask, bool need_pen,
         // (the split over the non-zeros: nnz and the CU count -- the test hook's, nnlm_debug_set_cus -- decide it, not B or KP)
         const int nwaves = nnlm_spb_waves(h->nnz, h->cus), nblk = (nwaves + 3) / 4;
         double *S = h->bsp_part + (size_t)3 * B * nblk;
-        nnlm_tu_sp_batch_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, nnlm_spb_chunk(h->nnz, nwaves), nwaves,
-                                h->sp_Wrow, h->bsp_Hrow, KP, h->boff_dev, B, amask, h->bsp_part, st);
+        if (h->sp_missing)
+            nnlm_tu_sp_batch_errors_missing(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, nnlm_spb_chunk(h->nnz, nwaves),
+                                            nwaves, h->sp_Wrow, h->bsp_Hrow, KP, h->boff_dev, B, amask, h->bsp_part, st);
+        else
+            nnlm_tu_sp_batch_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, nnlm_spb_chunk(h->nnz, nwaves), nwaves,
+                                    h->sp_Wrow, h->bsp_Hrow, KP, h->boff_dev, B, amask, h->bsp_part, st);
         batch_reduce_kernel<<<3 * B, 256, 0, st>>>(h->bsp_part, nblk, S);
-        nnlm_tu_sp_batch_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->boff_dev, B, KP, amask, h->bres, st);
+        if (h->sp_missing) nnlm_tu_sp_batch_final_missing(S, B, amask, h->bres, st);
+        else nnlm_tu_sp_batch_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->boff_dev, B, KP, amask, h->bres, st);
     } else {
         ProfScope ps(h, P_BATCH_ERRORS, st);
         const int nit = h->npad / 64, mt = (h->m + 63) / 64;
@@ -4756,6 +4956,42 @@ extern "C" int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, cons
     CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
                        mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
     CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    return NNLM_OK;
+}
+
+// nnlm_c_nnmf_csc_batch on a sparse A whose absent entries are missing, with an optional hold-out pattern (ho_colptr NULL: none): the
+// matrix goes through nnlm_set_matrix_csc_missing_batch; + the held-out errors of the final factors per member (NaN without a set or
+// with an empty one)
+extern "C" int nnlm_c_nnmf_csc_missing_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, const long long *ho_colptr,
+                                             const int *ho_rowidx, unsigned B, const unsigned *k, const double *W_init, const double *H_init,
+                                             const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int n_threads,
+                                             int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method,
+                                             unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                                             double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                                             double *holdout_mse, double *holdout_mkl, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (any_null(colptr, k, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned) ||
+        any_null(holdout_mse, holdout_mkl))
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_missing_batch: NULL argument");
+    int rc = batch_ranks(nullptr, "nnlm_c_nnmf_csc_missing_batch", "members", B, k, [&] {
+        return (method >= 3 && method <= 4) ? fail(nullptr, NNLM_ERR_UNSUPPORTED, "nnlm_c_nnmf_csc_missing_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method)
+                                            : NNLM_OK;
+    });
+    if (rc != NNLM_OK) return rc;
+    OneShot os;
+    rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing_batch(h, n, m, colptr, rowidx, x, ho_colptr, ho_rowidx); });
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
+    std::vector<double> Wi, Hi;
+    default_factors(cb, n, m, B, k, nullptr, nullptr, &W_init, &H_init, Wi, Hi);
+    CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
+    CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
+    CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    if (ho_colptr) CHK(nnlm_holdout_errors(h, holdout_mse, holdout_mkl));
+    else
+        for (unsigned b = 0; b < B; b++) holdout_mse[b] = holdout_mkl[b] = std::nan("");
     return NNLM_OK;
 }
 

@@ -1,8 +1,9 @@
-// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_kl.h), see tu_sweepq.h.
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_na_batch.h, k_sparse_kl.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
 #include "k_sparse_batch.h"
 #include "k_sparse_na.h"
+#include "k_sparse_na_batch.h"
 #include "k_sparse_kl.h"
 
 // Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
@@ -145,6 +146,44 @@ void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int
     }
 }
 void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st) { sp_err_final_missing_kernel<<<1, 64, 0, st>>>(s, out); }
+
+// ---- batched factorisation, absent entries missing (k_sparse_na_batch.h) ----
+template <int NT> static void launch_sp_gram_batch(const SpGramBatchArgs &a, bool f64, hipStream_t st)
+{
+    const int nb = (a.g.nworkers + 3) / 4;
+    if (f64) sp_gram_batch_kernel<double, NT><<<nb, 256, 0, st>>>(a);
+    else sp_gram_batch_kernel<float, NT><<<nb, 256, 0, st>>>(a);
+}
+void nnlm_tu_sp_gram_batch(const SpGramBatchArgs &a, int NT, bool f64, hipStream_t st)
+{
+    switch (NT) {
+    case 1: launch_sp_gram_batch<1>(a, f64, st); break;
+    case 2: launch_sp_gram_batch<2>(a, f64, st); break;
+    case 3: launch_sp_gram_batch<3>(a, f64, st); break;
+    default: launch_sp_gram_batch<4>(a, f64, st); break;
+    }
+}
+void nnlm_tu_sp_gram_batch_fixup(const SpGramBatchArgs &a, const int *longc, int nlong, int KP, hipStream_t st)
+{
+    if (nlong <= 0) return;
+    sp_gram_batch_fixup_kernel<<<nlong, 256, 0, st>>>(a, longc, KP);
+}
+void nnlm_tu_sp_batch_errors_missing(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk,
+                                     int nwaves, const double *Wrow, const double *Hrow, int KP, const int *off, int B, unsigned long long amask,
+                                     double *partial, hipStream_t st)
+{
+    const int nblk = (nwaves + 3) / 4;
+    if (f64)
+        sp_batch_errors_kernel<double, true><<<nblk, 256, 0, st>>>(ptr, idx, (const double *)val, ncols, nnz, chunk, nwaves, Wrow, Hrow, KP, off, B,
+                                                                   amask, partial, nblk);
+    else
+        sp_batch_errors_kernel<float, true><<<nblk, 256, 0, st>>>(ptr, idx, (const float *)val, ncols, nnz, chunk, nwaves, Wrow, Hrow, KP, off, B,
+                                                                  amask, partial, nblk);
+}
+void nnlm_tu_sp_batch_final_missing(const double *s, int B, unsigned long long amask, double *out, hipStream_t st)
+{
+    sp_batch_final_missing_kernel<<<(B + 63) / 64, 64, 0, st>>>(s, B, amask, out);
+}
 
 // ---- KL loss, absent entries zeros (k_sparse_kl.h) ----
 int nnlm_spkl_short_max(void) { return SPKL_SHORT_MAX; }

@@ -77,6 +77,26 @@ void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int
 // out[0] = S1, out[1] = S3 + S2 (sum of squares, KL sum over the stored entries)
 void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st);
 
+// Batched factorisation on such a matrix (k_sparse_na_batch.h): the Grams of all members in one launch.  g.Y is the row copy at the
+// STACKED KP; column c's Grams take `slot` doubles of g.G (member b's at goff_b, compact at its own KP_b), a segment of a long column
+// `slot` doubles of g.seg.  pairs / tiles: the upper tile pairs (ta <= tb, ta-major) that meet an active member's diagonal block, and
+// the coordinate tiles those pairs touch.  tab[i] = member of stacked coordinate i or -1 (not active / beyond the stack),
+// tab[64 + i] = goff_b + (i - off_b) KP_b - off_b: element (i, j) of the stack goes to word tab[64 + i] + j of the slot.
+struct SpGramBatchArgs {
+    SpGramArgs g;
+    size_t slot;
+    unsigned pairs, tiles;
+    int tab[128];
+};
+void nnlm_tu_sp_gram_batch(const SpGramBatchArgs &a, int NT, bool f64, hipStream_t st);
+void nnlm_tu_sp_gram_batch_fixup(const SpGramBatchArgs &a, const int *longc, int nlong, int KP, hipStream_t st);
+// The error sums of the batch when absent entries are missing: nnlm_tu_sp_batch_errors with S2_b = sum of wh over the stored entries
+void nnlm_tu_sp_batch_errors_missing(const long long *ptr, const int *idx, const void *val, bool f64, int ncols, long long nnz, long long chunk,
+                                     int nwaves, const double *Wrow, const double *Hrow, int KP, const int *off, int B, unsigned long long amask,
+                                     double *partial, hipStream_t st);
+// out[2 b] = S1_b, out[2 b + 1] = S3_b + S2_b for every member with its bit of amask set (nnlm_tu_sp_err_final_missing per member)
+void nnlm_tu_sp_batch_final_missing(const double *s, int B, unsigned long long amask, double *out, hipStream_t st);
+
 // Sparse A, KL loss (k_sparse_kl.h, tu_sparse.hip): scd_kl_update / lee_kl_update over the stored entries of the lines [0, ncols)
 struct SpKlArgs {
     const long long *ptr;  // [ncols + 1] CSC (H half-step) / CSR (W half-step)
