@@ -431,12 +431,21 @@ int nnlm_debug_exchange(nnlm_handle **handles, int nranks, int which, int stage)
  * Test hook: handles created from now on plan their launches as if the device had `cus` compute units (0 = the device's own
  * count) -- small problems then take the launch forms large ones take on the real device (persistent SCD sweep). */
 int nnlm_debug_set_cus(int cus);
+/* Test hook: handles created from now on launch xprod16_tn_kernel (the split-fp16 cross product) with `waves` = 8 or 10 wavefronts per
+ * block -- 128- or 160-column tiles -- wherever that form exists (10: ranks up to 52); 0 = the launch plan decides. */
+int nnlm_debug_set_xprod_waves(int waves);
+/* The launch plan of one xprod16_tn_kernel launch: ldc output columns (a multiple of 128), `stages` contraction stages of 64 elements,
+ * rank k <= 64, `cus` compute units, force_waves as nnlm_debug_set_xprod_waves.  Pure function, works without a GPU.
+ * out[0..6] = wavefronts per block, split-K slabs S, stages per slab, tiles, blocks (tiles x S), 4-row pieces of the factor image a
+ * stage loads (all 4 ceil(k / 16); 13 at k = 49 .. 52), LDS bytes of a block; out[7] = 0. */
+int nnlm_xprod_plan(int ldc, int stages, int k, int cus, int force_waves, int out[8]);
 /* Test hook: the matrix-sized workspaces of the KL solvers (starting states of all columns, transposed copy of A, streaming scratch)
  * "do not fit" when they exceed `bytes` (0 = no limit): the half-step then takes its smaller-footprint path -- the streaming kernel
  * over column chunks -- exactly as it does when hipMalloc itself says no. */
 int nnlm_debug_alloc_limit(size_t bytes);
 /* Facts about the handle's last launches, for bench.py's kernel attribution: key = "cus" (compute units the launch policy
- * counts), "sweep_form_w" / "sweep_form_h" (SCD sweep of the last W / H half-step: 0 plain sweep_scd_q_kernel, 1 persistent
+ * counts), "xprod_waves_w" / "xprod_waves_h" and "xprod_splits_w" / "xprod_splits_h" (wavefronts per block and split-K slabs of the last
+ * xprod16_tn_kernel launch of the W / H half-step, 0 none yet), "xprod_splits_err" (slabs of the last xprod16_err_kernel launch, 0 none yet), "sweep_form_w" / "sweep_form_h" (SCD sweep of the last W / H half-step: 0 plain sweep_scd_q_kernel, 1 persistent
  * sweep_scd_qw_kernel -- both strict fp64 --, 2 sweep_scd_f_kernel, 3 sweep_row_kernel (fp32-operand mode: 3 while the launch is one
  * round of four-column wavefronts, at most 32 columns per CU), -1 none yet), "sweep_groups_w" /
  * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "lee_lanes_w" / "lee_lanes_h" and

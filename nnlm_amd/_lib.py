@@ -32,7 +32,7 @@ EXPORTS = [
     "nnlm_half_step", "nnlm_iterate", "nnlm_run", "nnlm_take_sweeps", "nnlm_errors", "nnlm_sync", "nnlm_profile_enable",
     "nnlm_profile_get", "nnlm_profile_reset", "nnlm_comm_unique_id", "nnlm_comm_init", "nnlm_comm_info",
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
-    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
+    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_xprod_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_matrix_csc_kl", "nnlm_c_nnmf_csc_kl", "nnlm_c_nnlm_csc_kl",
@@ -162,6 +162,10 @@ def load():
     lib.nnlm_comm_set_form.argtypes = [vp, C.c_int]
     lib.nnlm_debug_set_cus.restype = C.c_int
     lib.nnlm_debug_set_cus.argtypes = [C.c_int]
+    lib.nnlm_debug_set_xprod_waves.restype = C.c_int
+    lib.nnlm_debug_set_xprod_waves.argtypes = [C.c_int]
+    lib.nnlm_xprod_plan.restype = C.c_int
+    lib.nnlm_xprod_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]
     lib.nnlm_debug_alloc_limit.restype = C.c_int
     lib.nnlm_debug_alloc_limit.argtypes = [C.c_size_t]
     lib.nnlm_release_caches.restype = C.c_int
@@ -922,7 +926,8 @@ class Handle:
         self._ck(self._lib.nnlm_comm_set_form(self._h, FORMS[form] if isinstance(form, str) else int(form)))
 
     def get_info(self, key):
-        """cus, sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
+        """cus, xprod_waves_w / xprod_waves_h and xprod_splits_w / xprod_splits_h (wavefronts per block and slabs of the last xprod16_tn_kernel
+        launch of each side), xprod_splits_err (slabs of the last fused xprod16_err_kernel launch), sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
         lee_lanes_w / lee_lanes_h and lee_regs_w / lee_regs_h (L and R of the last sweep_ls_kernel<R, L, 2> launch, -1 none yet),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
         column / a row of a dense matrix)."""
@@ -970,6 +975,18 @@ def debug_exchange(handles, which, stage):
 def debug_set_cus(cus: int):
     """Test hook: handles created from now on plan their launches for `cus` compute units (0 = the device's own count)."""
     _check(load().nnlm_debug_set_cus(int(cus)))
+
+
+def debug_set_xprod_waves(waves: int):
+    """Test hook: handles created from now on run the split-fp16 cross product with 8 or 10 wavefronts per block (0 = the plan decides)."""
+    _check(load().nnlm_debug_set_xprod_waves(int(waves)))
+
+
+def xprod_plan(ldc, stages, k, cus, force_waves=0):
+    """Launch plan of the split-fp16 cross product (pure host function of the C ABI, works without a GPU)."""
+    out = (C.c_int * 8)()
+    _check(load().nnlm_xprod_plan(int(ldc), int(stages), int(k), int(cus), int(force_waves), out))
+    return dict(zip(("waves", "splits", "stages_per_split", "tiles", "blocks", "pieces", "lds_bytes"), list(out)[:7]))
 
 
 def debug_alloc_limit(nbytes: int):

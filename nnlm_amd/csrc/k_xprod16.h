@@ -42,27 +42,43 @@ __device__ static inline void split16(float v, float scale, _Float16 &hi, _Float
 }
 
 // scal_exp[0] = eA (written by the host), scal_exp[1] = eY (written by factor16_kernel's companion absmax pass)
-// Ring of XPROD_NBUF = 3 LDS stage buffers: two stages in flight while one is consumed, 144 KB at KP = 64 -- the block owns its CU.
+// Ring of XPROD_NBUF = 3 LDS stage buffers: two stages in flight while one is consumed -- the block owns its CU.
 // (A two-buffer, 96 KB form that leaves room for a workgroup of the SCD sweep on the same CU was measured in round 4 -- DESIGN.md
 // section 6: co-residency hides 0.07 of 0.26 ms -- and is not kept.)
-template <int NKQ>
-__global__ __launch_bounds__(XPROD_THREADS) void xprod16_tn_kernel(const uint32_t *__restrict__ A16, int lda,   // lda: elements per column
-                                                                   const uint32_t *__restrict__ Y16, int ldy,   // ldy: elements per row
-                                                                   double *__restrict__ Cx, int ldc, size_t slab_stride,
-                                                                   int stage_begin, int stage_end, int stages_per_split,
-                                                                   const int *__restrict__ scal_exp)
+//
+// NWV wavefronts per block (8 or 10): the tile is 16 NWV columns, the A image NWV x 4 KB per stage.  The second width exists because the
+// grid is (tiles, slabs) and a block fills its CU: 128-column tiles with an integer slab count leave CUs idle where 160-column tiles fill them
+// (xprod_plan in nnlm_mi355x.hip chooses).  The columns of a launch are a multiple of 128, not of 160: a wavefront whose 16 columns lie at or beyond them loads no
+// A, computes on nothing and stores nothing; it still loads its share of the factor image and takes part in every barrier.
+// YP: the 4-row pieces of the factor image that are loaded, <= 4 NKQ.  Rows >= k of the split copy are zero, so pieces past ceil(k / 4)
+// need not be fetched; the host instantiates YP = 13 for k = 49 .. 52 (what lets the 10-wavefront ring fit at NKQ = 4) and all 4 NKQ
+// pieces otherwise (launch_xprod16_m in nnlm_mi355x.hip).  A lane of the last MFMA tile whose row lies past the loaded pieces
+// reads a 256-byte row of zeros that every ring buffer carries behind its image (written once per block, before the first barrier).
+__host__ __device__ constexpr static inline int xprod16_buf_bytes(int nwv, int nkq, int yp) { return nwv * 4096 + yp * 1024 + (yp < 4 * nkq ? XPROD_ROWB : 0); }
+__host__ __device__ constexpr static inline int xprod16_lds_bytes(int nwv, int nkq, int yp) { return XPROD_NBUF * xprod16_buf_bytes(nwv, nkq, yp); }
+template <int NKQ, int NWV = XPROD_WAVES, int YP = 4 * NKQ>
+__global__ __launch_bounds__(64 * NWV) void xprod16_tn_kernel(const uint32_t *__restrict__ A16, int lda,   // lda: elements per column
+                                                              const uint32_t *__restrict__ Y16, int ldy,   // ldy: elements per row
+                                                              double *__restrict__ Cx, int ldc, int ncols, // ncols: columns of this launch, a multiple of 16
+                                                              size_t slab_stride, int stage_begin, int stage_end, int stages_per_split,
+                                                              const int *__restrict__ scal_exp)
 {
-    constexpr int KP = 16 * NKQ;
-    constexpr int BUF = XPROD_A_IMG_BYTES + KP * XPROD_ROWB;
+    static_assert(NWV == 8 || NWV == 10, "8 or 10 wavefronts");
+    static_assert(YP >= 1 && YP <= 4 * NKQ && YP > 4 * (NKQ - 1), "the loaded pieces reach into the last MFMA tile");
+    constexpr int AIMG = NWV * 4096;
+    constexpr bool TRIM = YP < 4 * NKQ;
+    constexpr int BUF = AIMG + YP * 1024 + (TRIM ? XPROD_ROWB : 0);
+    static_assert(XPROD_NBUF * BUF <= 160 * 1024, "the ring fits the CU's LDS");
+    static_assert(YP <= 2 * NWV, "at most two factor pieces per wavefront");
     constexpr int FL = XPROD_FLUSH_ELEMS / 64;
-    constexpr int YI = KP / 4;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lg = lane >> 4;
     // (ablations of this kernel -- no MFMAs, re-read of a cached stage, late issue, descending order: scripts/exp/csrc_r5/k_xprod16.h with
     //  scripts/exp/xprod_exp.hip / xerr_exp.hip; the product kernel carries no switch)
-    const int j0 = (int)blockIdx.x * XPROD_TN_BJ;
+    const int j0 = (int)blockIdx.x * (16 * NWV);
+    const bool live = j0 + 16 * wave < ncols; // (wave-uniform: a wavefront's 16 columns are all inside or all outside)
     int st0 = stage_begin + (int)blockIdx.y * stages_per_split;
     int st1 = st0 + stages_per_split;
     if (st1 > stage_end) st1 = stage_end;
@@ -76,27 +92,44 @@ __global__ __launch_bounds__(XPROD_THREADS) void xprod16_tn_kernel(const uint32_
         acc64[b] = f64x4{0, 0, 0, 0};
     }
 
-    // a stage = one 256-byte chunk ([64 hi | 64 lo]) of 128 columns of A and of KP rows of the factor; the sixteen
+    // a stage = one 256-byte chunk ([64 hi | 64 lo]) of 16 NWV columns of A and of 4 YP rows of the factor; the sixteen
     // 16-byte slots of a row are XOR-swizzled with the row index through the global source address (as in k_xprod.h).
-    // Piece t = wave + 8 i of an image = rows 4 t + lg: (row & 15) = (4 wave + lg) & 15 for every i, so ONE per-lane byte offset
-    // per image serves all of a wavefront's requests; piece and stage go into the scalar base.
-    const int rw = 4 * wave + lg, sw = l15 ^ (rw & 15);
-    const unsigned voffA = (unsigned)(((size_t)rw * lda + sw * 4) * 4), voffY = (unsigned)(((size_t)rw * ldy + sw * 4) * 4);
-    const unsigned long long baseA = xp_uniform64(A16 + (size_t)j0 * lda), baseY = xp_uniform64(Y16);
+    // A: a wavefront loads the four 4-row pieces of its OWN 16 columns (the rows it reads back), piece pc = rows 16 wave + 4 pc + lg, one
+    // per-lane byte offset per piece; the wavefront's first row and the stage go into the scalar base.
+    // Factor: piece t = wave + NWV i (i < 2) = rows 4 t + lg, one per-lane byte offset per i.
+    unsigned voffA[4], voffY[2];
+#pragma unroll
+    for (int pc = 0; pc < 4; pc++) {
+        const int r = 4 * pc + lg;
+        voffA[pc] = (unsigned)(((size_t)r * lda + (l15 ^ r) * 4) * 4);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int r = 4 * (wave + NWV * i) + lg;
+        voffY[i] = (unsigned)(((size_t)r * ldy + (l15 ^ (r & 15)) * 4) * 4);
+    }
+    const unsigned long long baseA = xp_uniform64(A16 + ((size_t)j0 + 16 * wave) * lda), baseY = xp_uniform64(Y16);
     const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)smem);
     auto issue = [&](int st, int bi) {
         const unsigned long long c0b = (unsigned long long)st * 256ull; // byte offset of the chunk
-        const unsigned dst = lds0 + (unsigned)bi * (unsigned)BUF + (unsigned)wave * 1024u;
+        const unsigned dst = lds0 + (unsigned)bi * (unsigned)BUF;
+        if (live) {
 #pragma unroll
-        for (int i = 0; i < XPROD_A_IMG_BYTES / 1024 / XPROD_WAVES; i++)
-            glds16_s(voffA, baseA + c0b + (unsigned long long)i * 32ull * (unsigned long long)lda * 4ull, dst + (unsigned)i * 8192u);
+            for (int pc = 0; pc < 4; pc++) glds16_s(voffA[pc], baseA + c0b, dst + (unsigned)wave * 4096u + (unsigned)pc * 1024u);
+        }
 #pragma unroll
-        for (int i = 0; i < (YI + XPROD_WAVES - 1) / XPROD_WAVES; i++)
-            if (wave + XPROD_WAVES * i < YI)
-                glds16_s(voffY, baseY + c0b + (unsigned long long)i * 32ull * (unsigned long long)ldy * 4ull,
-                         dst + (unsigned)XPROD_A_IMG_BYTES + (unsigned)i * 8192u);
+        for (int i = 0; i < 2; i++)
+            if (wave + NWV * i < YP) glds16_s(voffY[i], baseY + c0b, dst + (unsigned)AIMG + (unsigned)(wave + NWV * i) * 1024u);
     };
-    const int per_stage = XPROD_A_IMG_BYTES / 1024 / XPROD_WAVES + strided_count(wave, YI);
+    const int per_stage = (live ? 4 : 0) + (wave < YP ? 1 : 0) + (wave + NWV < YP ? 1 : 0);
+    if constexpr (TRIM) { // the row of zeros behind every buffer's factor image
+        if (tid < XPROD_NBUF * 16) *(uint4 *)(smem + (tid >> 4) * BUF + AIMG + YP * 1024 + (tid & 15) * 16) = uint4{0u, 0u, 0u, 0u};
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // (landed before the first raw s_barrier below)
+    }
+    // byte offset of a lane's row of MFMA tile nt inside the factor image
+    int yoff[NKQ];
+#pragma unroll
+    for (int nt = 0; nt < NKQ; nt++) yoff[nt] = AIMG + ((TRIM && 16 * nt + l15 >= 4 * YP) ? 4 * YP : 16 * nt + l15) * XPROD_ROWB;
     if (st0 < st1) issue(st0, 0);
     constexpr int NBUF = XPROD_NBUF;
     static_assert(NBUF == 3, "two stages in flight while one is consumed");
@@ -108,37 +141,40 @@ __global__ __launch_bounds__(XPROD_THREADS) void xprod16_tn_kernel(const uint32_
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (st + 2 < st1) issue(st + 2, (st + 2 - st0) % NBUF);
+        if (live) {
 #pragma unroll
-        for (int c2 = 0; c2 < 2; c2++) { // two K = 32 chunks per stage; lane (l15, lg) holds elements 32*c2 + 8*lg .. +7
-            const int arow = 16 * wave + l15;
-            const int sh = (4 * c2 + lg), sl = 8 + 4 * c2 + lg; // logical 16-byte slots of the hi / lo halves
-            const xh8 ah = *(const xh8 *)(buf + arow * XPROD_ROWB + ((sh ^ l15) * 16));
-            const xh8 al = *(const xh8 *)(buf + arow * XPROD_ROWB + ((sl ^ l15) * 16));
-            xh8 yh[NKQ], yl[NKQ];
+            for (int c2 = 0; c2 < 2; c2++) { // two K = 32 chunks per stage; lane (l15, lg) holds elements 32*c2 + 8*lg .. +7
+                const int arow = 16 * wave + l15;
+                const int sh = (4 * c2 + lg), sl = 8 + 4 * c2 + lg; // logical 16-byte slots of the hi / lo halves
+                const xh8 ah = *(const xh8 *)(buf + arow * XPROD_ROWB + ((sh ^ l15) * 16));
+                const xh8 al = *(const xh8 *)(buf + arow * XPROD_ROWB + ((sl ^ l15) * 16));
+                xh8 yh[NKQ], yl[NKQ];
 #pragma unroll
-            for (int nt = 0; nt < NKQ; nt++) {
-                const unsigned char *yrow = buf + XPROD_A_IMG_BYTES + (16 * nt + l15) * XPROD_ROWB;
-                yh[nt] = *(const xh8 *)(yrow + ((sh ^ l15) * 16));
-                yl[nt] = *(const xh8 *)(yrow + ((sl ^ l15) * 16));
+                for (int nt = 0; nt < NKQ; nt++) {
+                    const unsigned char *yrow = buf + yoff[nt];
+                    yh[nt] = *(const xh8 *)(yrow + ((sh ^ l15) * 16));
+                    yl[nt] = *(const xh8 *)(yrow + ((sl ^ l15) * 16));
+                }
+#pragma unroll
+                for (int nt = 0; nt < NKQ; nt++) {
+                    accm[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh[nt], accm[nt], 0, 0, 0);
+                    accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl[nt], accx[nt], 0, 0, 0);
+                    accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh[nt], accx[nt], 0, 0, 0);
+                }
             }
+            if (++since_flush == FL) {
+                since_flush = 0;
 #pragma unroll
-            for (int nt = 0; nt < NKQ; nt++) {
-                accm[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yh[nt], accm[nt], 0, 0, 0);
-                accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, yl[nt], accx[nt], 0, 0, 0);
-                accx[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, yh[nt], accx[nt], 0, 0, 0);
-            }
-        }
-        if (++since_flush == FL) {
-            since_flush = 0;
+                for (int b = 0; b < NKQ; b++) {
 #pragma unroll
-            for (int b = 0; b < NKQ; b++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) acc64[b][r] += (double)accm[b][r] + (double)accx[b][r] * (1.0 / XPROD16_LO_SCALE);
-                accm[b] = f32x4{0, 0, 0, 0};
-                accx[b] = f32x4{0, 0, 0, 0};
+                    for (int r = 0; r < 4; r++) acc64[b][r] += (double)accm[b][r] + (double)accx[b][r] * (1.0 / XPROD16_LO_SCALE);
+                    accm[b] = f32x4{0, 0, 0, 0};
+                    accx[b] = f32x4{0, 0, 0, 0};
+                }
             }
         }
     }
+    if (!live) return;
     // epilogue: D[M = column, N = kq], undo the two power-of-two scalings (exact)
     const double unscale = ldexp(1.0, -(scal_exp[0] + scal_exp[1]));
     double *out = Cx + (size_t)blockIdx.y * slab_stride;

@@ -215,6 +215,9 @@ struct nnlm_handle {
     uint32_t *W16c = nullptr, *H16c = nullptr; // kq-contiguous split copies [npad][2][64], [mpad][2][64] (fused error block)
     bool fuse_err = false;       // request: the next W half-step's cross product also evaluates the error sums of (W, H) now current
     int cus_device = 0;          // the device's CU count (cus may be the test hook's)
+    int xprod_waves = 0;         // test hook (nnlm_debug_set_xprod_waves): block width of xprod16_tn_kernel, 0 = the plan decides
+    int xp_err_splits = 0;       // slabs of the last xprod16_err_kernel launch
+    int xp_waves[2] = {0, 0}, xp_splits[2] = {0, 0}; // [which]: wavefronts per block and slabs of the last xprod16_tn_kernel launch
     int fused_nb = 0;            // answer: number of (sum of squares, KL) pairs it left in `partials` (0 = not fused)
     // multi-GPU: the error block of a trace iteration is enqueued from INSIDE the speculative W half-step, right behind its cross product:
     // its all-reduces (two sums, one sweep counter) must be issued ahead of that half-step's all-gather -- RCCL runs a communicator's
@@ -401,6 +404,7 @@ extern "C" unsigned nnlm_trace_capacity(unsigned max_iter, unsigned trace)
 }
 
 static std::atomic<int> g_debug_cus{0}; // nnlm_debug_set_cus (test hook, read once per nnlm_create): compute units the launch policies of new handles count (0 = the device's)
+static std::atomic<int> g_debug_xprod_waves{0}; // nnlm_debug_set_xprod_waves (test hook, read once per nnlm_create): 8 | 10 wavefronts per block of xprod16_tn_kernel, 0 = the plan decides
 // Pinned bounce buffers of nnlm_set_matrix, kept between calls.  Pinning costs ~0.3 ms per MB: two fresh 64 MB buffers were ~40 ms of EVERY
 // upload (half of config 2's 78 ms, most of the 53 ms an 80 MB matrix took -- scripts/gpu_call_breakdown.py).  One pair per process, taken
 // by the call that finds it free (a concurrent upload on another thread allocates its own and frees it), released at exit.
@@ -491,6 +495,13 @@ extern "C" int nnlm_debug_alloc_limit(size_t bytes)
     return NNLM_OK;
 }
 
+extern "C" int nnlm_debug_set_xprod_waves(int waves)
+{
+    if (waves != 0 && waves != 8 && waves != 10) return fail(nullptr, NNLM_ERR_ARG, "nnlm_debug_set_xprod_waves: %d (0, 8 or 10)", waves);
+    g_debug_xprod_waves = waves;
+    return NNLM_OK;
+}
+
 extern "C" int nnlm_debug_set_cus(int cus)
 {
     if (cus < 0) return fail(nullptr, NNLM_ERR_ARG, "nnlm_debug_set_cus: %d", cus);
@@ -555,6 +566,7 @@ extern "C" int nnlm_create(nnlm_handle **out, int device, int precision)
         h->prec = precision;
         h->cus = h->cus_device = res.cus;
         if (const int dc = g_debug_cus.load(std::memory_order_relaxed); dc > 0) h->cus = dc;
+        h->xprod_waves = g_debug_xprod_waves.load(std::memory_order_relaxed);
         h->stream = res.stream, h->stream_e = res.stream_e;
         h->ev_hdone = res.ev_hdone, h->ev_err = res.ev_err, h->ev_xdone = res.ev_xdone;
         h->scal = res.scal, h->sweeps = res.sweeps, h->host_res = res.host_res, h->sweeps_tmp = res.sweeps_tmp, h->sweepq_img = res.sweepq_img;
@@ -584,6 +596,7 @@ extern "C" int nnlm_create(nnlm_handle **out, int device, int precision)
     h->cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     h->cus_device = h->cus;
     if (const int dc = g_debug_cus.load(std::memory_order_relaxed); dc > 0) h->cus = dc; // test hook (nnlm_debug_set_cus): the sweep's launch policy at small sizes
+    h->xprod_waves = g_debug_xprod_waves.load(std::memory_order_relaxed);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&h->stream_e, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_hdone, hipEventDisableTiming) != hipSuccess ||
@@ -1605,37 +1618,74 @@ extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_
 // ---------------------------------------------------------------------------------------------
 // factors
 // ---------------------------------------------------------------------------------------------
-// Split-K factor S for tiles_x output tiles.  The cross-product kernels run one block per CU (their LDS ring fills the
-// CU), so a launch executes in ceil(blocks/256) rounds of ceil(stages/S) stages each; every block also pays ~3 stage
-// times of pipeline fill/drain, and every slab costs fp64 writes here and fp64 reads in the solver that sums the slabs
-// (S = 16 instead of 3 at config 2 made the sweep's start-up 0.06 ms longer -- measured).  Pick the cheapest S <= 16.
-static int split_plan(int tiles_x, int stages, int *S, int *sps)
+// Launch plan of an A-streaming cross product over `cols` output columns (a multiple of 128) and `stages` contraction stages.
+// The kernels run one block per CU (their LDS ring fills the CU), so a launch executes in ceil(blocks / cus) rounds of ceil(stages / S)
+// stages each; every block also pays ~3 stage times of pipeline fill/drain, and every slab costs fp64 writes here and fp64 reads in the
+// solver that sums the slabs (S = 16 instead of 3 at config 2 made the sweep's start-up 0.06 ms longer -- measured).
+// The split-fp16 kernel (k_xprod16.h) has two block widths, 8 or 10 wavefronts = 128 or 160 columns: where 128-column tiles times an
+// integer slab count leave CUs idle (config 2, H half-step: 79 x 3 = 237 blocks of 256; W half-step: 158 x 3 = 474, two rounds), 160-column
+// tiles can fill them (64 x 4 = 256 and 127 x 2 = 254).  A 160-column stage moves more bytes through the CU than a 128-column one, so a
+// stage is priced by its bytes, relative to the 128-column stage: A bytes + XPLAN_Y_WEIGHT x factor bytes (L2 hits).  Pick the cheapest
+// (wavefronts, S <= 16); ties go to 8 wavefronts and to the smaller S.  With 8 wavefronts the relative price is 1 and the choice of S is
+// the one this function made before it knew of a second width.
+// Measured (scripts/exp/xprod_exp.hip -DXPROD_BLOCKS, profiles/xprod_blocks_ab.harness.md): 16 against 13 factor pieces per stage change the
+// time of config 2's launches by 0.6 - 0.8 %, which makes a factor byte worth 0.06 - 0.09 of a byte of A; with 0.08 the model puts the
+// 160-column form at 0.94 (H) and 0.90 (W) of the 128-column one, measured 0.98 and 0.91.
+#define XPLAN_Y_WEIGHT 0.08  // a factor byte (L2 hit) against a byte of A (HBM)
+#define XPLAN_SLAB_COST 0.75 // a slab, in 128-column stage times (as before: the sweep's longer start-up, see above)
+// Factor pieces (4 rows each) a stage of xprod16_tn_kernel loads at rank k: all 4 NKQ, except at k = 49 .. 52, where the 13 that can be
+// non-zero are what lets the 160-column ring fit (one trimmed instantiation, used by both widths; trimming alone gains < 1 %)
+static int xprod16_pieces(int k) { return (k > 48 && k <= 52) ? 13 : 4 * (k < 1 ? 1 : k > NNLM_KQ_MAX ? 4 : (k + 15) / 16); }
+struct XPlan {
+    int nwv, S, sps, tiles_x, yp, lds;
+};
+// force_waves: 0 = both widths where allowed
+static XPlan xprod_plan(int cols, int stages, int k, int cus, int force_waves, bool allow10)
 {
-    const int cus = 256;
+    if (cus < 1) cus = 1;
+    if (stages < 1) stages = 1;
     const int smax = 16;
-    int best_s = 1;
+    const int nkq = k < 1 ? 1 : k > NNLM_KQ_MAX ? 4 : (k + 15) / 16; // (rank > 64: launches of 64 rows each, all pieces)
+    const int yp = xprod16_pieces(k);
+    const bool can10 = allow10 && k >= 1 && k <= NNLM_KQ_MAX && xprod16_lds_bytes(10, nkq, yp) <= 160 * 1024;
+    const double stage8 = 8 * 4096 + XPLAN_Y_WEIGHT * yp * 1024, stage10 = 10 * 4096 + XPLAN_Y_WEIGHT * yp * 1024;
+    int best_s = 1, best_w = 8;
     double best_cost = 1e300;
-    for (int s = 1; s <= smax; s++) {
-        if (s > 1 && stages / s < 8) break;
-        const long blocks = (long)tiles_x * s;
-        const long rounds = (blocks + cus - 1) / cus;
-        const int per_block = (stages + s - 1) / s;
-        const double cost = (double)rounds * (per_block + 3) + 0.75 * s;
-        if (cost < best_cost - 1e-9) {
-            best_cost = cost;
-            best_s = s;
+    for (int w = 8; w <= 10; w += 2) {
+        if (w == 10 && (!can10 || force_waves == 8)) continue;
+        if (w == 8 && force_waves == 10 && can10) continue;
+        const int tiles = (cols + 16 * w - 1) / (16 * w);
+        const double rel = w == 8 ? 1.0 : stage10 / stage8;
+        for (int s = 1; s <= smax; s++) {
+            if (s > 1 && stages / s < 8) break;
+            const long blocks = (long)tiles * s;
+            const long rounds = (blocks + cus - 1) / cus;
+            const int per_block = (stages + s - 1) / s;
+            const double cost = (double)rounds * (per_block + 3) * rel + XPLAN_SLAB_COST * s;
+            if (cost < best_cost - 1e-9) {
+                best_cost = cost;
+                best_s = s;
+                best_w = w;
+            }
         }
     }
+    XPlan r;
     int per = (stages + best_s - 1) / best_s;
     if (per < 1) per = 1;
-    *S = (stages + per - 1) / per;
-    if (*S < 1) *S = 1;
-    *sps = per;
-    return 0;
+    r.S = (stages + per - 1) / per;
+    if (r.S < 1) r.S = 1;
+    r.sps = per;
+    r.nwv = best_w;
+    r.tiles_x = (cols + 16 * best_w - 1) / (16 * best_w);
+    r.yp = yp;
+    r.lds = xprod16_lds_bytes(best_w, nkq, yp);
+    return r;
 }
 
 struct HalfPlan {
     int stage_begin, stage_end, S, sps, tiles_x;
+    int nwv = XPROD_WAVES; // wavefronts per block: 16 nwv columns per tile (10: xprod16_tn_kernel only)
+    int cols = 0;          // columns the launch covers, from col_off on (a multiple of 128)
     int col_off = 0; // first column of the factor being solved that this launch covers (column shards of the multi-GPU NA path)
 };
 
@@ -1732,21 +1782,36 @@ static SweepArgs sweep_args(const nnlm_handle *h, const Side &s, const double re
 // (the split-fp16 kernels' stages of 64 elements are the same in the fp32-operand mode, the only mode that has them)
 static int stage_elems(const nnlm_handle *h) { return XPROD_ROWB / (int)esize(h); }
 
-static HalfPlan plan_half(const nnlm_handle *h, int which, int rank, int nranks)
+// The kernel a dense half-step of side `which` launches decides which widths the plan may use: only xprod16_tn_kernel has the 160-column
+// form -- the fused cross product / error kernel of a trace iteration and the strict kernels keep 128 columns.
+// fused: the launch is the fused kernel's (callers pass h->fuse_err of the W half-step being planned)
+static bool xprod_wide_ok(const nnlm_handle *h, int which, bool fused) { return h->x16 && !h->sparse && h->k >= 1 && h->k <= NNLM_KQ_MAX && !(which == 0 && fused); }
+
+// plan of `cols` columns from p.col_off on over the stages [p.stage_begin, p.stage_end)
+static void plan_cols(const nnlm_handle *h, int which, int cols, HalfPlan &p, bool fused)
+{
+    int len = p.stage_end - p.stage_begin;
+    if (len < 1) len = 1;
+    // xprod16_tn_kernel is planned for the handle's CU count (the test hook's, if set); the fused and the strict kernels for the device's
+    // own, as before: the strict mode's results do not depend on nnlm_debug_set_cus (the sweep forms it selects are bit-identical)
+    const bool tn16 = h->x16 && !h->sparse && !(which == 0 && fused);
+    const int cus = (tn16 || h->cus_device < 1) ? h->cus : h->cus_device;
+    const XPlan x = xprod_plan(cols, len, h->k, cus, h->xprod_waves, xprod_wide_ok(h, which, fused));
+    p.S = x.S, p.sps = x.sps, p.tiles_x = x.tiles_x, p.nwv = x.nwv, p.cols = cols;
+}
+
+static HalfPlan plan_half(const nnlm_handle *h, int which, int rank, int nranks, bool fused)
 {
     const Side s = side_of(h, which);
     HalfPlan p;
-    const int stages_total = s.ldy / stage_elems(h), tiles_x = s.ldc / XPROD_TN_BJ;
+    const int stages_total = s.ldy / stage_elems(h);
     // this rank's slab of the contraction
     const int per_rank = (stages_total + nranks - 1) / nranks;
     p.stage_begin = rank * per_rank;
     p.stage_end = p.stage_begin + per_rank;
     if (p.stage_end > stages_total) p.stage_end = stages_total;
     if (p.stage_begin > stages_total) p.stage_begin = stages_total;
-    int len = p.stage_end - p.stage_begin;
-    if (len < 1) len = 1;
-    split_plan(tiles_x, len, &p.S, &p.sps);
-    p.tiles_x = tiles_x;
+    plan_cols(h, which, s.ldc, p, fused);
     return p;
 }
 
@@ -1796,8 +1861,9 @@ static int factors_alloc(nnlm_handle *h, int k, int row_pad)
         HIPCHK(h, hipMalloc(&h->Wmask, (size_t)h->npad * h->MW * 8));
         HIPCHK(h, hipMalloc(&h->Hmask, (size_t)h->mpad * h->MW * 8));
         // split-K slabs: sized for the worst case over ranks (nranks = 1 gives the largest S)
-        const HalfPlan ph = plan_half(h, 1, 0, 1), pw = plan_half(h, 0, 0, 1);
-        size_t eh = (size_t)ph.S * h->KP * h->mpad, ew = (size_t)pw.S * h->KP * h->npad;
+        // (the W half-step has two plans: with and without the fused error kernel, which keeps 128-column blocks)
+        const HalfPlan ph = plan_half(h, 1, 0, 1, false), pw = plan_half(h, 0, 0, 1, false), pw2 = plan_half(h, 0, 0, 1, true);
+        size_t eh = (size_t)ph.S * h->KP * h->mpad, ew = (size_t)(pw.S > pw2.S ? pw.S : pw2.S) * h->KP * h->npad;
         if (h->x16) {
             HIPCHK(h, hipMalloc(&h->Y16, (size_t)h->KP * (h->npad > h->mpad ? h->npad : h->mpad) * 4 + 4096));
             HIPCHK(h, hipMalloc(&h->W16c, (size_t)h->npad * 64 * 4 + 4096));
@@ -2040,15 +2106,35 @@ static void launch_xprod_nkq(nnlm_handle *h, const Side &s, const HalfPlan &p)
 // Split-fp16 cross product (k_xprod16.h): split copy of the fixed factor scaled by its own power of two, then the
 // A-streaming kernel on A16 (H half-step) or A16T (W half-step: the transposed copy makes it the same "TN" kernel).
 // q0: first of the 16 NKQ rows of the split copy and of the slabs this launch covers (rank > 64: one launch per 64 rows)
+template <int NKQ, int NWV, int YP>
+static void launch_xprod16_nwy(nnlm_handle *h, const Side &s, const HalfPlan &p, int q0)
+{
+    dim3 grid(p.tiles_x, p.S);
+    const int lds = xprod16_lds_bytes(NWV, NKQ, YP);
+    set_dyn_lds((const void *)xprod16_tn_kernel<NKQ, NWV, YP>, lds, "xprod16_tn_kernel");
+    xprod16_tn_kernel<NKQ, NWV, YP><<<grid, 64 * NWV, lds, h->stream>>>(s.A16 + (size_t)p.col_off * s.ldy, s.ldy, h->Y16 + (size_t)q0 * s.ldy, s.ldy,
+                                                                        h->Cx + (size_t)q0 * s.ldc + p.col_off, s.ldc, p.cols, s.slab_stride,
+                                                                        p.stage_begin, p.stage_end, p.sps, h->scal_exp);
+}
+// The instantiations: all 4 NKQ factor pieces in both widths for NKQ <= 3; NKQ = 4 with all 16 pieces (8 wavefronts only: the 160-column
+// ring does not fit) and with the 13 pieces of k = 49 .. 52 in both widths (rows >= k of the split copy are zero: factor16_kernel).
 template <int NKQ>
 static void launch_xprod16_m(nnlm_handle *h, const Side &s, const HalfPlan &p, int q0 = 0)
 {
-    dim3 grid(p.tiles_x, p.S);
-    const int lds = xprod_tn_lds_bytes(16 * NKQ);
-    set_dyn_lds((const void *)xprod16_tn_kernel<NKQ>, lds, "xprod16_tn_kernel");
-    xprod16_tn_kernel<NKQ><<<grid, XPROD_THREADS, lds, h->stream>>>(s.A16 + (size_t)p.col_off * s.ldy, s.ldy, h->Y16 + (size_t)q0 * s.ldy, s.ldy,
-                                                                    h->Cx + (size_t)q0 * s.ldc + p.col_off, s.ldc, s.slab_stride, p.stage_begin,
-                                                                    p.stage_end, p.sps, h->scal_exp);
+    const bool trim = NKQ == 4 && xprod16_pieces(h->k - q0) == 13;
+    if constexpr (NKQ == 4) {
+        if (p.nwv == 10 && !trim) { // (xprod_plan admits 10 wavefronts only where the ring fits: not reached)
+            g_attr_err = hipErrorInvalidValue, g_attr_what = "xprod16_tn_kernel: 160-column blocks at a rank whose ring does not fit";
+            return;
+        }
+        if (trim && p.nwv == 10) launch_xprod16_nwy<4, 10, 13>(h, s, p, q0);
+        else if (trim) launch_xprod16_nwy<4, 8, 13>(h, s, p, q0);
+        else launch_xprod16_nwy<4, 8, 16>(h, s, p, q0);
+    } else {
+        if (p.nwv == 10) launch_xprod16_nwy<NKQ, 10, 4 * NKQ>(h, s, p, q0);
+        else launch_xprod16_nwy<NKQ, 8, 4 * NKQ>(h, s, p, q0);
+    }
+    h->xp_waves[s.which] = p.nwv, h->xp_splits[s.which] = p.S;
 }
 // split copy of the fixed factor, scaled by its own power of two (two small kernels, outside the cross product's timing
 // scope).  Measured: making these faster (2-D absmax grid, no memset) or moving sweep_consts_kernel to the Gram stream
@@ -2102,6 +2188,7 @@ static void launch_xprod16_err_m(nnlm_handle *h, const HalfPlan &p)
     }
     h->err_zero_word = nullptr;
     h->fused_nb = p.tiles_x * p.S;
+    h->xp_err_splits = p.S;
 }
 static void launch_xprod16(nnlm_handle *h, const Side &s, const HalfPlan &p)
 {
@@ -3112,7 +3199,7 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
     const bool colshard = h->sharded && (h->any_missing || h->dense_cols);
     if (colshard && phase == PH_A) return NNLM_OK;
     if (phase == PH_C || (phase == PH_B && !colshard)) {
-        const HalfPlan pp = plan_half(h, which, h->rank, h->nranks);
+        const HalfPlan pp = plan_half(h, which, h->rank, h->nranks, h->fuse_err);
         return half_step_solve(h, s, reg, inner_max_iter, inner_rel_tol, method, pp.S, speculative, phase, colshard);
     }
     if (h->any_missing) { // NA path workspaces, on first use
@@ -3120,13 +3207,13 @@ static int half_step(nnlm_handle *h, int which, const double reg[3], unsigned in
         if (rc == NNLM_OK) rc = ensure_gcols(h);
         if (rc != NNLM_OK) return rc;
     }
-    HalfPlan p = plan_half(h, which, colshard ? 0 : h->rank, colshard ? 1 : h->nranks);
+    HalfPlan p = plan_half(h, which, colshard ? 0 : h->rank, colshard ? 1 : h->nranks, h->fuse_err);
     if (colshard) { // own columns only, whole contraction
         const ShardCols sc = shard_cols(h, s.ncols);
         const int tile = XPROD_TN_BJ;
         p.col_off = sc.col0;
-        p.tiles_x = (sc.col1 - sc.col0 + tile - 1) / tile;
-        if (p.tiles_x > 0) split_plan(p.tiles_x, p.stage_end - p.stage_begin, &p.S, &p.sps);
+        p.tiles_x = 0, p.cols = 0;
+        if (sc.col1 > sc.col0) plan_cols(h, which, (sc.col1 - sc.col0 + tile - 1) / tile * tile, p, h->fuse_err);
         const size_t need = (size_t)p.S * s.slab_stride;
         if (need > h->Cx_elems) { // (fewer tiles -> deeper split-K than the single-GPU plan the slabs were sized for)
             sync_all(h);
@@ -3451,7 +3538,7 @@ extern "C" int nnlm_debug_partial(nnlm_handle *h, int which, double *G_out, doub
     const Side s = side_of(h, which);
     const int ld = s.ldc;
     if (!h->sharded) {
-        const HalfPlan q = plan_half(h, which, 0, 1);
+        const HalfPlan q = plan_half(h, which, 0, 1, h->fuse_err);
         const size_t cnt = s.slab_stride;
         slab_reduce_kernel<<<(unsigned)((cnt + 255) / 256), 256, 0, h->stream>>>(h->Cx, q.S, cnt, h->red + (size_t)h->KP * h->KP);
     }
@@ -3809,6 +3896,11 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
 {
     if (!h || !key || !value) return fail(h, NNLM_ERR_ARG, "nnlm_get_info: NULL argument");
     if (strcmp(key, "cus") == 0) *value = h->cus;
+    else if (strcmp(key, "xprod_waves_w") == 0) *value = h->xp_waves[0]; // (xprod16_tn_kernel, last launch of each side; 0 = none yet)
+    else if (strcmp(key, "xprod_waves_h") == 0) *value = h->xp_waves[1];
+    else if (strcmp(key, "xprod_splits_w") == 0) *value = h->xp_splits[0];
+    else if (strcmp(key, "xprod_splits_h") == 0) *value = h->xp_splits[1];
+    else if (strcmp(key, "xprod_splits_err") == 0) *value = h->xp_err_splits; // (xprod16_err_kernel: the W half-step of a trace iteration)
     else if (strcmp(key, "sweep_form_w") == 0) *value = h->sweep_form[0]; // (0 / 1 strict kernels, 2 k_sweep_f.h, 3 k_sweep_r.h)
     else if (strcmp(key, "sweep_form_h") == 0) *value = h->sweep_form[1];
     else if (strcmp(key, "sweep_groups_w") == 0) *value = h->sweep_groups[0];
@@ -3863,7 +3955,7 @@ extern "C" int nnlm_shard_range(int n, int m, int precision, int which, int rank
     t.m = m;
     t.npad = round_up_i(n, NNLM_PAD_N);
     t.mpad = round_up_i(m, NNLM_PAD_M);
-    const HalfPlan p = plan_half(&t, which, rank, nranks);
+    const HalfPlan p = plan_half(&t, which, rank, nranks, false);
     const int CE = stage_elems(&t);
     const int lim = side_of(&t, which).p;
     int c0 = p.stage_begin * CE, c1 = p.stage_end * CE;
@@ -3871,6 +3963,18 @@ extern "C" int nnlm_shard_range(int n, int m, int precision, int which, int rank
     if (c0 > c1) c0 = c1;
     *begin = c0;
     *end = c1;
+    return NNLM_OK;
+}
+
+// The plan of one xprod16_tn_kernel launch over ldc output columns (a multiple of 128) and `stages` contraction stages at rank k on
+// `cus` compute units, with `force_waves` as nnlm_debug_set_xprod_waves sets it.  Pure function; out[8] = wavefronts per block, slabs S,
+// stages per slab, tiles, blocks, factor pieces per stage, LDS bytes of a block, 0.
+extern "C" int nnlm_xprod_plan(int ldc, int stages, int k, int cus, int force_waves, int *out)
+{
+    if (ldc < 128 || ldc % 128 || stages < 1 || k < 1 || k > NNLM_KQ_MAX || cus < 1 || (force_waves != 0 && force_waves != 8 && force_waves != 10) || !out)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_xprod_plan: bad arguments");
+    const XPlan x = xprod_plan(ldc, stages, k, cus, force_waves, true);
+    out[0] = x.nwv, out[1] = x.S, out[2] = x.sps, out[3] = x.tiles_x, out[4] = x.tiles_x * x.S, out[5] = x.yp, out[6] = x.lds, out[7] = 0;
     return NNLM_OK;
 }
 
@@ -4361,7 +4465,7 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     h->sg_request = false;
     h->fuse_err = false;
     h->cur_which = which;
-    HalfPlan p = plan_half(h, which, 0, 1);
+    HalfPlan p = plan_half(h, which, 0, 1, h->fuse_err);
     if (h->sparse) p.S = 1; // (one slab: the SpMM has no split-K)
     // Hold-out handle with a non-empty set: A has missing entries, every column solves with a Gram of its own.  The
     // cross product below needs nothing new (A holds 0 at a missing entry); the NA workspaces: the row copy for the stacked KP (at least

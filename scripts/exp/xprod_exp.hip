@@ -1,4 +1,72 @@
 // Ablation micro-benchmark of xprod_tn_kernel (not part of the product).
+// -DXPROD_BLOCKS: instead of the round-5 ablations, time the PRODUCT's xprod16_tn_kernel (nnlm_amd/csrc/k_xprod16.h) at config 2's two
+// launches for {8, 10} wavefronts per block x {all 16, the 13 needed at k = 50} factor pieces, each at the slab counts that fill the
+// device best, and print the weight of a factor byte against a byte of A that the four times imply (XPLAN_Y_WEIGHT in nnlm_mi355x.hip).
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -DXPROD_BLOCKS scripts/exp/xprod_exp.hip -o scripts/exp/xprod_blocks_exp
+#ifdef XPROD_BLOCKS
+#include "../../nnlm_amd/csrc/k_xprod16.h"
+#include <cstdio>
+#include <cmath>
+#include <algorithm>
+#include <vector>
+#define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
+struct Times { float mean, sd, mn; };
+template <int NWV, int YP> static Times run16b(const uint32_t *A, int lda, const uint32_t *Y, int ldy, double *Cx, int ldc, int S, int stages, int reps, const int *sc)
+{
+    const int lds = xprod16_lds_bytes(NWV, 4, YP), tiles = (ldc + 16 * NWV - 1) / (16 * NWV), sps = (stages + S - 1) / S;
+    hipFuncSetAttribute((const void *)xprod16_tn_kernel<4, NWV, YP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    dim3 grid(tiles, (stages + sps - 1) / sps);
+    std::vector<hipEvent_t> ev(reps + 1);
+    for (auto &e : ev) hipEventCreate(&e);
+    for (int i = 0; i < 3; i++) xprod16_tn_kernel<4, NWV, YP><<<grid, 64 * NWV, lds>>>(A, lda, Y, ldy, Cx, ldc, ldc, (size_t)64 * ldc, 0, stages, sps, sc);
+    hipDeviceSynchronize();
+    hipEventRecord(ev[0]);
+    for (int i = 0; i < reps; i++) {
+        xprod16_tn_kernel<4, NWV, YP><<<grid, 64 * NWV, lds>>>(A, lda, Y, ldy, Cx, ldc, ldc, (size_t)64 * ldc, 0, stages, sps, sc);
+        hipEventRecord(ev[i + 1]);
+    }
+    hipEventSynchronize(ev[reps]);
+    std::vector<float> t(reps);
+    for (int i = 0; i < reps; i++) hipEventElapsedTime(&t[i], ev[i], ev[i + 1]);
+    for (auto &e : ev) hipEventDestroy(e);
+    double m = 0, v = 0;
+    for (float x : t) m += x;
+    m /= reps;
+    for (float x : t) v += (x - m) * (x - m);
+    return {(float)m, (float)std::sqrt(v / (reps - 1)), *std::min_element(t.begin(), t.end())};
+}
+int main()
+{
+    const int npad = 20224, mpad = 10112, reps = 30;
+    uint32_t *A, *Y; double *Cx; int *sc;
+    CK(hipMalloc(&A, (size_t)npad * mpad * 4)); CK(hipMalloc(&Y, (size_t)64 * npad * 4)); CK(hipMalloc(&Cx, (size_t)16 * 64 * npad * 8));
+    CK(hipMemset(A, 0x3c, (size_t)npad * mpad * 4)); CK(hipMemset(Y, 0x3c, (size_t)64 * npad * 4));
+    CK(hipMalloc(&sc, 8)); CK(hipMemset(sc, 0, 8));
+    const double gb = (double)npad * mpad * 4 / 1e9;
+    // {name, lda = contraction length, ldc = columns}
+    struct { const char *name; int len, cols; } L[2] = {{"H half-step (10112 cols x 316 stages)", npad, mpad}, {"W half-step (20224 cols x 158 stages)", mpad, npad}};
+    printf("| launch | waves | pieces | S | blocks | mean ms | sd | min ms | TB/s of A (mean) |\n|---|---|---|---|---|---|---|---|---|\n");
+    for (int l = 0; l < 2; l++) {
+        const int len = L[l].len, cols = L[l].cols, stages = len / 64;
+        double t8[2] = {0, 0}, t10[2] = {0, 0};
+        auto row = [&](int w, int yp, int S, Times t) {
+            const int tiles = (cols + 16 * w - 1) / (16 * w), sps = (stages + S - 1) / S;
+            printf("| %s | %d | %d | %d | %d | %.4f | %.4f | %.4f | %.2f |\n", L[l].name, w, yp, S, tiles * ((stages + sps - 1) / sps), t.mean, t.sd, t.mn, gb / t.mean);
+        };
+        for (int S : {2, 3, 4}) {
+            Times a = run16b<8, 16>(A, len, Y, len, Cx, cols, S, stages, reps, sc), b = run16b<8, 13>(A, len, Y, len, Cx, cols, S, stages, reps, sc);
+            Times c = run16b<10, 13>(A, len, Y, len, Cx, cols, S, stages, reps, sc);
+            row(8, 16, S, a), row(8, 13, S, b), row(10, 13, S, c);
+            if (S == 3) t8[0] = a.mean, t8[1] = b.mean;
+            if ((l == 0 && S == 4) || (l == 1 && S == 2)) t10[0] = c.mean;
+        }
+        // T ~ A bytes + w * factor bytes per stage at fixed geometry:  T(8,16) / T(8,13) = (32768 + 16384 w) / (32768 + 13312 w)
+        const double r = t8[0] / t8[1], w = 32768.0 * (r - 1.0) / (16384.0 - 13312.0 * r);
+        printf("%s: factor-byte weight implied by 8 waves, 16 vs 13 pieces at S = 3: %.3f; best 10-wave / 8-wave trimmed = %.4f\n", L[l].name, w, t10[0] / t8[1]);
+    }
+    return 0;
+}
+#else
 #include "csrc_r5/k_xprod.h"
 #include "csrc_r5/k_xprod16.h"
 #include <cstdio>
@@ -58,3 +126,4 @@ int main()
     }
     return 0;
 }
+#endif
