@@ -194,6 +194,16 @@ int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr
  * walk over the non-zeros for the error sums of all members.  The batch's own limits hold (methods 1 and 2, rank sum <= 64, no
  * communicator).  A handle loaded by any other sparse entry refuses the batch entries as before.  nnlm_get_info: "sparse_batch". */
 int nnlm_set_matrix_csc_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* nnlm_set_matrix_csc_kl for restarts and rank sweeps of count data: the same arguments, contract and validation (a negative stored
+ * value is refused) and the same resident layout.  The handle is the sparse KL handle nnlm_set_matrix_csc_kl leaves -- solo calls behave
+ * bit for bit as there -- and ALSO accepts nnlm_set_factors_batch, nnlm_run_batch and nnlm_get_factors_batch with ALL FOUR methods.
+ * Methods 1 and 2 run as on a handle of nnlm_set_matrix_csc_batch, bit for bit.  Methods 3 and 4 (KL loss): per half-step one row copy
+ * and one column-sum launch for the stacked fixed factor, then ONE solver launch over the lines of at most "sparse_kl_short_max" stored
+ * entries for all active members (a wavefront per line interleaves "sparse_kl_batch_group" members); a longer line is solved once per
+ * member.  Member b of the batch equals the solo fit of rank k[b] on an nnlm_set_matrix_csc_kl handle from the same start after the
+ * same number of iterations BIT FOR BIT (the traces differ by the error block's summation order).  The batch's other limits hold (rank
+ * sum <= 64, no masks, no communicator).  nnlm_get_info: "sparse_kl_batch". */
+int nnlm_set_matrix_csc_kl_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
 /* The same CSC contract and validation as nnlm_set_matrix_csc, but absent entries are MISSING (a score matrix: movies x customers): every
  * stored entry is an observation, an explicitly stored zero included, and the factorisation fits the stored entries only -- the
  * reference's update_with_missing() (src/update_with_missing.cpp:58-139) on the matrix with NA at the absent entries, without anything
@@ -322,8 +332,9 @@ int nnlm_sync(nnlm_handle *h);
  * Missing entries are accepted in ONE form: a hold-out handle (nnlm_set_matrix_holdout).  Every member then solves each column with the
  * Gram over that column's observed rows, as a solo missing-value run does, behind the same single cross product; the traces' sums
  * run over the training entries.  A matrix that arrived with NA / NaN / Inf through nnlm_set_matrix stays refused.
- * A sparse A is accepted through two doors: nnlm_set_matrix_csc_batch (absent entries zeros) and nnlm_set_matrix_csc_missing_batch
- * (absent entries missing, with or without a hold-out set).
+ * A sparse A is accepted through three doors: nnlm_set_matrix_csc_batch (absent entries zeros), nnlm_set_matrix_csc_missing_batch
+ * (absent entries missing, with or without a hold-out set) and nnlm_set_matrix_csc_kl_batch (absent entries zeros, stored values >= 0:
+ * the one handle on which the batch also runs methods 3 and 4, KL loss).
  * ---------------------------------------------------------------------------------------- */
 /* k[B] ranks; W = the members' n x k[b] blocks one after another (column-major each), H = their k[b] x m blocks one after another;
  * NULL = zeros.  Replaces the handle's factors (nnlm_set_factors ends a batch). */
@@ -354,6 +365,14 @@ int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, const int *rowi
                           int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
                           double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
                           const nnlm_callbacks *cb);
+
+/* nnlm_c_nnmf_csc_batch through nnlm_set_matrix_csc_kl_batch: the same arguments, all four methods (KL loss: stored values >= 0). */
+int nnlm_c_nnmf_csc_kl_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned B, const unsigned *k,
+                             const double *W_init, const double *H_init, const double alpha[3], const double beta[3], unsigned max_iter,
+                             double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                             int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                             double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                             const nnlm_callbacks *cb);
 
 /* nnlm_c_nnmf_csc_batch on a sparse A whose absent entries are MISSING (nnlm_set_matrix_csc_missing_batch), with an optional hold-out
  * pattern ho_colptr / ho_rowidx after x (ho_colptr NULL: none) and holdout_mse[B], holdout_mkl[B] at the end: nnlm_holdout_errors of the
@@ -462,10 +481,14 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * "sp_gram_workers" (sp_gram_kernel workers of the last half-step whose absent entries are missing, summed over its column chunks),
  * "sp_gram_batch_pairs" (upper 16 x 16 tile pairs of the stacked Gram that the sp_gram_batch_kernel launches of the last batch half-step
  * on a handle loaded by nnlm_set_matrix_csc_missing_batch formed: those meeting an ACTIVE member's diagonal block; 0 none yet),
- * "sparse_batch" (1 after nnlm_set_matrix_csc_batch or nnlm_set_matrix_csc_missing_batch, else 0), "sp_batch_waves" (wavefronts of one sp_batch_errors_kernel launch on the
+ * "sparse_batch" (1 after nnlm_set_matrix_csc_batch, nnlm_set_matrix_csc_missing_batch or nnlm_set_matrix_csc_kl_batch, else 0), "sp_batch_waves" (wavefronts of one sp_batch_errors_kernel launch on the
  * resident sparse matrix -- a function of its non-zeros and the CU count only --, 0 without one), "sparse_kl" (1 after nnlm_set_matrix_csc_kl, else 0), "sparse_kl_form_w" / "sparse_kl_form_h" (KL solver forms of the last W / H half-step on
  * such a handle: bit 0 = sp_kl_solve_kernel ran, a wavefront per line of at most "sparse_kl_short_max" stored entries; bit 1 =
- * sp_kl_solve_long_kernel ran, a workgroup per longer line; -1 none yet). */
+ * sp_kl_solve_long_kernel ran, a workgroup per longer line; -1 none yet), "sparse_kl_batch" (1 after nnlm_set_matrix_csc_kl_batch, else
+ * 0), "sparse_kl_batch_form_w" / "sparse_kl_batch_form_h" (forms of the last batched KL W / H half-step: bit 0 = sp_kl_batch_kernel ran,
+ * one launch over the short lines for all active members; bit 1 = sp_kl_solve_long_kernel ran once per active member; -1 none yet),
+ * "sparse_kl_batch_group" (member chains a wavefront of sp_kl_batch_kernel interleaves: 1, 2 or 4; the library's default, or the value of
+ * the environment variable NNLM_SPKL_BATCH_GROUP when the handle was created -- results do not depend on it, only the time). */
 int nnlm_get_info(nnlm_handle *h, const char *key, double *value);
 
 #ifdef __cplusplus

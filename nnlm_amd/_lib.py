@@ -41,6 +41,7 @@ EXPORTS = [
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
     "nnlm_predict_entries", "nnlm_top_n",
     "nnlm_set_matrix_csc_batch", "nnlm_c_nnmf_csc_batch",
+    "nnlm_set_matrix_csc_kl_batch", "nnlm_c_nnmf_csc_kl_batch",
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
 ]
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
@@ -186,6 +187,10 @@ def load():
     lib.nnlm_c_nnmf_csc_batch.argtypes = [C.c_int, C.c_int, lp, ip, dp] + lib.nnlm_c_nnmf_batch.argtypes[3:]
     lib.nnlm_set_matrix_csc_batch.restype = C.c_int
     lib.nnlm_set_matrix_csc_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes
+    lib.nnlm_c_nnmf_csc_kl_batch.restype = C.c_int
+    lib.nnlm_c_nnmf_csc_kl_batch.argtypes = lib.nnlm_c_nnmf_csc_batch.argtypes
+    lib.nnlm_set_matrix_csc_kl_batch.restype = C.c_int
+    lib.nnlm_set_matrix_csc_kl_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes
     lib.nnlm_set_matrix_csc_missing_batch.restype = C.c_int
     lib.nnlm_set_matrix_csc_missing_batch.argtypes = lib.nnlm_set_matrix_csc.argtypes + [lp, ip]
     lib.nnlm_c_nnmf_csc_missing_batch.restype = C.c_int
@@ -512,6 +517,16 @@ def c_nnmf_csc_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_it
                         method, trace, callbacks, _csc=(n, m, ptr, idx, val))
 
 
+def c_nnmf_csc_kl_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
+                        inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_csc_batch through nnlm_set_matrix_csc_kl_batch (nnlm_c_nnmf_csc_kl_batch): all four methods (KL loss over the stored
+    entries; stored values >= 0); per KL half-step one solver launch over the short lines for all members."""
+    n, m = (int(v) for v in shape)
+    ptr, idx, val = _csc_arrays(indptr, indices, data)
+    return c_nnmf_batch(None, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol,
+                        method, trace, callbacks, _csc=(n, m, ptr, idx, val), _csc_kl=True)
+
+
 def c_nnmf_csc_missing_batch(indptr, indices, data, shape, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
                              inner_max_iter, inner_rel_tol, method, trace, callbacks=None, holdout=None):
     """c_nnmf_csc_batch with the absent entries of A MISSING (nnlm_c_nnmf_csc_missing_batch).  holdout: None or a CSC pattern
@@ -537,7 +552,7 @@ def _holdout_pattern(holdout, m):
 
 
 def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
-                 trace, callbacks=None, _holdout=None, _csc=None, _csc_missing=None):
+                 trace, callbacks=None, _holdout=None, _csc=None, _csc_missing=None, _csc_kl=False):
     """Batched c_nnmf (nnlm_c_nnmf_batch): member b has rank ks[b] and starts from W[b] (n x k_b), H[b] (k_b x m) -- either list may
     be None for the library's default init.  Returns one c_nnmf-style dict per member."""
     lib = load()
@@ -567,7 +582,8 @@ def c_nnmf_batch(A, ks, W, H, alpha, beta, max_iter, rel_tol, n_threads, verbose
         rc = lib.nnlm_c_nnmf_csc_missing_batch(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), _lp(ho[0]) if ho else None,
                                                _ip(ho[1]) if ho else None, *args, _dp(hmse), _dp(hmkl), cbp)
     elif _csc is not None:
-        rc = lib.nnlm_c_nnmf_csc_batch(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), *args, cbp)
+        entry = lib.nnlm_c_nnmf_csc_kl_batch if _csc_kl else lib.nnlm_c_nnmf_csc_batch
+        rc = entry(n, m, _lp(_csc[2]), _ip(_csc[3]), _dp(_csc[4]), *args, cbp)
     elif _holdout is None:
         rc = lib.nnlm_c_nnmf_batch(_dp(A), n, m, *args, cbp)
     else:
@@ -721,6 +737,14 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc_kl(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_kl_batch(self, indptr, indices, data, shape):
+        """set_matrix_csc_kl for restarts and rank sweeps: the same sparse KL handle, which also accepts set_factors_batch / run_batch
+        with all four methods."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc_kl_batch(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
         self.n, self.m = n, m
 
     def set_matrix_csc_missing(self, indptr, indices, data, shape):

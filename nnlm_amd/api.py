@@ -550,8 +550,14 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     included, is an observation): per half-step one SpMM and, per column chunk, one launch for the per-column Grams of all members.
     check_k's bound is the fewest stored entries of a row or a column, as for nnmf(absent = 'missing'); ``absent``, if given with it, must
     be 'missing'; a dense A is refused.
+
+    ``sparse_batch`` = "kl" takes a sparse A of counts (stored values >= 0, absent entries zeros) and admits loss = 'mkl' (method "scd"
+    or "lee"): per half-step one solver launch over the lines of at most 256 stored entries for all members; member b is bit for bit
+    nnmf(A, k_b, loss = 'mkl', sparse_kl = True) from the same start.  loss = 'mse' with it behaves as ``sparse_batch`` = True.  A dense
+    A and absent = 'missing' are refused; without it loss = 'mkl' is refused as before.
     """
     missing_door = _sparse_batch_arg(sparse_batch, "nnmf_batch")
+    kl_door = sparse_batch == "kl" if isinstance(sparse_batch, str) else False
     sparse_batch = bool(sparse_batch)
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
@@ -564,10 +570,15 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
         raise unsupported("masks are not supported by the batched factorisation")
     if init is not None and any(x.get("W0") is not None or x.get("H0") is not None for x in init):
         raise unsupported("known profiles (W0 / H0) are not supported by the batched factorisation")
-    if _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss") != "mse":
+    loss = _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss")
+    if loss != "mse" and not kl_door:
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
     if is_sparse(A) and not sparse_batch:
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
+    if kl_door and not is_sparse(A):
+        raise unsupported("sparse_batch = 'kl' needs a sparse A (an object with tocsc()): the batched KL solver runs over the stored "
+                          "entries of a sparse count matrix")
+    kl_door = kl_door and loss == "mkl"  # (square loss through this door: sparse_batch = True)
     if missing_door:
         _missing_door_checks(A, nnmf_options, unsupported)
         nnmf_options = dict(nnmf_options, absent="missing")
@@ -594,18 +605,24 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     if on_device:  # one ingest shared by all members; the handle then runs the batch (what nnlm_c_nnmf_batch does around a host A)
         h = _lib.Handle(_device_index(A), _env_precision())
     try:
-        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door)
+        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door, kl_door)
     finally:
         if h is not None:
             h.close()
 
 
 def _sparse_batch_arg(sparse_batch, who):
-    """True when sparse_batch is the string "missing" (the door of a sparse A whose absent entries are missing); any other string is an
-    argument error, anything else is the flag it has always been."""
+    """True when sparse_batch is the string "missing" (the door of a sparse A whose absent entries are missing); "kl" (nnmf_batch's door
+    of KL loss on a sparse count matrix) passes as not that door; any other string is an argument error, anything else is the flag it
+    has always been."""
     if isinstance(sparse_batch, str):
+        if sparse_batch == "kl":
+            if who == "nnmf_cv":
+                raise _lib.NnlmError(_lib.ERR_UNSUPPORTED, "nnmf_cv: sparse_batch = 'kl' is not supported: a hold-out set on a sparse matrix "
+                                                           "whose absent entries are zeros is not built (use nnmf_batch)")
+            return False
         if sparse_batch != "missing":
-            raise _lib.NnlmError(_lib.ERR_ARG, "%s: sparse_batch must be False, True or 'missing' (got %r)" % (who, sparse_batch))
+            raise _lib.NnlmError(_lib.ERR_ARG, "%s: sparse_batch must be False, True, 'missing' or 'kl' (got %r)" % (who, sparse_batch))
         return True
     return False
 
@@ -620,7 +637,7 @@ def _missing_door_checks(A, nnmf_options, unsupported):
                           "entries are missing); use sparse_batch = True for absent entries that are zeros")
 
 
-def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False):
+def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False, kl_door=False):
     """nnmf_batch behind its argument checks; h: the handle of a device A (None for a host A)."""
     B = len(ks)
     prep, Ws, Hs, mat = [], [], [], None
@@ -630,12 +647,14 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
     elif missing_door:  # (canonical CSC once for all members; check_k's bound: the fewest stored entries of a line)
         mat = _nnmf_matrix_missing(A, "mse")
-    elif is_sparse(A):  # (sparse_batch = True: canonical CSC once for all members; check_k's bound is min(n, m))
-        c = _sparse_input(A, "A", "mse")
+    elif is_sparse(A):  # (sparse_batch = True / 'kl': canonical CSC once for all members; check_k's bound is min(n, m))
+        c = _sparse_input(A, "A", "mkl" if kl_door else "mse", sparse_kl=kl_door)
         mat = dict(A=c, n=c.shape[0], m=c.shape[1], min_k=min(c.shape))
     for b in range(B):  # member after member, each consuming the generator as nnmf() would
         # (A is checked and converted by the first member's call only: every member shares that one fp64 copy)
         args, ctx, mat = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
+        if kl_door:
+            ctx["sparse_kl"] = True  # (what nnmf(sparse_kl = True) records for the same member)
         if b == 0 and h is None and not isinstance(mat["A"], CSC) and not np.isfinite(mat["A"]).all():
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
         n, m = mat["n"], mat["m"]
@@ -649,7 +668,8 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False
     if missing_door:
         outs = _lib.c_nnmf_csc_missing_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     elif isinstance(a0[0], CSC):
-        outs = _lib.c_nnmf_csc_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
+        entry = _lib.c_nnmf_csc_kl_batch if kl_door else _lib.c_nnmf_csc_batch
+        outs = entry(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     elif h is None:
         outs = _lib.c_nnmf_batch(a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     else:

@@ -84,7 +84,7 @@ __device__ static inline double spkl_update(const SpKlArgs &a, double s0, double
     if (METHOD == 4) { // src/base_algorithms.cpp:141-147
         double tmp = s0 / (sumw + a.r0 * xq + a.r1 * (S - xq) + a.r2);
         *coef = (tmp - 1) * xq;
-        S += (tmp - 1) * xq;
+        S = __builtin_fma(tmp - 1, xq, S); // (one rounding, written out: the contraction every instantiation had chosen must not depend on the caller)
         const double xn = xq * tmp;
         tmp = 2 * fabs(tmp - 1) / (tmp + 1);
         if (tmp > rel) rel = tmp;

@@ -29,6 +29,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <atomic>
 #include <climits>
 #include <cmath>
@@ -46,7 +47,7 @@ static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
               P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES,
-              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_COUNT };
+              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_SPKL_BATCH_H, P_SPKL_BATCH_W, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -63,9 +64,11 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  solver launches (k_sparse_kl.h: starting states in the prologue, short and long form)
 //  "sp_batch_errors": the error block of a batched factorisation on a sparse A (k_sparse_batch.h: the row copies, the stacked Grams and
 //  coordinate sums, ONE sp_batch_errors_kernel launch over the non-zeros for all members, its reduction and the closing kernel)
+//  "spkl_batch_h" / "spkl_batch_w": the solver launches of a batched KL half-step on a sparse A (k_sparse_kl_batch.h: ONE launch over the
+//  short lines for all active members, then the long form once per active member); its row copy and column sums are in "spkl_copy"
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
                                           "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries",
-                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors"};
+                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors", "spkl_batch_h", "spkl_batch_w"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -173,6 +176,8 @@ struct nnlm_handle {
     int spkl_nlong[2] = {0, 0}, spkl_nshort[2] = {0, 0};
     void *spkl_state = nullptr;     // [nnz] states of the long lines' entries (mode's type), on first use
     int spkl_form[2] = {-1, -1};    // per half-step: forms of its last KL launch (bit 0 short, bit 1 long; nnlm_get_info)
+    int spklb_form[2] = {-1, -1};   // the same of its last BATCHED KL launch (bit 0: sp_kl_batch_kernel, bit 1: per-member long launches)
+    int spklb_group = nnlm_spkl_batch_group(); // member chains a wavefront of sp_kl_batch_kernel interleaves
     std::vector<long long> spg_hptr[2];
     long long *spg_segoff[2] = {nullptr, nullptr};
     int *spg_longc[2] = {nullptr, nullptr};
@@ -786,7 +791,7 @@ static void free_matrix(nnlm_handle *h)
         hipFree(h->spkl_longc[o]);
         h->spkl_longc[o] = nullptr;
         h->spkl_nlong[o] = h->spkl_nshort[o] = 0;
-        h->spkl_form[o] = -1;
+        h->spkl_form[o] = h->spklb_form[o] = -1;
     }
     hipFree(h->spkl_state);
     h->spkl_state = nullptr;
@@ -1522,6 +1527,15 @@ extern "C" int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const l
 extern "C" int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
 {
     return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_kl", true);
+}
+
+// The sparse KL handle of nnlm_set_matrix_csc_kl (same arguments, checks, resident layout and long-line lists) that the batch entries also
+// accept, with all four methods: the flag is all that differs
+extern "C" int nnlm_set_matrix_csc_kl_batch(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
+{
+    const int rc = set_matrix_csc_impl(h, n, m, colptr, rowidx, x, false, "nnlm_set_matrix_csc_kl_batch", true);
+    if (rc == NNLM_OK) h->sp_batch = true;
+    return rc;
 }
 
 // The sparse handle of nnlm_set_matrix_csc (same arguments, checks and resident layout; absent entries are zeros) that the batch entries
@@ -3923,6 +3937,10 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sparse_kl_form_w") == 0) *value = h->spkl_form[0];
     else if (strcmp(key, "sparse_kl_form_h") == 0) *value = h->spkl_form[1];
     else if (strcmp(key, "sparse_kl_short_max") == 0) *value = nnlm_spkl_short_max();
+    else if (strcmp(key, "sparse_kl_batch") == 0) *value = (h->sparse && h->sp_kl && h->sp_batch) ? 1.0 : 0.0;
+    else if (strcmp(key, "sparse_kl_batch_form_w") == 0) *value = h->spklb_form[0];
+    else if (strcmp(key, "sparse_kl_batch_form_h") == 0) *value = h->spklb_form[1];
+    else if (strcmp(key, "sparse_kl_batch_group") == 0) *value = h->spklb_group;
     else if (strcmp(key, "sp_gram_chunks") == 0) *value = h->spg_chunks;
     else if (strcmp(key, "sp_gram_bytes") == 0) *value = (double)h->spg_buf_bytes;
     else if (strcmp(key, "sp_workers") == 0) *value = (h->sparse && h->KP > 0) ? nnlm_sp_workers(h->nnz, h->KP, h->cus_device) : 0;
@@ -4266,11 +4284,11 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
 static_assert(SPB_BATCH_MAX == BATCH_MAX, "sp_batch_errors_kernel keeps one LDS slot per member");
 static int batch_refusal(nnlm_handle *h, const char *who)
 {
-    if (h->sparse && h->sp_kl)
+    if (h->sparse && h->sp_kl && !h->sp_batch)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl) is not supported by the batched factorisation "
                                              "(dense A, square loss only)", who);
-    // (the doors: a sparse matrix loaded by nnlm_set_matrix_csc_batch -- absent entries zeros, square loss -- or by
-    //  nnlm_set_matrix_csc_missing_batch -- absent entries missing -- passes)
+    // (the doors: a sparse matrix loaded by nnlm_set_matrix_csc_batch -- absent entries zeros, square loss --, by
+    //  nnlm_set_matrix_csc_kl_batch -- the same with KL loss too -- or by nnlm_set_matrix_csc_missing_batch -- absent entries missing -- passes)
     if (h->sparse && !h->sp_batch)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is not supported by the batched factorisation (dense A only)", who);
     if (h->any_missing && !h->holdout && !h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A", who);
@@ -4450,6 +4468,78 @@ static int batch_solve_sparse_missing(nnlm_handle *h, const Side &s, const doubl
     return NNLM_OK;
 }
 
+// KL half-step of every active member on a sparse A loaded by nnlm_set_matrix_csc_kl_batch (no SpMM, no Gram, no Cx):
+// ONE row copy of the stacked fixed factor and ONE launch for the column sums of its K coordinates, then ONE sp_kl_batch_kernel launch
+// over the short lines for all active members (k_sparse_kl_batch.h; larger ranks first, so that the members a wavefront interleaves have
+// ranks close to each other -- a member's result does not depend on the order).  Lines beyond the short form stay per member:
+// sp_kl_solve_long_kernel as half_step_sparse_kl launches it, on the member's offsets, one member after another on the stream, so the
+// one state per stored entry (spkl_state) serves them all.
+static int batch_half_step_sparse_kl(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
+                                     const std::vector<char> &act)
+{
+    const int o = s.which, B = h->bB;
+    const bool f64 = h->prec == NNLM_PREC_F64;
+    const size_t es = esize(h);
+    int rc = ensure_klsw(h);
+    if (rc != NNLM_OK) return rc;
+    if (h->spkl_nlong[o] > 0 && !h->spkl_state) HIPCHK(h, hipMalloc(&h->spkl_state, (size_t)h->nnz * es + 64));
+    {
+        ProfScope ps(h, P_SPKL_COPY);
+        if (f64) factor_rows_kernel<double><<<(s.p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->KP, (double *)h->sp_Y);
+        else factor_rows_kernel<float><<<(s.p + 255) / 256, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->KP, (float *)h->sp_Y);
+        kl_sumw_kernel<<<h->k, 256, 0, h->stream>>>(s.Y, s.ldy, s.p, h->klsw);
+    }
+    SpKlBatchArgs ba;
+    SpKlArgs &a = ba.a;
+    a.ptr = s.sp_ptr; a.idx = s.sp_idx; a.val = s.sp_val;
+    a.Y = h->sp_Y;
+    a.KP = h->KP; a.ncols = s.ncols; a.k = h->k;
+    a.X = s.X; a.Xout = s.Xout; a.ldx = s.ldc;
+    a.sumw = h->klsw;
+    a.r0 = reg[0]; a.r1 = reg[1]; a.r2 = reg[2];
+    a.mask = nullptr; a.mw = 1; // (a batch has no masks)
+    a.max_iter = inner_max_iter; a.rel_tol = inner_rel_tol;
+    a.op = s.op; a.op_mode = s.op ? s.op_mode : 0; a.op_ld = s.op_ld;
+    a.sweeps = nullptr;
+    a.state = h->spkl_state;
+    a.longc = h->spkl_longc[o];
+    a.nlong = h->spkl_nlong[o];
+    ba.sweeps = h->bsweeps;
+    ba.nmem = 0;
+    for (int b = 0; b < 64; b++) ba.mem[b] = ba.off[b] = ba.kb[b] = 0;
+    for (int b = 0; b < B; b++) {
+        ba.off[b] = (unsigned char)h->boff[b];
+        ba.kb[b] = (unsigned char)h->bk[b];
+        if (act[b]) ba.mem[ba.nmem++] = (unsigned char)b;
+    }
+    std::stable_sort(ba.mem, ba.mem + ba.nmem, [&](unsigned char x, unsigned char y) { return h->bk[x] > h->bk[y]; });
+    int form = 0;
+    {
+        ProfScope ps(h, o == 1 ? P_SPKL_BATCH_H : P_SPKL_BATCH_W);
+        if (h->spkl_nshort[o] > 0 && ba.nmem > 0) {
+            nnlm_tu_sp_kl_batch(ba, method, f64, h->spklb_group, h->stream);
+            form |= 1;
+        }
+        for (int b = 0; b < B && a.nlong > 0; b++) {
+            if (!act[b]) continue;
+            const int ob = h->boff[b];
+            SpKlArgs m = a;
+            m.Y = (const char *)a.Y + (size_t)ob * es; // (the member's coordinates of a row of the stacked copy; the row stride stays a.KP)
+            m.k = h->bk[b];
+            m.X = a.X + (size_t)ob * a.ldx;
+            m.Xout = a.Xout + (size_t)ob * a.ldx;
+            m.sumw = a.sumw + ob;
+            if (a.op) m.op = (char *)a.op + (size_t)ob * a.op_ld * es;
+            m.sweeps = h->bsweeps + b;
+            nnlm_tu_sp_kl_long(m, method, f64, h->stream);
+            form |= 2;
+        }
+    }
+    h->spklb_form[o] = form;
+    LAUNCHCHK(h);
+    return NNLM_OK;
+}
+
 // One half-step of every active member (act[b] != 0).  W is solved in place (no speculation, so no second buffer): a frozen member's
 // rows are never written.
 static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
@@ -4465,6 +4555,7 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
     h->sg_request = false;
     h->fuse_err = false;
     h->cur_which = which;
+    if (method >= 3) return batch_half_step_sparse_kl(h, s, reg, inner_max_iter, inner_rel_tol, method, act); // (nnlm_run_batch: that handle only)
     HalfPlan p = plan_half(h, which, 0, 1, h->fuse_err);
     if (h->sparse) p.S = 1; // (one slab: the SpMM has no split-K)
     // Hold-out handle with a non-empty set: A has missing entries, every column solves with a Gram of its own.  The
@@ -4657,7 +4748,9 @@ extern "C" int nnlm_run_batch(nnlm_handle *h, const double alpha[3], const doubl
                 n_trace, n_iteration, warned, cb};
     int rc = L.check("nnlm_run_batch");
     if (rc != NNLM_OK) return rc;
-    if (method >= 3) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_run_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
+    // (KL loss: the handle of nnlm_set_matrix_csc_kl_batch alone)
+    if (method >= 3 && !(h->sparse && h->sp_kl && h->sp_batch))
+        return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_run_batch: method %d (KL loss) is not supported by the batched factorisation: square loss (methods 1, 2) only", method);
     rc = batch_refusal(h, "nnlm_run_batch");
     if (rc != NNLM_OK) return rc;
     HIPCHK(h, hipSetDevice(h->device));
@@ -5052,6 +5145,32 @@ extern "C" int nnlm_c_nnmf_csc_batch(int n, int m, const long long *colptr, cons
     if (rc != NNLM_OK) return rc;
     OneShot os;
     rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix_csc_batch(h, n, m, colptr, rowidx, x); });
+    if (rc != NNLM_OK) return rc;
+    nnlm_handle *h = os.h;
+    std::vector<double> Wi, Hi;
+    default_factors(cb, n, m, B, k, nullptr, nullptr, &W_init, &H_init, Wi, Hi);
+    CHK(nnlm_set_factors_batch(h, B, k, W_init, H_init));
+    CHK(nnlm_run_batch(h, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, mse_error,
+                       mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb));
+    CHK(nnlm_get_factors_batch(h, W_out, H_out));
+    return NNLM_OK;
+}
+
+// nnlm_c_nnmf_csc_batch through nnlm_set_matrix_csc_kl_batch: the same arguments, all four methods (KL loss: stored values >= 0)
+extern "C" int nnlm_c_nnmf_csc_kl_batch(int n, int m, const long long *colptr, const int *rowidx, const double *x, unsigned B, const unsigned *k,
+                                        const double *W_init, const double *H_init, const double alpha[3], const double beta[3], unsigned max_iter,
+                                        double rel_tol, int n_threads, int verbose, int show_warning, unsigned inner_max_iter, double inner_rel_tol,
+                                        int method, unsigned trace, double *W_out, double *H_out, double *mse_error, double *mkl_error,
+                                        double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
+                                        const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    if (any_null(colptr, k, alpha, beta, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned))
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_c_nnmf_csc_kl_batch: NULL argument");
+    int rc = batch_ranks(nullptr, "nnlm_c_nnmf_csc_kl_batch", "members", B, k, [&] { return NNLM_OK; });
+    if (rc != NNLM_OK) return rc;
+    OneShot os;
+    rc = os.open([&](nnlm_handle *h) { return nnlm_set_matrix_csc_kl_batch(h, n, m, colptr, rowidx, x); });
     if (rc != NNLM_OK) return rc;
     nnlm_handle *h = os.h;
     std::vector<double> Wi, Hi;

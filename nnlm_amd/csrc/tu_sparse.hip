@@ -1,10 +1,13 @@
-// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_na_batch.h, k_sparse_kl.h), see tu_sweepq.h.
+// tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_na_batch.h, k_sparse_kl.h,
+// k_sparse_kl_batch.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
 #include "k_sparse_batch.h"
 #include "k_sparse_na.h"
 #include "k_sparse_na_batch.h"
 #include "k_sparse_kl.h"
+#include "k_sparse_kl_batch.h"
+#include <cstdlib>
 
 // Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
 // launched once per 64 coordinates)
@@ -201,5 +204,45 @@ void nnlm_tu_sp_kl(const SpKlArgs &a, int method, bool f64, int nshort, hipStrea
     } else {
         if (f64) launch_sp_kl<4, double>(a, nshort, st);
         else launch_sp_kl<4, float>(a, nshort, st);
+    }
+}
+
+void nnlm_tu_sp_kl_long(const SpKlArgs &a, int method, bool f64, hipStream_t st)
+{
+    if (a.nlong <= 0) return;
+    if (method == 3) {
+        if (f64) sp_kl_solve_long_kernel<3, double><<<a.nlong, 256, 0, st>>>(a);
+        else sp_kl_solve_long_kernel<3, float><<<a.nlong, 256, 0, st>>>(a);
+    } else {
+        if (f64) sp_kl_solve_long_kernel<4, double><<<a.nlong, 256, 0, st>>>(a);
+        else sp_kl_solve_long_kernel<4, float><<<a.nlong, 256, 0, st>>>(a);
+    }
+}
+
+// ---- KL loss, batched (k_sparse_kl_batch.h) ----
+int nnlm_spkl_batch_group(void)
+{
+    const char *e = getenv("NNLM_SPKL_BATCH_GROUP");
+    const int g = e ? atoi(e) : SPKL_BATCH_G;
+    return (g == 1 || g == 2 || g == 4) ? g : SPKL_BATCH_G;
+}
+
+template <int METHOD, typename T> static void launch_sp_kl_batch(const SpKlBatchArgs &a, int group, hipStream_t st)
+{
+    const int nb = (a.a.ncols + 3) / 4;
+    switch (group) {
+    case 1: sp_kl_batch_kernel<METHOD, T, 1><<<nb, 256, 0, st>>>(a); break;
+    case 2: sp_kl_batch_kernel<METHOD, T, 2><<<nb, 256, 0, st>>>(a); break;
+    default: sp_kl_batch_kernel<METHOD, T, 4><<<nb, 256, 0, st>>>(a); break;
+    }
+}
+void nnlm_tu_sp_kl_batch(const SpKlBatchArgs &a, int method, bool f64, int group, hipStream_t st)
+{
+    if (method == 3) {
+        if (f64) launch_sp_kl_batch<3, double>(a, group, st);
+        else launch_sp_kl_batch<3, float>(a, group, st);
+    } else {
+        if (f64) launch_sp_kl_batch<4, double>(a, group, st);
+        else launch_sp_kl_batch<4, float>(a, group, st);
     }
 }

@@ -124,3 +124,20 @@ struct SpKlArgs {
 int nnlm_spkl_short_max(void);
 // method 3 (SCD) or 4 (Lee); short form over all lines (it skips the long ones) when nshort > 0, long form over a.longc when a.nlong > 0
 void nnlm_tu_sp_kl(const SpKlArgs &a, int method, bool f64, int nshort, hipStream_t st);
+
+// The same half-step for the active members of a batch (k_sparse_kl_batch.h): a.Y, a.X, a.Xout, a.sumw and a.op are
+// the STACKED factor's, a.k the sum of the ranks, a.mask NULL.  Member b holds the coordinates off[b] .. off[b] + kb[b] - 1 and counts
+// its sweeps in sweeps[b]; mem[0 .. nmem) lists the members that run (the others' rows are neither read for a sum nor written).
+struct SpKlBatchArgs {
+    SpKlArgs a;
+    unsigned long long *sweeps; // [B]
+    int nmem;
+    unsigned char mem[64], off[64], kb[64];
+};
+#define SPKL_BATCH_G 2 // member chains a wavefront interleaves: the lowest time of 1, 2, 4 at 1 % / F32 / 8 x 8, by under 1 %
+// the group size a new handle takes: SPKL_BATCH_G, or NNLM_SPKL_BATCH_GROUP = 1, 2 or 4 (the measurement's switch)
+int nnlm_spkl_batch_group(void);
+// ONE launch over all lines of at most nnlm_spkl_short_max() stored entries, group = 1, 2 or 4; the longer lines stay the caller's
+void nnlm_tu_sp_kl_batch(const SpKlBatchArgs &a, int method, bool f64, int group, hipStream_t st);
+// the long form alone (sp_kl_solve_long_kernel over a.longc): a batch launches it once per active member, on that member's offsets
+void nnlm_tu_sp_kl_long(const SpKlArgs &a, int method, bool f64, hipStream_t st);
