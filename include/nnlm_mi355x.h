@@ -458,6 +458,15 @@ int nnlm_debug_set_xprod_waves(int waves);
  * out[0..6] = wavefronts per block, split-K slabs S, stages per slab, tiles, blocks (tiles x S), 4-row pieces of the factor image a
  * stage loads (all 4 ceil(k / 16); 13 at k = 49 .. 52), LDS bytes of a block; out[7] = 0. */
 int nnlm_xprod_plan(int ldc, int stages, int k, int cus, int force_waves, int out[8]);
+/* Which KL solver (methods 3 and 4) a dense half-step with a contraction of length p takes at rank k in arithmetic mode `precision`, with
+ * mask_words 64-bit mask words per column of the solved factor (0: no mask), when its matrix-sized workspaces fit (the fallbacks on a
+ * failed allocation -- own starting states, streaming -- are run-time answers and not part of the plan).  Pure function, works without a
+ * GPU.  out[0] = kernel: 0 kl_tile_kernel with two row buffers, 1 kl_tile_kernel with one row buffer, 2 kl_reg64_kernel, 3
+ * kl_stream_kernel; out[1] = exact pieces per thread (16-byte pieces of the contraction: 4 floats / 2 doubles x 512 threads); out[2] = the
+ * instantiated piece count that runs (kl_reg64_kernel rounds up to 1, 2, 3, 5, 7, 10, 12, 14, 16, 18, 20); out[3] = columns per block;
+ * out[4] = dynamic LDS bytes of a block; out[5] = wavefronts of a block (of 8) that own a last instantiated piece holding data;
+ * out[6] = out[7] = 0.  Streaming: out[1..3] = out[5] = 0. */
+int nnlm_kl_plan(int p, int k, int precision, int mask_words, int out[8]);
 /* Test hook: the matrix-sized workspaces of the KL solvers (starting states of all columns, transposed copy of A, streaming scratch)
  * "do not fit" when they exceed `bytes` (0 = no limit): the half-step then takes its smaller-footprint path -- the streaming kernel
  * over column chunks -- exactly as it does when hipMalloc itself says no. */
@@ -472,6 +481,8 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * of the launch -- and coordinate registers per lane R of the sweep_ls_kernel<R, L, 2> launch of the last W / H half-step, -1 none
  * yet), "kl_form_w" / "kl_form_h" (KL solver of the last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
  * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
+ * "kl_pieces_w" / "kl_pieces_h" and "kl_cols_w" / "kl_cols_h" (instantiated pieces per thread and columns per block of the kl_tile_kernel
+ * or kl_reg64_kernel launch of the last W / H half-step -- out[2] and out[3] of nnlm_kl_plan --, 0 when it streamed, -1 none yet),
  * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies),
  * "matrix_min_col_observed" / "matrix_min_row_observed" (dense matrix: the fewest observed -- finite -- entries of any column / any row,
  * n / m without missing entries; counted on the device at the first query; -1 on a sparse handle),

@@ -32,7 +32,7 @@ EXPORTS = [
     "nnlm_half_step", "nnlm_iterate", "nnlm_run", "nnlm_take_sweeps", "nnlm_errors", "nnlm_sync", "nnlm_profile_enable",
     "nnlm_profile_get", "nnlm_profile_reset", "nnlm_comm_unique_id", "nnlm_comm_init", "nnlm_comm_info",
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
-    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_xprod_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
+    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_xprod_plan", "nnlm_kl_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_matrix_csc_kl", "nnlm_c_nnmf_csc_kl", "nnlm_c_nnlm_csc_kl",
@@ -167,6 +167,8 @@ def load():
     lib.nnlm_debug_set_xprod_waves.argtypes = [C.c_int]
     lib.nnlm_xprod_plan.restype = C.c_int
     lib.nnlm_xprod_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]
+    lib.nnlm_kl_plan.restype = C.c_int
+    lib.nnlm_kl_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip]
     lib.nnlm_debug_alloc_limit.restype = C.c_int
     lib.nnlm_debug_alloc_limit.argtypes = [C.c_size_t]
     lib.nnlm_release_caches.restype = C.c_int
@@ -953,6 +955,9 @@ class Handle:
         """cus, xprod_waves_w / xprod_waves_h and xprod_splits_w / xprod_splits_h (wavefronts per block and slabs of the last xprod16_tn_kernel
         launch of each side), xprod_splits_err (slabs of the last fused xprod16_err_kernel launch), sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
         lee_lanes_w / lee_lanes_h and lee_regs_w / lee_regs_h (L and R of the last sweep_ls_kernel<R, L, 2> launch, -1 none yet),
+        kl_form_w / kl_form_h (KL solver of the last half-step: 0 tile, 1 tile on its own starting states, 2 reg64, 3 streaming, -1 none yet),
+        kl_pieces_w / kl_pieces_h and kl_cols_w / kl_cols_h (instantiated pieces per thread and columns per block of that launch as in
+        kl_plan(); 0 streaming, -1 none yet),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
         column / a row of a dense matrix)."""
         v = C.c_double(0)
@@ -1011,6 +1016,18 @@ def xprod_plan(ldc, stages, k, cus, force_waves=0):
     out = (C.c_int * 8)()
     _check(load().nnlm_xprod_plan(int(ldc), int(stages), int(k), int(cus), int(force_waves), out))
     return dict(zip(("waves", "splits", "stages_per_split", "tiles", "blocks", "pieces", "lds_bytes"), list(out)[:7]))
+
+
+KL_TILE2, KL_TILE1, KL_REG64, KL_STREAM = 0, 1, 2, 3  # "kernel" of kl_plan()
+
+
+def kl_plan(p, k, precision, mask_words=0):
+    """Which KL solver a dense half-step with a contraction of length p takes when its workspaces fit (pure host function of the C ABI,
+    works without a GPU): kernel (KL_TILE2 / KL_TILE1 / KL_REG64 / KL_STREAM), exact and instantiated pieces per thread, columns per
+    block, dynamic LDS bytes, wavefronts of a block that own a last piece."""
+    out = (C.c_int * 8)()
+    _check(load().nnlm_kl_plan(int(p), int(k), int(precision), int(mask_words), out))
+    return dict(zip(("kernel", "pieces_exact", "pieces", "cols", "lds_bytes", "last_waves"), list(out)[:6]))
 
 
 def debug_alloc_limit(nbytes: int):

@@ -86,6 +86,7 @@ struct nnlm_handle {
     int cus = 256;              // compute units of the device (sweep launch policy: one wavefront of the SCD sweep per SIMD, 4 SIMDs per CU)
     int sweep_wgs = 0;          // workgroups of the last sweep_scd_q(w)_kernel launch = Gram partial-sum slabs it left behind
     int cur_which = 1;          // the half-step in progress (0: W, 1: H)
+    int kl_pieces[2] = {-1, -1}, kl_cols[2] = {-1, -1}; // per half-step: instantiated pieces per thread and columns per block of its last kl_tile_kernel / kl_reg64_kernel launch (0 streaming)
     int kl_form[2] = {-1, -1}; // per half-step: its last KL solver launch (0 tile kernel on the GEMM's states, 1 tile kernel on its own states, 2 strict register kernel, 3 streaming)
     int sweep_form[2] = {-1, -1}, sweep_groups[2] = {0, 0}; // per half-step (0: W, 1: H): form of its last SCD sweep launch (0 plain, 1 persistent) and
                                                              // column groups per workgroup (nnlm_get_info)
@@ -2449,8 +2450,9 @@ static int launch_sweep(nnlm_handle *h, int method, const SweepArgs &a)
 // strict fp64 mode: kl_reg64_kernel (k_kl.h).  EPT2 = double2 chunks of the contraction per thread (rounded up to an
 // instantiated value), C = columns per workgroup (C * EPT2 <= 20 chunks = 160 state registers)
 template <int EPT2, int C>
-static void launch_kl64_m(int method, const Kl64Args &ka, hipStream_t s)
+static void launch_kl64_m(int method, const Kl64Args &ka, hipStream_t s, int ran[2])
 {
+    ran[0] = EPT2, ran[1] = C; // (the instantiation itself, not the ladder's word for it)
     const int nb = (ka.ncols - ka.colbase + C - 1) / C;
     if (nb <= 0) return;
     const size_t lds = kl64_lds_bytes(EPT2, C, ka.k);
@@ -2464,27 +2466,38 @@ static void launch_kl64_m(int method, const Kl64Args &ka, hipStream_t s)
 }
 static int kl64_ept2(int p) { return ((p + 1) / 2 + KL64_THREADS - 1) / KL64_THREADS; } // > 20: too long for the register-resident kernel
 static bool kl64_fits(int p, int k) { return kl64_ept2(p) <= 20 && kl64_lds_bytes(kl64_ept2(p) <= 5 ? 5 : (kl64_ept2(p) <= 10 ? 10 : 20), 4, k) <= (size_t)160 * 1024; }
-static void launch_kl64(int method, const Kl64Args &ka, hipStream_t s)
+// the rounding ladder: the instantiated piece count that takes e exact pieces (e <= 20), and its columns per block
+static int kl64_inst(int e)
 {
-    const int e = kl64_ept2(ka.p);
-    if (e <= 1) launch_kl64_m<1, 4>(method, ka, s);
-    else if (e <= 2) launch_kl64_m<2, 4>(method, ka, s);
-    else if (e <= 3) launch_kl64_m<3, 4>(method, ka, s);
-    else if (e <= 5) launch_kl64_m<5, 4>(method, ka, s);
-    else if (e <= 7) launch_kl64_m<7, 2>(method, ka, s);
-    else if (e <= 10) launch_kl64_m<10, 2>(method, ka, s);
-    else if (e <= 12) launch_kl64_m<12, 1>(method, ka, s);
-    else if (e <= 14) launch_kl64_m<14, 1>(method, ka, s);
-    else if (e <= 16) launch_kl64_m<16, 1>(method, ka, s);
-    else if (e <= 18) launch_kl64_m<18, 1>(method, ka, s);
-    else launch_kl64_m<20, 1>(method, ka, s);
+    static const int rungs[] = {1, 2, 3, 5, 7, 10, 12, 14, 16, 18, 20};
+    for (int r : rungs)
+        if (e <= r) return r;
+    return 20;
+}
+static int kl64_cols(int inst) { return inst <= 5 ? 4 : (inst <= 10 ? 2 : 1); }
+static void launch_kl64(int method, const Kl64Args &ka, hipStream_t s, int ran[2])
+{
+    switch (kl64_inst(kl64_ept2(ka.p))) {
+    case 1: launch_kl64_m<1, 4>(method, ka, s, ran); break;
+    case 2: launch_kl64_m<2, 4>(method, ka, s, ran); break;
+    case 3: launch_kl64_m<3, 4>(method, ka, s, ran); break;
+    case 5: launch_kl64_m<5, 4>(method, ka, s, ran); break;
+    case 7: launch_kl64_m<7, 2>(method, ka, s, ran); break;
+    case 10: launch_kl64_m<10, 2>(method, ka, s, ran); break;
+    case 12: launch_kl64_m<12, 1>(method, ka, s, ran); break;
+    case 14: launch_kl64_m<14, 1>(method, ka, s, ran); break;
+    case 16: launch_kl64_m<16, 1>(method, ka, s, ran); break;
+    case 18: launch_kl64_m<18, 1>(method, ka, s, ran); break;
+    default: launch_kl64_m<20, 1>(method, ka, s, ran); break;
+    }
 }
 
 // F32 mode: kl_tile_kernel (k_kl.h).  EPT4 = float4 chunks of the contraction per thread, C = columns per workgroup
 // (C * EPT4 * 8 state registers per thread).
 template <int EPT4, int C, bool ONEBUF = false>
-static void launch_kl_tile_m(int method, const KlTileArgs &ta, int nb, size_t lds, hipStream_t s)
+static void launch_kl_tile_m(int method, const KlTileArgs &ta, int nb, size_t lds, hipStream_t s, int ran[2])
 {
+    ran[0] = EPT4, ran[1] = C; // (the instantiation itself)
     if (method == 3) {
         set_dyn_lds((const void *)kl_tile_kernel<EPT4, C, 3, ONEBUF>, (int)lds, "kl_tile_kernel");
         kl_tile_kernel<EPT4, C, 3, ONEBUF><<<nb, KLT_THREADS, lds, s>>>(ta);
@@ -2507,33 +2520,33 @@ static bool kl_tile_fits(int p, int k, int mw_masked)
     return e > 0 && kl_tile_lds_bytes(p, k, kl_tile_cols(e), mw_masked, kl_tile_nbuf(e)) <= (size_t)160 * 1024 &&
            2 * round_up_i(k, 2) * ERRF_TILE * 4 <= 160 * 1024;
 }
-static void launch_kl_tile(int method, const KlTileArgs &ta, hipStream_t s)
+static void launch_kl_tile(int method, const KlTileArgs &ta, hipStream_t s, int ran[2])
 {
     const int e = kl_tile_ept4(ta.p), C = kl_tile_cols(e);
     const int nb = (ta.ncols - ta.colbase + C - 1) / C;
     if (nb <= 0) return;
     const size_t lds = kl_tile_lds_bytes(ta.p, ta.k, C, ta.mask ? ta.mw : 0, kl_tile_nbuf(e));
     switch (e) {
-    case 11: launch_kl_tile_m<11, 1, true>(method, ta, nb, lds, s); break;
-    case 12: launch_kl_tile_m<12, 1, true>(method, ta, nb, lds, s); break;
-    case 13: launch_kl_tile_m<13, 1, true>(method, ta, nb, lds, s); break;
-    case 14: launch_kl_tile_m<14, 1, true>(method, ta, nb, lds, s); break;
-    case 15: launch_kl_tile_m<15, 1, true>(method, ta, nb, lds, s); break;
-    case 16: launch_kl_tile_m<16, 1, true>(method, ta, nb, lds, s); break;
-    case 17: launch_kl_tile_m<17, 1, true>(method, ta, nb, lds, s); break;
-    case 18: launch_kl_tile_m<18, 1, true>(method, ta, nb, lds, s); break;
-    case 19: launch_kl_tile_m<19, 1, true>(method, ta, nb, lds, s); break;
-    case 20: launch_kl_tile_m<20, 1, true>(method, ta, nb, lds, s); break;
-    case 1: launch_kl_tile_m<1, 8>(method, ta, nb, lds, s); break;
-    case 2: launch_kl_tile_m<2, 8>(method, ta, nb, lds, s); break;
-    case 3: launch_kl_tile_m<3, 4>(method, ta, nb, lds, s); break;
-    case 4: launch_kl_tile_m<4, 4>(method, ta, nb, lds, s); break;
-    case 5: launch_kl_tile_m<5, 4>(method, ta, nb, lds, s); break;
-    case 6: launch_kl_tile_m<6, 2>(method, ta, nb, lds, s); break;
-    case 7: launch_kl_tile_m<7, 2>(method, ta, nb, lds, s); break;
-    case 8: launch_kl_tile_m<8, 2>(method, ta, nb, lds, s); break;
-    case 9: launch_kl_tile_m<9, 2>(method, ta, nb, lds, s); break;
-    default: launch_kl_tile_m<10, 2>(method, ta, nb, lds, s); break;
+    case 11: launch_kl_tile_m<11, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 12: launch_kl_tile_m<12, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 13: launch_kl_tile_m<13, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 14: launch_kl_tile_m<14, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 15: launch_kl_tile_m<15, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 16: launch_kl_tile_m<16, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 17: launch_kl_tile_m<17, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 18: launch_kl_tile_m<18, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 19: launch_kl_tile_m<19, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 20: launch_kl_tile_m<20, 1, true>(method, ta, nb, lds, s, ran); break;
+    case 1: launch_kl_tile_m<1, 8>(method, ta, nb, lds, s, ran); break;
+    case 2: launch_kl_tile_m<2, 8>(method, ta, nb, lds, s, ran); break;
+    case 3: launch_kl_tile_m<3, 4>(method, ta, nb, lds, s, ran); break;
+    case 4: launch_kl_tile_m<4, 4>(method, ta, nb, lds, s, ran); break;
+    case 5: launch_kl_tile_m<5, 4>(method, ta, nb, lds, s, ran); break;
+    case 6: launch_kl_tile_m<6, 2>(method, ta, nb, lds, s, ran); break;
+    case 7: launch_kl_tile_m<7, 2>(method, ta, nb, lds, s, ran); break;
+    case 8: launch_kl_tile_m<8, 2>(method, ta, nb, lds, s, ran); break;
+    case 9: launch_kl_tile_m<9, 2>(method, ta, nb, lds, s, ran); break;
+    default: launch_kl_tile_m<10, 2>(method, ta, nb, lds, s, ran); break;
     }
 }
 
@@ -2908,8 +2921,10 @@ static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsi
         if (rc != NNLM_OK) return rc;
         kl_common_args(ta, h, a, sumw_cols);
         ta.mw = h->MW;
-        launch_kl_tile(method, ta, h->stream);
+        int ran[2] = {0, 0};
+        launch_kl_tile(method, ta, h->stream, ran);
         h->kl_form[s.which] = kl_own_init ? 1 : 0;
+        h->kl_pieces[s.which] = ran[0], h->kl_cols[s.which] = ran[1];
     } else if (reg64_path) {
         // ---- strict fp64 mode: register-resident fp64 state, the row of the fixed factor parked in LDS between the passes ----
         // (starting states: What64[j][i], the layout of A; W half-step, roles swapped: What64^T [row of A][column of A], next to AT)
@@ -2929,8 +2944,10 @@ static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsi
         int rc = kl_row_sums(h, s, a, &sumw_cols);
         if (rc != NNLM_OK) return rc;
         kl_common_args(ka, h, a, sumw_cols);
-        launch_kl64(method, ka, h->stream);
+        int ran[2] = {0, 0};
+        launch_kl64(method, ka, h->stream, ran);
         h->kl_form[s.which] = 2;
+        h->kl_pieces[s.which] = ran[0], h->kl_cols[s.which] = ran[1];
     } else {
         // ---- no size limits: state vectors and data columns streamed from a scratch buffer (kl_stream_kernel), `chunk` columns at a
         // time: the whole range when the scratch for it can be had (two vectors per column), otherwise as many as fit
@@ -2956,6 +2973,7 @@ static int half_step_kl(nnlm_handle *h, const Side &s, const double reg[3], unsi
             }
         }
         h->kl_form[s.which] = 3;
+        h->kl_pieces[s.which] = h->kl_cols[s.which] = 0;
         const int col_end = a.ncols;
         for (int c0 = a.col0; c0 < col_end; c0 += chunk) {
             KlArgs ac = a;
@@ -3925,6 +3943,10 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "lee_regs_h") == 0) *value = h->lee_regs[1];
     else if (strcmp(key, "kl_form_w") == 0) *value = h->kl_form[0];
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
+    else if (strcmp(key, "kl_pieces_w") == 0) *value = h->kl_pieces[0]; // (instantiated pieces per thread / columns per block of the last
+    else if (strcmp(key, "kl_pieces_h") == 0) *value = h->kl_pieces[1]; //  kl_tile_kernel or kl_reg64_kernel launch; 0 streaming, -1 none yet)
+    else if (strcmp(key, "kl_cols_w") == 0) *value = h->kl_cols[0];
+    else if (strcmp(key, "kl_cols_h") == 0) *value = h->kl_cols[1];
     else if (strcmp(key, "matrix_nnz") == 0) *value = h->sparse ? (double)h->nnz : -1.0;
     else if (strcmp(key, "matrix_holdout") == 0) *value = h->holdout ? (double)h->ho_nnz : -1.0;
     else if (strcmp(key, "matrix_bytes") == 0) *value = matrix_bytes(h);
@@ -3993,6 +4015,33 @@ extern "C" int nnlm_xprod_plan(int ldc, int stages, int k, int cus, int force_wa
         return fail(nullptr, NNLM_ERR_ARG, "nnlm_xprod_plan: bad arguments");
     const XPlan x = xprod_plan(ldc, stages, k, cus, force_waves, true);
     out[0] = x.nwv, out[1] = x.S, out[2] = x.sps, out[3] = x.tiles_x, out[4] = x.tiles_x * x.S, out[5] = x.yp, out[6] = x.lds, out[7] = 0;
+    return NNLM_OK;
+}
+
+// Which KL solver a half-step with a contraction of length p takes at rank k (mask_words: 64-bit mask words per column of the solved
+// factor, 0 without a mask) when its matrix-sized workspaces fit -- the decisions of half_step_kl(), launch_kl_tile() and launch_kl64()
+// from their own helpers.  Pure function; out[8] = kernel (0 kl_tile_kernel with two row buffers, 1 with one, 2 kl_reg64_kernel,
+// 3 kl_stream_kernel), exact pieces per thread, instantiated pieces (reg64 rounds up), columns per block, dynamic LDS bytes, wavefronts of
+// a block that own a last (instantiated) piece, 0, 0.
+extern "C" int nnlm_kl_plan(int p, int k, int precision, int mask_words, int *out)
+{
+    if (p < 1 || k < 1 || (precision != NNLM_PREC_F32 && precision != NNLM_PREC_F64) || mask_words < 0 || !out)
+        return fail(nullptr, NNLM_ERR_ARG, "nnlm_kl_plan: bad arguments");
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (precision == NNLM_PREC_F32 && kl_tile_fits(p, k, mask_words)) {
+        const int e = kl_tile_ept4(p), C = kl_tile_cols(e), nbuf = kl_tile_nbuf(e), P4 = kl_tile_p4(p);
+        out[0] = nbuf == 2 ? 0 : 1, out[1] = out[2] = e, out[3] = C;
+        out[4] = (int)kl_tile_lds_bytes(p, k, C, mask_words, nbuf);
+        for (int w = 0; w < KLT_THREADS / 64; w++) out[5] += (e - 1) * KLT_THREADS + 64 * w < P4; // `last` of kl_tile_kernel
+    } else if (precision == NNLM_PREC_F64 && k <= NNLM_KQ_MAX && kl64_fits(p, k)) {
+        const int e = kl64_ept2(p), inst = kl64_inst(e), C = kl64_cols(inst), P2 = (p + 1) / 2;
+        out[0] = 2, out[1] = e, out[2] = inst, out[3] = C;
+        out[4] = (int)kl64_lds_bytes(inst, C, k);
+        for (int w = 0; w < KL64_THREADS / 64; w++) out[5] += (inst - 1) * KL64_THREADS + 64 * w < P2; // chunks that hold data
+    } else {
+        out[0] = 3;
+        out[4] = (k + 24) * 8; // (launch_kl_stream)
+    }
     return NNLM_OK;
 }
 

@@ -600,7 +600,8 @@ def test_nnlm_with_more_than_64_predictors(monkeypatch):
 def test_kl_contraction_longer_than_32768(pname, prec, tol, method, n):
     """nnmf(loss = 'mkl') on an n x 9 matrix: the H half-step contracts over n rows (the reference streams any length,
     src/base_algorithms.cpp:71-151), the W half-step solves n columns.  F32 mode: 23000 and 40000 take the one-row-buffer form of
-    kl_tile_kernel (12 / 20 pieces per thread), 41500 kl_stream_kernel; strict mode: kl_stream_kernel beyond 20480."""
+    kl_tile_kernel (12 / 20 pieces per thread), 41500 kl_stream_kernel; strict mode: kl_stream_kernel beyond 20480.  Every other piece count of
+    both register-resident kernels, at the ends of its last piece: tests/test_gpu_kl_pieces.py."""
     rng = np.random.default_rng(method)
     m, k = 9, 3
     A = rng.random((n, m))
