@@ -2387,7 +2387,8 @@ static void launch_sweep_q(nnlm_handle *h, const SweepArgs &a)
     // form costs ceil(groups / SIMDs) rounds of S sweeps.  The persistent form gives every CU G column groups, shared by its four
     // wavefronts by the wrap-around rule -- ceil(G S / 4) sweeps per round of (one workgroup per CU) -- and is taken, with the G that
     // costs least, whenever that is less: the benchmark's W half-step (1250 groups on 1024 SIMDs) G = 5, 1.25 S instead of 2 S;
-    // 2500 groups G = 10, 2.5 S instead of 3 S.  (Costs in quarters of S.)
+    // 2500 groups G = 5 in two rounds of workgroups, 2.5 S instead of 3 S (G = 10 in one round costs the same: a tie keeps the smaller
+    // G, so 8 and 10 are never taken).  (Costs in quarters of S.)
     const int ngroups = (a.ncols - a.col0 + 15) / 16, simds = 4 * h->cus;
     int G = 0;
     if (ngroups > simds && a.max_iter >= 4) {

@@ -493,7 +493,11 @@ def test_virtual_ranks_run_whole_sharded_half_steps(monkeypatch, pname, prec, to
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(300, 101, 9), (90, 130, 13), (257, 1000, 17), (70, 50, 21), (111, 77, 26), (120, 49, 32), (64, 97, 33),
                                    (75, 200, 38), (130, 60, 44), (60, 129, 48), (400, 530, 50), (88, 65, 53), (140, 64, 58),
-                                   (90, 97, 64)])  # k = 9 .. 64: every instantiation sweep_scd_q_kernel<NT, NB> has (NB = ceil(k / 4) = 3 .. 16)
+                                   (90, 97, 64)])
+# k = 9 .. 64 in the fp32-operand mode, 49 .. 1000 columns on the real device: since the end of round 6 that is sweep_row_kernel (k_sweep_r.h,
+# four-wavefront workgroups) for k <= 50 and sweep_scd_f_kernel<4, 14 | 15 | 16, true, 4> (k_sweep_f.h) for k = 53, 58, 64.  (Written for the
+# non-strict sweep_scd_q_kernel<NT, NB>, NB = 3 .. 16, which no longer exists; every instantiation of today's four sweep kernels is run by
+# tests/test_gpu_scd_forms.py.)
 @pytest.mark.parametrize("inner,itol", [(50, 1e-3), (7, 1e-9), (200, 1e-6), (0, 1e-9), (1, -1.0)])
 def test_fast_sweep_with_masks_and_early_finishers(shape, inner, itol):
     n, m, k = shape
