@@ -308,7 +308,8 @@ __global__ __launch_bounds__(256) void a16_transpose_kernel(const float *__restr
 //   * a(i, j) is rebuilt from the hi/lo halves already in the A image (hi + lo * 2^-11: 22 bits), moved into the accumulator
 //     layout of W H by a one-hot MFMA (exact: one product with 1.0 and one with 2^-11 per element);
 //   * the two sums: fp32 over the 16 elements of a lane per stage, fp64 across stages, one pair per block in `partial`.
-// No missing values, no masks on A (host falls back to errors_f32_kernel).
+// Missing entries of A: the HAS_MISS instantiations (below).  The first and the last evaluation of a run, errors() and ranks beyond 64
+// have no W half-step to ride in and take errors_f32_kernel / errors_kernel<float>.
 //
 // Wavefront-specialised (round 5): a wavefront owns 32 rows of the block and ONE of the two jobs.
 //   * wavefronts 0..3 ("E", rows 32 rg ..): W H and the error arithmetic.  W fragments of two M-tiles stay in registers, every H
