@@ -298,6 +298,39 @@ int nnlm_set_factors_device(nnlm_handle *h, unsigned k, const nnlm_dev_matrix *W
  * are written, the gaps of a strided buffer stay as they are; a NULL descriptor = not wanted. */
 int nnlm_get_factors_device(nnlm_handle *h, const nnlm_dev_matrix *W, const nnlm_dev_matrix *H, void *stream);
 
+/* A SPARSE matrix that already lives in device memory, compressed by columns (CSC) or by rows (CSR): ptr has m + 1 (CSC) or n + 1 (CSR)
+ * entries, idx and val have nnz entries each, all three contiguous device (or managed) arrays of the handle's device.  ptr_dtype and
+ * idx_dtype are NNLM_IT_I32 or NNLM_IT_I64, independently; val_dtype is one of the four NNLM_DT_*.  `stream` as for nnlm_set_matrix_device.
+ * The call returns after its last read of the caller's arrays; the handle owns copies.
+ *
+ * The handle afterwards is the one the matching host entry leaves for the fp64 widening of the same values -- the six resident arrays
+ * (both sides, indices ascending in every line), nnz, n_non_missing, any_missing, the byte count, the sizing of the partial sums, the
+ * long-column tables (missing door) and long-line lists (KL doors), the flags -- with kl_const differing by summation order only.
+ * `door` chooses that entry: 0 nnlm_set_matrix_csc, NNLM_SP_BATCH nnlm_set_matrix_csc_batch, NNLM_SP_KL nnlm_set_matrix_csc_kl,
+ * NNLM_SP_KL | NNLM_SP_BATCH nnlm_set_matrix_csc_kl_batch, NNLM_SP_ABSENT_MISSING nnlm_set_matrix_csc_missing, NNLM_SP_ABSENT_MISSING |
+ * NNLM_SP_BATCH nnlm_set_matrix_csc_missing_batch without a hold-out set; NNLM_SP_ABSENT_MISSING | NNLM_SP_KL is NNLM_ERR_ARG.
+ *
+ * Everything is done by kernels (k_sparse_ingest.h): the given side is checked and copied with type conversion,
+ * the other side is built by a stable radix sort.  Nothing of size nnz crosses to the host; the two int64 pointer arrays come back,
+ * (n + m + 2) * 8 bytes.  Refusals follow the host entries' contract, same codes, first offender named (for CSR the words "row" and
+ * "column" trade places): ptr[0] != 0, a decreasing pointer, ptr[last] != nnz, nnz > n m, an index out of range, indices of a line not
+ * strictly increasing, a non-finite value, a negative value on a KL door, the two range rules of NNLM_PREC_F32 (NNLM_ERR_UNSUPPORTED), a
+ * sharded handle (NNLM_ERR_UNSUPPORTED), a pointer that is not device memory of the handle's device, a bad dtype, layout or door code.
+ * No value read from the caller's arrays is used as an address before it has been checked: a malformed input ends in a refusal, and a
+ * refused call leaves the handle's previous matrix and factors as they were.  Temporaries (at most 24 bytes per stored entry beside the
+ * new resident arrays, see DESIGN) are freed before the call returns; a failed allocation is NNLM_ERR_HIP with the handle unchanged.
+ * nnlm_get_info "matrix_min_col_observed" / "matrix_min_row_observed" answer for a handle loaded here: the fewest stored entries of a
+ * column / of a row on the missing doors, n / m on the others. */
+enum { NNLM_IT_I32 = 0, NNLM_IT_I64 = 1 };
+enum { NNLM_SP_CSC = 0, NNLM_SP_CSR = 1 };
+enum { NNLM_SP_ABSENT_MISSING = 1, NNLM_SP_KL = 2, NNLM_SP_BATCH = 4 }; /* `door` bits */
+typedef struct { const void *ptr, *idx, *val; int ptr_dtype, idx_dtype, val_dtype, layout; long long nnz; } nnlm_dev_sparse;
+int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_sparse *A, int n, int m, int door, void *stream);
+/* TEST HOOK: the resident arrays of one side of the handle's sparse matrix (side 0: by columns, ptr_out [m + 1], idx_out = rows; side 1:
+ * by rows, ptr_out [n + 1], idx_out = columns; idx_out and val_out [nnz]), values widened to fp64.  A NULL output = not wanted.
+ * NNLM_ERR_ARG when the handle holds no sparse matrix. */
+int nnlm_debug_sparse_resident(nnlm_handle *h, int side, long long *ptr_out, int *idx_out, double *val_out);
+
 /*
  * One half-step = update()/update_with_missing() (reference src/update_with_missing.cpp:3-55, :58-139).
  * which = 0 updates W (solves A^T ~ H^T W^T with `reg` = alpha), 1 updates H (`reg` = beta).
@@ -485,7 +518,10 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * or kl_reg64_kernel launch of the last W / H half-step -- out[2] and out[3] of nnlm_kl_plan --, 0 when it streamed, -1 none yet),
  * "matrix_nnz" (non-zeros of a sparse matrix, -1 for a dense one), "matrix_bytes" (device bytes the resident matrix occupies),
  * "matrix_min_col_observed" / "matrix_min_row_observed" (dense matrix: the fewest observed -- finite -- entries of any column / any row,
- * n / m without missing entries; counted on the device at the first query; -1 on a sparse handle),
+ * n / m without missing entries; counted on the device at the first query; -1 on a sparse handle loaded from host arrays; on one loaded
+ * by nnlm_set_matrix_sparse_device the fewest stored entries of a column / row when absent entries are missing, else n / m),
+ * "sp_ingest_check_share" / "sp_ingest_sort_tile" (stored entries per workgroup of the entry check and of a radix pass of
+ * nnlm_set_matrix_sparse_device: constants of the build),
  * "matrix_absent_missing" (1 after nnlm_set_matrix_csc_missing, else 0), "sp_gram_chunks" / "sp_gram_bytes" (column chunks of the last
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),

@@ -43,6 +43,7 @@ EXPORTS = [
     "nnlm_set_matrix_csc_batch", "nnlm_c_nnmf_csc_batch",
     "nnlm_set_matrix_csc_kl_batch", "nnlm_c_nnmf_csc_kl_batch",
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
+    "nnlm_set_matrix_sparse_device", "nnlm_debug_sparse_resident",
 ]
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
 BY = {"column": 0, "row": 1}
@@ -59,7 +60,19 @@ class DevMatrix(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("dtype", C.c_int), ("row_stride", C.c_longlong), ("col_stride", C.c_longlong)]
 
 
+class DevSparse(C.Structure):
+    """nnlm_dev_sparse: a CSC / CSR matrix in device memory (three contiguous 1-D arrays)."""
+    _fields_ = [("ptr", C.c_void_p), ("idx", C.c_void_p), ("val", C.c_void_p), ("ptr_dtype", C.c_int), ("idx_dtype", C.c_int),
+                ("val_dtype", C.c_int), ("layout", C.c_int), ("nnz", C.c_longlong)]
+
+
 DT_F64, DT_F32, DT_F16, DT_BF16 = 0, 1, 2, 3
+IT_I32, IT_I64 = 0, 1
+SP_CSC, SP_CSR = 0, 1
+SP_ABSENT_MISSING, SP_KL, SP_BATCH = 1, 2, 4  # `door` bits of nnlm_set_matrix_sparse_device
+SP_LAYOUTS = {"csc": SP_CSC, "csr": SP_CSR}
+_IT_NAMES = {"int32": IT_I32, "int64": IT_I64, "int": IT_I32, "long": IT_I64}
+_IT_TYPESTR = {"i4": IT_I32, "i8": IT_I64}
 _DT_SIZE = {DT_F64: 8, DT_F32: 4, DT_F16: 2, DT_BF16: 2}
 _DT_NAMES = {"float64": DT_F64, "float32": DT_F32, "float16": DT_F16, "bfloat16": DT_BF16, "double": DT_F64, "float": DT_F32, "half": DT_F16}
 _DT_TYPESTR = {"f8": DT_F64, "f4": DT_F32, "f2": DT_F16}
@@ -212,6 +225,10 @@ def load():
     lib.nnlm_set_factors_device.argtypes = [vp, C.c_uint, dmp, dmp, ip, ip, vp]
     lib.nnlm_get_factors_device.restype = C.c_int
     lib.nnlm_get_factors_device.argtypes = [vp, dmp, dmp, vp]
+    lib.nnlm_set_matrix_sparse_device.restype = C.c_int
+    lib.nnlm_set_matrix_sparse_device.argtypes = [vp, C.POINTER(DevSparse), C.c_int, C.c_int, C.c_int, vp]
+    lib.nnlm_debug_sparse_resident.restype = C.c_int
+    lib.nnlm_debug_sparse_resident.argtypes = [vp, C.c_int, lp, ip, dp]
     lib.nnlm_predict_entries.restype = C.c_int
     lib.nnlm_predict_entries.argtypes = [vp, C.c_longlong, ip, ip, dp]
     lib.nnlm_top_n.restype = C.c_int
@@ -369,6 +386,106 @@ def dev_matrix(x, device=None):
         raise _dev_restrict("strides %s (in elements): zero (broadcast / expand) and negative strides are not accepted; make the array "
                             "contiguous first" % (strides,))
     return DevMatrix(ptr, dt, strides[0], strides[1]), x, shape, stream
+
+
+def _dev_vector(x, name, kinds, device):
+    """(pointer, dtype code, length, stream or None) of a contiguous 1-D array in device memory; kinds = "int" or "float"."""
+    names, typestrs, wanted = ((_IT_NAMES, _IT_TYPESTR, "int32 or int64") if kinds == "int"
+                               else (_DT_NAMES, _DT_TYPESTR, "float64, float32, float16 or bfloat16"))
+    stream = None
+    if _is_tensor_like(x):
+        dev = x.device
+        if getattr(dev, "type", "cpu") == "cpu":
+            raise _dev_restrict("%s lives in host memory (device %s); pass the matrix as a host sparse object, or move it to the GPU" % (name, dev))
+        idx = getattr(dev, "index", None)
+        if device is not None and idx is not None and int(idx) != int(device):
+            raise _dev_restrict("%s lives on device %d, the handle on device %d" % (name, int(idx), int(device)))
+        shape = tuple(int(v) for v in x.shape)
+        dn = str(x.dtype).split(".")[-1]
+        if dn not in names:
+            raise _dev_restrict("%s has dtype %s; it must be %s" % (name, x.dtype, wanted))
+        dt = names[dn]
+        if len(shape) != 1:
+            raise _dev_restrict("%s is a %d-D array; it must be 1-D" % (name, len(shape)))
+        stride = int(x.stride()[0])
+        ptr = int(x.data_ptr())
+    else:
+        try:
+            cai = x.__cuda_array_interface__
+        except Exception:
+            cai = None
+        if not isinstance(cai, dict):
+            raise _dev_restrict("%s (%s) is neither a tensor (data_ptr / stride / shape / dtype / device) nor a __cuda_array_interface__ "
+                                "producer" % (name, type(x).__name__))
+        if int(cai.get("version", 0)) < 2:
+            raise _dev_restrict("__cuda_array_interface__ version %s; versions 2 and 3 are supported" % cai.get("version"))
+        shape = tuple(int(v) for v in cai["shape"])
+        ts = str(cai["typestr"])
+        if ts[:1] == ">" or ts[1:] not in typestrs:
+            raise _dev_restrict("%s has typestr %r; it must be %s" % (name, ts, wanted))
+        dt = typestrs[ts[1:]]
+        if len(shape) != 1:
+            raise _dev_restrict("%s is a %d-D array; it must be 1-D" % (name, len(shape)))
+        es = int(ts[2:])
+        stride = 1 if cai.get("strides") is None else int(cai["strides"][0]) // es if int(cai["strides"][0]) % es == 0 else 0
+        ptr = int(cai["data"][0])
+        idx = getattr(getattr(x, "device", None), "id", None)
+        if device is not None and isinstance(idx, int) and idx != int(device):
+            raise _dev_restrict("%s lives on device %d, the handle on device %d" % (name, idx, int(device)))
+        st = cai.get("stream") if int(cai.get("version", 0)) >= 3 else None
+        if st is not None and int(st) != 1:
+            stream = int(st)
+    if shape[0] > 1 and stride != 1:
+        raise _dev_restrict("%s has stride %d (in elements); it must be contiguous" % (name, stride))
+    return ptr, dt, shape[0], stream
+
+
+def dev_sparse(ptr, idx, val, shape, layout, device=None):
+    """(DevSparse, keep-alive, (n, m), stream or None) of a CSC / CSR matrix whose three arrays live in device memory: ptr (m + 1 entries
+    for "csc", n + 1 for "csr") and idx (nnz) int32 or int64, val (nnz) any of the four floating types; tensor-like objects or
+    __cuda_array_interface__ producers, as dev_matrix takes them.  ValueError, before any device call, for an array that is not 1-D or
+    not contiguous, a wrong length, another dtype, a host tensor, a tensor of another device."""
+    if layout not in SP_LAYOUTS:
+        raise ValueError(f"layout must be 'csc' or 'csr' (got {layout!r})")
+    n, m = (int(v) for v in shape)
+    if n < 1 or m < 1:
+        raise _dev_restrict("an empty %d x %d matrix" % (n, m))
+    lines = m if layout == "csc" else n
+    pp, pt, pl, s0 = _dev_vector(ptr, "ptr", "int", device)
+    ip_, it, il, s1 = _dev_vector(idx, "idx", "int", device)
+    vp_, vt, vl, s2 = _dev_vector(val, "val", "float", device)
+    if pl != lines + 1:
+        raise _dev_restrict("ptr has %d entries; a %s matrix of shape (%d, %d) needs %d" % (pl, layout, n, m, lines + 1))
+    if il != vl:
+        raise _dev_restrict("idx has %d entries, val has %d" % (il, vl))
+    stream = next((s for s in (s0, s1, s2) if s is not None), None)
+    return DevSparse(pp, ip_ or None, vp_ or None, pt, it, vt, SP_LAYOUTS[layout], il), (ptr, idx, val), (n, m), stream
+
+
+def sparse_tensor_parts(A):
+    """(ptr, idx, val, shape, layout) of a compressed sparse tensor in device memory -- an object whose `layout` prints as
+    torch.sparse_csc or torch.sparse_csr and whose device is not the CPU --, None for anything else; a device tensor of another sparse
+    layout (COO, BSR, BSC) is a ValueError.  No tensor library is imported."""
+    lay = getattr(A, "layout", None)
+    if lay is None or isinstance(A, (np.ndarray, np.generic)) or not hasattr(A, "device"):
+        return None
+    name = str(lay)
+    if not name.startswith("torch.sparse_"):
+        return None
+    if getattr(A.device, "type", "cpu") == "cpu":
+        return None
+    if name == "torch.sparse_csc":
+        return A.ccol_indices(), A.row_indices(), A.values(), tuple(int(v) for v in A.shape), "csc"
+    if name == "torch.sparse_csr":
+        return A.crow_indices(), A.col_indices(), A.values(), tuple(int(v) for v in A.shape), "csr"
+    raise ValueError(f"a device tensor of layout {name} is not accepted: convert it with A.to_sparse_csc() (or to_sparse_csr()) first")
+
+
+def is_host_sparse_tensor(A):
+    """True for a tensor of a torch sparse layout that lives in host memory (no entry takes one: scipy.sparse is the host form)."""
+    lay = getattr(A, "layout", None)
+    return (lay is not None and str(lay).startswith("torch.sparse_") and hasattr(A, "device")
+            and getattr(A.device, "type", "cpu") == "cpu")
 
 
 def _tensor_module(x):
@@ -790,6 +907,30 @@ class Handle:
         self.n, self.m = n, m
         del keep
 
+    def set_matrix_sparse_device(self, ptr, idx, val, shape, layout="csc", absent="zero", kl=False, batch=False, stream=None):
+        """A sparse matrix of shape (n, m) whose CSC / CSR arrays live in device memory (see dev_sparse): validated, transposed and
+        converted by kernels, nothing of size nnz crosses to the host.  absent = "zero" | "missing", kl and batch choose the host entry
+        whose handle this leaves (set_matrix_csc, _missing, _kl, each with or without _batch).  stream: as for set_matrix_device."""
+        if absent not in ("zero", "missing"):
+            raise ValueError(f"absent must be 'zero' or 'missing' (got {absent!r})")
+        d, keep, (n, m), st = dev_sparse(ptr, idx, val, shape, layout, self.device)
+        st = _stream_of(val if _is_tensor_like(val) else None, stream) if (stream is not None or st is None) else st
+        door = (SP_ABSENT_MISSING if absent == "missing" else 0) | (SP_KL if kl else 0) | (SP_BATCH if batch else 0)
+        self._ck(self._lib.nnlm_set_matrix_sparse_device(self._h, C.byref(d), n, m, door, C.c_void_p(st)))
+        self.n, self.m = n, m
+        del keep
+
+    def debug_sparse_resident(self, side):
+        """(ptr int64, idx int32, val fp64) of the resident sparse matrix: side 0 by columns (idx = rows), side 1 by rows."""
+        side = int(side)
+        nnz = int(self.get_info("matrix_nnz"))
+        if nnz < 0:
+            raise NnlmError(ERR_ARG, "debug_sparse_resident: the handle holds no sparse matrix")
+        ptr = np.zeros((self.m if side == 0 else self.n) + 1, dtype=np.int64)
+        idx, val = np.zeros(nnz, dtype=np.int32), np.zeros(nnz, dtype=np.float64)
+        self._ck(self._lib.nnlm_debug_sparse_resident(self._h, side, _lp(ptr), _ip(idx), _dp(val)))
+        return ptr, idx, val
+
     def set_factors_device(self, k, W=None, H=None, Wm=None, Hm=None, stream=None):
         """set_factors with W (n x k) and H (k x m) in device memory; None = zeros; the masks are host arrays."""
         k = int(k)
@@ -958,6 +1099,8 @@ class Handle:
         kl_form_w / kl_form_h (KL solver of the last half-step: 0 tile, 1 tile on its own starting states, 2 reg64, 3 streaming, -1 none yet),
         kl_pieces_w / kl_pieces_h and kl_cols_w / kl_cols_h (instantiated pieces per thread and columns per block of that launch as in
         kl_plan(); 0 streaming, -1 none yet),
+        sp_ingest_check_share / sp_ingest_sort_tile (stored entries per workgroup of the entry check / of a radix pass of
+        set_matrix_sparse_device),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
         column / a row of a dense matrix)."""
         v = C.c_double(0)

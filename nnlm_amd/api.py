@@ -393,9 +393,55 @@ def finish_nnmf(out, ctx, run_time=None):
 # ------------------------------------------------------------------------------------------------
 def _refuse_device(x, who, name):
     """The entries that stage their matrix on the host say so by name when handed device memory."""
+    _refuse_sparse_tensor(x, who, name)
     if _lib.is_device_array(x):
         raise NnlmStop("%s: %s lives in device memory; this entry takes host arrays only (nnmf() and nnmf_batch() accept a device "
                        "matrix) -- copy it to the host first." % (who, name))
+
+
+def _refuse_sparse_tensor(x, who, name):
+    """A sparse tensor (any torch sparse layout) where an entry takes host arrays: refused by name, in device or in host memory."""
+    if x is None or isinstance(x, (np.ndarray, np.generic, list, tuple, dict, int, float)):
+        return
+    if _lib.is_host_sparse_tensor(x):
+        raise NnlmStop("%s: %s is a sparse tensor in host memory; pass a host sparse matrix as an object with tocsc() (scipy.sparse), or "
+                       "move the tensor to the GPU for nnmf() / nnmf_batch()." % (who, name))
+    if str(getattr(x, "layout", "")).startswith("torch.sparse_") and _lib.is_device_array(x):
+        raise NnlmStop("%s: %s is a sparse tensor in device memory; this entry takes host arrays only (nnmf() and nnmf_batch() accept a "
+                       "sparse CSC / CSR tensor of the GPU) -- pass the matrix as a host sparse object (tocsc())." % (who, name))
+
+
+def _sparse_device_parts(A, who):
+    """_lib.sparse_tensor_parts(A) for nnmf() / nnmf_batch(); a sparse tensor in host memory is refused by name."""
+    if A is None or isinstance(A, (np.ndarray, np.generic, list, tuple, dict, int, float)):
+        return None
+    if _lib.is_host_sparse_tensor(A):
+        raise NnlmStop("%s: A is a sparse tensor in host memory; pass a host sparse matrix as an object with tocsc() (scipy.sparse), or move "
+                       "the tensor to the GPU." % who)
+    try:
+        return _lib.sparse_tensor_parts(A)
+    except ValueError as e:
+        raise NnlmStop("%s: %s" % (who, e)) from None
+
+
+def _sparse_device_refusals(loss, absent, sparse_kl):
+    """What _sparse_input refuses without looking at the values (the rest is the library's message)."""
+    if sparse_kl and absent == "missing":
+        raise NnlmStop(_SPARSE_KL_MISSING)
+    if loss == "mkl" and not sparse_kl:
+        raise NnlmStop("Sparse A is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'.")
+
+
+def _sparse_device_matrix(parts, h, absent, kl, batch):
+    """The `matrix` of _prepare_nnmf for a sparse tensor in device memory: ingested into h (nnlm_set_matrix_sparse_device); check_k's
+    bound with absent = 'missing' is the fewest stored entries of a row or a column, from the handle."""
+    ptr, idx, val, shape, layout = parts
+    h.set_matrix_sparse_device(ptr, idx, val, shape, layout, absent=absent, kl=kl, batch=batch)
+    n, m = h.n, h.m
+    min_k = min(n, m)
+    if absent == "missing" and h.matrix_info()["any_missing"]:
+        min_k = min(min_k, int(h.get_info("matrix_min_row_observed")), int(h.get_info("matrix_min_col_observed")))
+    return dict(A=None, n=n, m=m, min_k=min_k)
 
 
 def _device_index(A):
@@ -454,17 +500,26 @@ def _tensor_lib(A):
 
 
 def _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
-                 show_warning, inner_max_iter, inner_rel_tol, rng, absent):
-    """nnmf() on a matrix in device memory: ingest, factors, run and export on one Handle; A never visits the host."""
+                 show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl=False, parts=None):
+    """nnmf() on a matrix in device memory: ingest, factors, run and export on one Handle; A never visits the host.  parts: the arrays
+    of a sparse CSC / CSR tensor (_lib.sparse_tensor_parts), ingested through the door `absent` and `sparse_kl` name."""
     torch = _tensor_lib(A)
+    if parts is not None:
+        loss = _match_arg(loss, ("mse", "mkl"), "loss")
+        absent = _match_arg(absent, ("zero", "missing"), "absent")
+        _sparse_device_refusals(loss, absent, sparse_kl)
+        sparse_kl = bool(sparse_kl) and loss == "mkl"
     g = rng or np.random.default_rng()
     t0 = time.perf_counter()
     with _lib.Handle(_device_index(A), _env_precision()) as h:
-        mat = _device_matrix(A, h)
+        mat = _device_matrix(A, h) if parts is None else _sparse_device_matrix(parts, h, absent, sparse_kl, False)
+        # (a sparse tensor: the handle knows what absent entries are; _prepare_nnmf's `absent` asks for an object with tocsc())
         args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, _host_factor_entries(init, "nnmf"), mask, W_norm, check_k, max_iter,
                                      rel_tol, n_threads, trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, matrix=mat,
-                                     absent=absent)
+                                     absent=absent if parts is None else "zero")
         ctx["init"] = init
+        if parts is not None:
+            ctx["absent"], ctx["sparse_kl"] = absent, sparse_kl
         n, m, K = mat["n"], mat["m"], args[1]
         Wm, Hm = args[4], args[5]
         W, H = _default_init(args[2], args[3], Wm, Hm, n, m, K, g)
@@ -500,10 +555,17 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     init entries and known profiles may be host arrays or tensors of that device (the latter are copied to the host, k (n + m) elements,
     stacked there and uploaded with the other factors); masks are host arrays.  check_k with missing entries:
     this route counts every non-finite entry (NaN, +-Inf) as missing, as the fit does; the host route counts NaN only.
+
+    ``A`` may also be a SPARSE tensor of the GPU, ``torch.sparse_csc_tensor`` or ``sparse_csr_tensor`` (int32 or int64 indices, any of the
+    four value types): its three arrays are validated, transposed and converted by kernels where they lie, and ``absent``, ``sparse_kl``,
+    ``loss`` mean what they mean for a host sparse A.  The structure must be canonical (indices strictly increasing in every line): what
+    as_csc() repairs on the host is refused here, with the library's message.  W and H come back as fp64 tensors on A's device.  Other
+    sparse layouts (COO, BSR, BSC) and sparse tensors in host memory are refused by name.
     """
-    if _lib.is_device_array(A):
+    parts = _sparse_device_parts(A, "nnmf")
+    if parts is not None or _lib.is_device_array(A):
         return _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
-                            show_warning, inner_max_iter, inner_rel_tol, rng, absent)
+                            show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts)
     args, ctx = prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads,
                              trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl)
     g = rng or np.random.default_rng()
@@ -573,16 +635,18 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     loss = _match_arg(nnmf_options.get("loss", "mse"), ("mse", "mkl"), "loss")
     if loss != "mse" and not kl_door:
         raise unsupported("loss = 'mkl' (KL) is not supported by the batched factorisation: square loss only")
-    if is_sparse(A) and not sparse_batch:
+    parts = _sparse_device_parts(A, "nnmf_batch")  # (a sparse CSC / CSR tensor of the GPU: the same doors, ingested where it lies)
+    sparse_A = is_sparse(A) or parts is not None
+    if sparse_A and not sparse_batch:
         raise unsupported("a sparse A is not supported by the batched factorisation (dense A only)")
-    if kl_door and not is_sparse(A):
+    if kl_door and not sparse_A:
         raise unsupported("sparse_batch = 'kl' needs a sparse A (an object with tocsc()): the batched KL solver runs over the stored "
                           "entries of a sparse count matrix")
     kl_door = kl_door and loss == "mkl"  # (square loss through this door: sparse_batch = True)
     if missing_door:
-        _missing_door_checks(A, nnmf_options, unsupported)
+        _missing_door_checks(A, nnmf_options, unsupported, sparse_A)
         nnmf_options = dict(nnmf_options, absent="missing")
-    elif is_sparse(A) and _match_arg(nnmf_options.get("absent", "zero"), ("zero", "missing"), "absent") == "missing":
+    elif sparse_A and _match_arg(nnmf_options.get("absent", "zero"), ("zero", "missing"), "absent") == "missing":
         raise unsupported("absent = 'missing' is not supported by the batched factorisation of a sparse A (sparse_batch = True): "
                           "absent entries are zeros")
     if sum(ks) > _lib.BATCH_MAX:
@@ -605,7 +669,7 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     if on_device:  # one ingest shared by all members; the handle then runs the batch (what nnlm_c_nnmf_batch does around a host A)
         h = _lib.Handle(_device_index(A), _env_precision())
     try:
-        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door, kl_door)
+        return _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door, kl_door, parts)
     finally:
         if h is not None:
             h.close()
@@ -627,9 +691,9 @@ def _sparse_batch_arg(sparse_batch, who):
     return False
 
 
-def _missing_door_checks(A, nnmf_options, unsupported):
+def _missing_door_checks(A, nnmf_options, unsupported, sparse_A=None):
     """sparse_batch = 'missing': a sparse A, and `absent`, if given, 'missing'."""
-    if not is_sparse(A):
+    if not (is_sparse(A) if sparse_A is None else sparse_A):
         raise unsupported("sparse_batch = 'missing' needs a sparse A (an object with tocsc()): the missing entries of a dense matrix of "
                           "the batched factorisation come from a hold-out set only")
     if _match_arg(nnmf_options.get("absent", "missing"), ("zero", "missing"), "absent") != "missing":
@@ -637,11 +701,16 @@ def _missing_door_checks(A, nnmf_options, unsupported):
                           "entries are missing); use sparse_batch = True for absent entries that are zeros")
 
 
-def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False, kl_door=False):
-    """nnmf_batch behind its argument checks; h: the handle of a device A (None for a host A)."""
+def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False, kl_door=False, parts=None):
+    """nnmf_batch behind its argument checks; h: the handle of a device A (None for a host A); parts: the arrays of a sparse tensor in
+    device memory (_lib.sparse_tensor_parts), ingested through the door's batch entry."""
     B = len(ks)
     prep, Ws, Hs, mat = [], [], [], None
-    if h is not None:
+    if parts is not None:
+        _sparse_device_refusals("mkl" if kl_door else "mse", "missing" if missing_door else "zero", kl_door)
+        mat = _sparse_device_matrix(parts, h, "missing" if missing_door else "zero", kl_door, True)
+        opts = dict(opts, absent="zero")  # (the handle knows; _prepare_nnmf's `absent` asks for an object with tocsc())
+    elif h is not None:
         mat = _device_matrix(A, h)
         if h.matrix_info()["any_missing"]:
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
@@ -655,6 +724,8 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False
         args, ctx, mat = _prepare_nnmf(A, ks[b], init=None if init is None else init[b], rng=g, matrix=mat, **opts)
         if kl_door:
             ctx["sparse_kl"] = True  # (what nnmf(sparse_kl = True) records for the same member)
+        if parts is not None and missing_door:
+            ctx["absent"] = "missing"
         if b == 0 and h is None and not isinstance(mat["A"], CSC) and not np.isfinite(mat["A"]).all():
             raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
         n, m = mat["n"], mat["m"]
@@ -665,7 +736,7 @@ def _nnmf_batch_members(A, ks, init, g, opts, unsupported, h, missing_door=False
     a0 = prep[0][0]
     cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    if missing_door:
+    if missing_door and parts is None:
         outs = _lib.c_nnmf_csc_missing_batch(*a0[0], ks, Ws, Hs, *a0[6:], callbacks=cb)
     elif isinstance(a0[0], CSC):
         entry = _lib.c_nnmf_csc_kl_batch if kl_door else _lib.c_nnmf_csc_batch

@@ -47,7 +47,8 @@ static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
               P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES,
-              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_SPKL_BATCH_H, P_SPKL_BATCH_W, P_COUNT };
+              P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_SPKL_BATCH_H, P_SPKL_BATCH_W,
+              P_SP_INGEST, P_SP_INGEST_PTR, P_SP_INGEST_CHECK, P_SP_INGEST_BUILD, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
 //  "allgather" / "allreduce": the RCCL collective of a sharded half-step between two events on the stream it is enqueued on;
 //  "unpack": shard_unpack_kernel + the sum of the ranks' Gram partial sums behind it)
@@ -66,9 +67,13 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  coordinate sums, ONE sp_batch_errors_kernel launch over the non-zeros for all members, its reduction and the closing kernel)
 //  "spkl_batch_h" / "spkl_batch_w": the solver launches of a batched KL half-step on a sparse A (k_sparse_kl_batch.h: ONE launch over the
 //  short lines for all active members, then the long form once per active member); its row copy and column sums are in "spkl_copy"
+//  "sp_ingest": nnlm_set_matrix_sparse_device from its first kernel to its last copy (k_sparse_ingest.h; the host's waits for the verdicts
+//  between the stages are inside it); "sp_ingest_ptr" / "sp_ingest_check" / "sp_ingest_build": the kernels of its stages alone -- the
+//  pointer check, the entry check with the conversions, the index histogram + its scan + the radix passes
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
                                           "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries",
-                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors", "spkl_batch_h", "spkl_batch_w"};
+                                          "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors", "spkl_batch_h", "spkl_batch_w",
+                                          "sp_ingest", "sp_ingest_ptr", "sp_ingest_check", "sp_ingest_build"};
 
 // A chunk of the columns of a sparse-missing half-step whose Grams are held at once (nnlm_handle::spg_plan): columns [c0, c1), long
 // columns longc[l0 .. l1)
@@ -1393,6 +1398,51 @@ static int spkl_layout(nnlm_handle *h, int o, const long long *ptr, int ncols)
     return NNLM_OK;
 }
 
+// The common tail of the sparse set-matrix entries, behind the six resident arrays: the partial sums' buffer, what absent entries are,
+// the per-orientation tables of the door (host pointer arrays colptr [m + 1], rowptr [n + 1]) and the KL constant from klc = the sum of
+// (v + eps) log(v + eps) - v over the stored entries.  Frees the matrix on failure.
+static int sp_finish(nnlm_handle *h, const char *who, const long long *colptr, const long long *rowptr, double klc, bool absent_missing, bool kl)
+{
+    const int n = h->n, m = h->m;
+    const long long nnz = h->nnz;
+    // partial sums of the error block (three per workgroup of sp_errors_kernel) and of the penalty sums (three per 256 columns)
+    const int nw = nnlm_sp_workers(nnz, 64, h->cus_device); // (the most workgroups any rank asks for: one worker per wavefront)
+    const size_t eb = (size_t)(nw + 3) / 4, pb = (size_t)((n > m ? n : m) + 255) / 256;
+    h->partials_elems = 3 * (eb > pb ? eb : pb) + 64;
+    if (hipMalloc(&h->partials, h->partials_elems * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        free_matrix(h);
+        return fail(h, NNLM_ERR_HIP, "%s: hipMalloc of %zu partial sums failed", who, h->partials_elems);
+    }
+    if (absent_missing) {
+        h->sp_missing = true;
+        h->n_non_missing = (double)nnz; // N_non_missing, src/nnmf.cpp:69
+        h->any_missing = (double)nnz != (double)n * (double)m;
+        h->kl_const = klc / h->n_non_missing; // src/nnmf.cpp:70: over the stored entries only
+        int rl = spg_layout(h, 1, colptr, m);
+        if (rl == NNLM_OK) rl = spg_layout(h, 0, rowptr, n);
+        if (rl != NNLM_OK) {
+            free_matrix(h);
+            return rl;
+        }
+        return NNLM_OK;
+    }
+    if (kl) {
+        h->sp_kl = true;
+        int rl = spkl_layout(h, 1, colptr, m);
+        if (rl == NNLM_OK) rl = spkl_layout(h, 0, rowptr, n);
+        if (rl != NNLM_OK) {
+            free_matrix(h);
+            return rl;
+        }
+    }
+    h->n_non_missing = (double)n * (double)m;
+    h->any_missing = false;
+    // the zeros add (n m - nnz) eps log eps
+    h->kl_const = (klc + ((double)n * (double)m - (double)nnz) * (NNLM_TINY * std::log(NNLM_TINY))) / h->n_non_missing;
+    return NNLM_OK;
+}
+
 // The CSC contract of the sparse set-matrix entries, checked in the order they have always reported it (first offender named)
 static int csc_check(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing, const char *who,
                      bool kl)
@@ -1477,42 +1527,7 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
         free_matrix(h);
         return rc;
     }
-    // partial sums of the error block (three per workgroup of sp_errors_kernel) and of the penalty sums (three per 256 columns)
-    const int nw = nnlm_sp_workers(nnz, 64, h->cus_device); // (the most workgroups any rank asks for: one worker per wavefront)
-    const size_t eb = (size_t)(nw + 3) / 4, pb = (size_t)((n > m ? n : m) + 255) / 256;
-    h->partials_elems = 3 * (eb > pb ? eb : pb) + 64;
-    if (hipMalloc(&h->partials, h->partials_elems * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        free_matrix(h);
-        return fail(h, NNLM_ERR_HIP, "%s: hipMalloc of %zu partial sums failed", who, h->partials_elems);
-    }
-    if (absent_missing) {
-        h->sp_missing = true;
-        h->n_non_missing = (double)nnz; // N_non_missing, src/nnmf.cpp:69
-        h->any_missing = (double)nnz != (double)n * (double)m;
-        h->kl_const = klc / h->n_non_missing; // src/nnmf.cpp:70: over the stored entries only
-        int rl = spg_layout(h, 1, colptr, m);
-        if (rl == NNLM_OK) rl = spg_layout(h, 0, rptr.data(), n);
-        if (rl != NNLM_OK) {
-            free_matrix(h);
-            return rl;
-        }
-        return NNLM_OK;
-    }
-    if (kl) {
-        h->sp_kl = true;
-        int rl = spkl_layout(h, 1, colptr, m);
-        if (rl == NNLM_OK) rl = spkl_layout(h, 0, rptr.data(), n);
-        if (rl != NNLM_OK) {
-            free_matrix(h);
-            return rl;
-        }
-    }
-    h->n_non_missing = (double)n * (double)m;
-    h->any_missing = false;
-    // the zeros add (n m - nnz) eps log eps
-    h->kl_const = (klc + ((double)n * (double)m - (double)nnz) * (NNLM_TINY * std::log(NNLM_TINY))) / h->n_non_missing;
-    return NNLM_OK;
+    return sp_finish(h, who, colptr, rptr.data(), klc, absent_missing, kl);
 }
 
 extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
@@ -1619,6 +1634,288 @@ extern "C" int nnlm_set_matrix_csc_missing_batch(nnlm_handle *h, int n, int m, c
     rc = up();
     if (rc != NNLM_OK) free_matrix(h);
     return rc;
+}
+
+// Sparse A that already lives in device memory (include/nnlm_mi355x.h, DESIGN section 4.21, k_sparse_ingest.h): the work of
+// set_matrix_csc_impl as kernels.  Everything is built in allocations of its own; the handle is touched only after the last stage has
+// succeeded, so a refusal leaves its previous matrix and factors alone.
+namespace {
+struct SpiBufs { // device allocations of one ingest: released at the end of the call unless the handle has taken them
+    std::vector<void *> v;
+    ~SpiBufs()
+    {
+        for (void *p : v) hipFree(p);
+    }
+    template <typename P> bool get(P **p, size_t bytes)
+    {
+        void *q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        v.push_back(q);
+        *p = (P *)q;
+        return true;
+    }
+    void release(void *p) { v.erase(std::find(v.begin(), v.end(), p)); } // (the handle owns it now)
+};
+} // namespace
+
+// One of the three arrays of a nnlm_dev_sparse, len contiguous elements of es bytes: dev_matrix_check's rules for a pointer (alignment,
+// device or managed memory of the handle's device, the extent inside its allocation, not a buffer of the handle), before a kernel reads it
+static int dev_array_check(nnlm_handle *h, const char *who, const char *name, const void *ptr, size_t es, long long len)
+{
+    if ((uintptr_t)ptr % es) return fail(h, NNLM_ERR_ARG, "%s: %s is not aligned to its %zu-byte elements", who, name, es);
+    hipPointerAttribute_t at;
+    memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, ptr);
+    (void)hipGetLastError(); // (the query leaves a sticky error behind for a pointer the runtime does not know)
+    if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+        return fail(h, NNLM_ERR_ARG, "%s: %s is not device (or managed) memory -- a host pointer?", who, name);
+    if (at.type == hipMemoryTypeDevice && at.device != h->device)
+        return fail(h, NNLM_ERR_ARG, "%s: %s lives on device %d, the handle on device %d", who, name, at.device, h->device);
+    void *base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) == hipSuccess) {
+        const size_t span = (size_t)len * es;
+        if ((const char *)ptr + span > (const char *)base + size)
+            return fail(h, NNLM_ERR_ARG, "%s: %s (%lld elements) reaches %zu bytes past the end of its allocation", who, name, len,
+                        (size_t)(((const char *)ptr + span) - ((const char *)base + size)));
+        if (owns_allocation(h, base)) return fail(h, NNLM_ERR_ARG, "%s: %s aliases a buffer of the handle itself", who, name);
+    } else
+        (void)hipGetLastError();
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_sparse *A, int n, int m, int door, void *stream)
+{
+    const char *who = "nnlm_set_matrix_sparse_device";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!A) return fail(h, NNLM_ERR_ARG, "%s: A is NULL", who);
+    if (A->layout != NNLM_SP_CSC && A->layout != NNLM_SP_CSR)
+        return fail(h, NNLM_ERR_ARG, "%s: A.layout = %d is neither NNLM_SP_CSC nor NNLM_SP_CSR", who, A->layout);
+    const bool csc = A->layout == NNLM_SP_CSC;
+    const char *pname = csc ? "colptr" : "rowptr", *lname = csc ? "column" : "row", *iname = csc ? "row" : "column";
+    if (n <= 0 || m <= 0 || !A->ptr)
+        return fail(h, NNLM_ERR_ARG, "%s: A must be a non-empty n x m matrix with %s[%s + 1] (n=%d, m=%d)", who, pname, csc ? "m" : "n", n, m);
+    if ((A->ptr_dtype != NNLM_IT_I32 && A->ptr_dtype != NNLM_IT_I64) || (A->idx_dtype != NNLM_IT_I32 && A->idx_dtype != NNLM_IT_I64))
+        return fail(h, NNLM_ERR_ARG, "%s: A.ptr_dtype = %d, A.idx_dtype = %d: each must be NNLM_IT_I32 or NNLM_IT_I64", who, A->ptr_dtype, A->idx_dtype);
+    if (A->val_dtype < NNLM_DT_F64 || A->val_dtype > NNLM_DT_BF16)
+        return fail(h, NNLM_ERR_ARG, "%s: A.val_dtype = %d is not one of NNLM_DT_F64 .. NNLM_DT_BF16", who, A->val_dtype);
+    const int all_doors = NNLM_SP_ABSENT_MISSING | NNLM_SP_KL | NNLM_SP_BATCH;
+    if (door < 0 || (door & ~all_doors))
+        return fail(h, NNLM_ERR_ARG, "%s: door = %d has bits other than NNLM_SP_ABSENT_MISSING, NNLM_SP_KL and NNLM_SP_BATCH", who, door);
+    const bool absent_missing = door & NNLM_SP_ABSENT_MISSING, kl = door & NNLM_SP_KL, batch = door & NNLM_SP_BATCH;
+    if (absent_missing && kl)
+        return fail(h, NNLM_ERR_ARG, "%s: door = NNLM_SP_ABSENT_MISSING | NNLM_SP_KL: KL loss on a sparse matrix takes absent entries as zeros", who);
+    if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix is single-GPU only (this handle has a communicator)", who);
+    const long long nnz = A->nnz;
+    if (nnz < 0) return fail(h, NNLM_ERR_ARG, "%s: nnz = %lld is negative", who, nnz);
+    if (nnz > 0 && (!A->idx || !A->val)) return fail(h, NNLM_ERR_ARG, "%s: idx / val is NULL with nnz = %lld", who, nnz);
+    const int lines = csc ? m : n, other = csc ? n : m; // lines of the given side, of the side to build
+    const bool p64 = A->ptr_dtype == NNLM_IT_I64, i64 = A->idx_dtype == NNLM_IT_I64, f64 = h->prec == NNLM_PREC_F64;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = dev_array_check(h, who, "A.ptr", A->ptr, p64 ? 8 : 4, (long long)lines + 1);
+    if (rc == NNLM_OK && nnz > 0) rc = dev_array_check(h, who, "A.idx", A->idx, i64 ? 8 : 4, nnz);
+    if (rc == NNLM_OK && nnz > 0) rc = dev_array_check(h, who, "A.val", A->val, dt_size(A->val_dtype), nnz);
+    if (rc != NNLM_OK) return rc;
+    g_attr_err = hipSuccess;
+    hipStream_t st = h->stream;
+    if ((rc = stream_after(h, st, (hipStream_t)stream)) != NNLM_OK) return rc; // the caller's stream produced the arrays
+    auto hipfail = [&](const char *what, hipError_t e) {
+        hipStreamSynchronize(st); // (nothing of this call is left in flight over buffers about to be freed)
+        (void)hipGetLastError();
+        return fail(h, NNLM_ERR_HIP, "%s: %s failed: %s", who, what, hipGetErrorString(e));
+    };
+    auto nomem = [&](const char *what) {
+        hipStreamSynchronize(st);
+        return fail(h, NNLM_ERR_HIP, "%s: hipMalloc of %s failed (nnz = %lld)", who, what, nnz);
+    };
+
+    SpiBufs bufs;
+    const size_t es = f64 ? 8 : 4, vb = (size_t)nnz * es + 64, ib = (size_t)nnz * 4 + 64; // (sp_upload's sizes)
+    long long *gptr = nullptr, *optr = nullptr; // the given side's resident arrays, the built side's
+    int *gidx = nullptr, *oidx = nullptr;
+    void *gval = nullptr, *oval = nullptr;
+    if (!bufs.get(&gptr, (size_t)(lines + 1) * 8) || !bufs.get(&optr, (size_t)(other + 1) * 8) || !bufs.get(&gidx, ib) || !bufs.get(&oidx, ib) ||
+        !bufs.get(&gval, vb) || !bufs.get(&oval, vb))
+        return nomem("the resident arrays");
+    std::vector<long long> hg, ho; // host copies of the two pointer arrays
+    std::vector<long long> hcode;
+    std::vector<double> hstat;
+    const int nb_ptr = (lines + 256) / 256;
+    const long long share = nnlm_spi_check_share(), tile = nnlm_spi_sort_tile(), stile = nnlm_spi_scan_tile();
+    const int nb_chk = (int)((nnz + share - 1) / share), nb_sort = (int)((nnz + tile - 1) / tile);
+    try {
+        hg.resize((size_t)lines + 1);
+        ho.resize((size_t)other + 1);
+        hcode.resize((size_t)(nb_ptr > nb_chk ? nb_ptr : nb_chk));
+        hstat.resize(3 * (size_t)nb_chk);
+    } catch (...) {
+        return fail(h, NNLM_ERR_HIP, "%s: host buffers for %d + %d pointers", who, n + 1, m + 1);
+    }
+    ProfScope ps_all(h, P_SP_INGEST);
+
+    // stage 1: the pointers
+    long long *dcode = nullptr;
+    double *dstat = nullptr;
+    if (!bufs.get(&dcode, hcode.size() * 8) || !bufs.get(&dstat, hstat.size() * 8)) return nomem("the per-block verdicts");
+    {
+        ProfScope ps(h, P_SP_INGEST_PTR);
+        nnlm_tu_spi_ptr(A->ptr, p64, lines, nnz, gptr, dcode, st);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hcode.data(), dcode, (size_t)nb_ptr * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(hg.data(), gptr, (size_t)(lines + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hipfail("the pointer check", e);
+    {
+        long long first = LLONG_MAX;
+        for (int b = 0; b < nb_ptr; b++) first = hcode[b] < first ? hcode[b] : first;
+        if (first == 0) return fail(h, NNLM_ERR_ARG, "%s: %s[0] = %lld, must be 0", who, pname, hg[0]);
+        if (first <= lines) return fail(h, NNLM_ERR_ARG, "%s: %s decreases at %s %d", who, pname, lname, (int)(first - 1));
+        if (first == (long long)lines + 1)
+            return fail(h, NNLM_ERR_ARG, "%s: %s[%d] = %lld, but A.nnz = %lld", who, pname, lines, hg[(size_t)lines], nnz);
+    }
+    if (nnz > (long long)n * (long long)m) return fail(h, NNLM_ERR_ARG, "%s: nnz = %lld exceeds n * m", who, nnz);
+
+    // stage 2: the entries, on pointers that hold; the given side's indices and values land in their resident types
+    const int bits = other <= 1 ? 0 : 32 - __builtin_clz((unsigned)(other - 1)), passes = (bits + 7) / 8;
+    int *ltmp = nullptr, *keyb = nullptr, *keyc = nullptr; // line numbers' other buffer; the keys after an odd / an even pass
+    void *vtmp = nullptr;
+    long long *ghist = nullptr, *bsum = nullptr;
+    const long long scan_len = 256LL * nb_sort > (long long)other + 1 ? 256LL * nb_sort : (long long)other + 1;
+    if (nnz > 0) {
+        if (passes >= 1 && (!bufs.get(&ltmp, ib) || !bufs.get(&vtmp, vb) || !bufs.get(&ghist, 256 * (size_t)nb_sort * 8))) return nomem("the sort buffers");
+        if (passes >= 2 && !bufs.get(&keyb, ib)) return nomem("the sort buffers");
+        if (passes >= 3 && !bufs.get(&keyc, ib)) return nomem("the sort buffers");
+    }
+    if (!bufs.get(&bsum, (size_t)((scan_len + stile - 1) / stile) * 8)) return nomem("the scan buffer");
+    // the entries' line numbers and values start where an even number of passes ends in the resident arrays
+    int *lcur = (passes & 1) ? ltmp : oidx, *lnext = (passes & 1) ? oidx : ltmp;
+    void *vcur = (passes & 1) ? vtmp : oval, *vnext = (passes & 1) ? oval : vtmp;
+    double over = 0.0, mx = 0.0, klc = 0.0;
+    if (nnz > 0) {
+        {
+            ProfScope ps(h, P_SP_INGEST_CHECK);
+            nnlm_tu_spi_check(gptr, lines, A->idx, i64, A->val, A->val_dtype, f64, nnz, other, kl, gidx, gval, vcur, lcur, dcode, dstat, st);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(hcode.data(), dcode, (size_t)nb_chk * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hstat.data(), dstat, 3 * (size_t)nb_chk * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hipfail("the entry check", e);
+        long long first = LLONG_MAX;
+        for (int b = 0; b < nb_chk; b++) first = hcode[b] < first ? hcode[b] : first;
+        if (first != LLONG_MAX) {
+            const long long eo = first >> 3;
+            const int kind = (int)(first & 7);
+            long long *di = dcode; // (the verdicts are read: their buffers carry the offender's index and value)
+            long long oi = 0;
+            double ov = 0.0;
+            nnlm_tu_spi_fetch(A->idx, i64, A->val, A->val_dtype, eo, di, dstat, st);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&oi, di, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(&ov, dstat, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return hipfail("reading the offending entry", e);
+            const int j = (int)(std::upper_bound(hg.begin(), hg.end(), eo) - hg.begin()) - 1;
+            if (kind == 0) return fail(h, NNLM_ERR_ARG, "%s: %s index %lld out of range at entry %lld (%s %d)", who, iname, oi, eo, lname, j);
+            if (kind == 1) return fail(h, NNLM_ERR_ARG, "%s: %s indices of %s %d are not strictly increasing (entry %lld)", who, iname, lname, j, eo);
+            if (kind == 2)
+                return fail(h, NNLM_ERR_ARG, absent_missing ? "%s: entry %lld (%s %lld, %s %d) is not finite; a stored entry is an observation "
+                                                              "(leave a missing entry out of the structure)"
+                                                            : "%s: entry %lld (%s %lld, %s %d) is not finite; a sparse matrix has no missing entries "
+                                                              "(use nnlm_set_matrix for NA data)", who, eo, iname, oi, lname, j);
+            return fail(h, NNLM_ERR_ARG, "%s: entry %lld (%s %lld, %s %d) is negative (%g); KL loss needs non-negative data", who, eo, iname, oi, lname, j, ov);
+        }
+        for (int b = 0; b < nb_chk; b++) { // block order, as ingest_fill sums
+            over += hstat[3 * (size_t)b];
+            if (hstat[3 * (size_t)b + 1] > mx) mx = hstat[3 * (size_t)b + 1];
+            klc += hstat[3 * (size_t)b + 2];
+        }
+    }
+    if (!f64 && over > 0.0)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
+                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over);
+    if (!f64 && mx > 0.0 && mx < 7.8886090522101181e-31)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "max |A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale A or use "
+                                             "the strict fp64 mode", mx);
+
+    // stage 3: the other side, on indices that hold
+    {
+        ProfScope ps(h, P_SP_INGEST_BUILD);
+        e = hipMemsetAsync(optr, 0, (size_t)(other + 1) * 8, st);
+        if (e == hipSuccess && nnz > 0) {
+            nnlm_tu_spi_count(gidx, nnz, optr, st);
+            nnlm_tu_spi_scan(optr, (long long)other + 1, bsum, st);
+            const int *kin = gidx;
+            for (int p = 0; p < passes; p++) {
+                int *kout = p == passes - 1 ? nullptr : ((p & 1) ? keyc : keyb);
+                nnlm_tu_spi_sort_pass(kin, lcur, vcur, kout, lnext, vnext, f64, nnz, 8 * p, ghist, bsum, st);
+                kin = kout;
+                std::swap(lcur, lnext);
+                std::swap(vcur, vnext);
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ho.data(), optr, (size_t)(other + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st); // the last read of the caller's arrays was in stage 2
+    if (e != hipSuccess) return hipfail("building the other side", e);
+
+    // the handle takes the six arrays: from here on this is set_matrix_csc_impl behind its uploads
+    sync_all(h);
+    free_factors(h);
+    free_matrix(h);
+    h->n = n;
+    h->m = m;
+    h->npad = round_up_i(n, NNLM_PAD_N);
+    h->mpad = round_up_i(m, NNLM_PAD_M);
+    h->sparse = true;
+    h->x16 = false;
+    h->nnz = nnz;
+    h->sp_cptr = csc ? gptr : optr, h->sp_rptr = csc ? optr : gptr;
+    h->sp_ridx = csc ? gidx : oidx, h->sp_cidx = csc ? oidx : gidx;
+    h->sp_cval = csc ? gval : oval, h->sp_rval = csc ? oval : gval;
+    for (void *p : {(void *)gptr, (void *)optr, (void *)gidx, (void *)oidx, gval, oval}) bufs.release(p);
+    h->sp_bytes = (size_t)(m + 1) * 8 + (size_t)(n + 1) * 8 + 2 * ib + 2 * vb;
+    const std::vector<long long> &hc = csc ? hg : ho, &hr = csc ? ho : hg;
+    rc = sp_finish(h, who, hc.data(), hr.data(), klc, absent_missing, kl);
+    if (rc != NNLM_OK) return rc;
+    h->sp_batch = batch;
+    if (absent_missing) { // the fewest stored entries of a column / of a row
+        long long mc = LLONG_MAX, mr = LLONG_MAX;
+        for (int j = 0; j < m; j++) mc = std::min(mc, hc[(size_t)j + 1] - hc[j]);
+        for (int i = 0; i < n; i++) mr = std::min(mr, hr[(size_t)i + 1] - hr[i]);
+        h->min_obs[0] = (int)mc, h->min_obs[1] = (int)mr;
+    } else
+        h->min_obs[0] = n, h->min_obs[1] = m;
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_debug_sparse_resident(nnlm_handle *h, int side, long long *ptr_out, int *idx_out, double *val_out)
+{
+    const char *who = "nnlm_debug_sparse_resident";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!h->sparse) return fail(h, NNLM_ERR_ARG, "%s: the handle holds no sparse matrix", who);
+    if (side != 0 && side != 1) return fail(h, NNLM_ERR_ARG, "%s: side = %d is neither 0 (by columns) nor 1 (by rows)", who, side);
+    HIPCHK(h, hipSetDevice(h->device));
+    sync_all(h);
+    const int lines = side == 0 ? h->m : h->n;
+    const size_t nnz = (size_t)h->nnz;
+    if (ptr_out) HIPCHK(h, hipMemcpy(ptr_out, side == 0 ? h->sp_cptr : h->sp_rptr, (size_t)(lines + 1) * 8, hipMemcpyDeviceToHost));
+    if (idx_out && nnz) HIPCHK(h, hipMemcpy(idx_out, side == 0 ? h->sp_ridx : h->sp_cidx, nnz * 4, hipMemcpyDeviceToHost));
+    if (val_out && nnz) {
+        const void *src = side == 0 ? h->sp_cval : h->sp_rval;
+        if (h->prec == NNLM_PREC_F64) HIPCHK(h, hipMemcpy(val_out, src, nnz * 8, hipMemcpyDeviceToHost));
+        else {
+            std::vector<float> f(nnz);
+            HIPCHK(h, hipMemcpy(f.data(), src, nnz * 4, hipMemcpyDeviceToHost));
+            for (size_t e = 0; e < nnz; e++) val_out[e] = (double)f[e];
+        }
+    }
+    return NNLM_OK;
 }
 
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
@@ -2048,6 +2345,10 @@ extern "C" int nnlm_get_factors_device(nnlm_handle *h, const nnlm_dev_matrix *W,
 // nnlm_get_info "matrix_min_col_observed" / "matrix_min_row_observed": on first query, cached with the matrix
 static int observed_min(nnlm_handle *h, int which, double *value)
 {
+    if (h->sparse && h->min_obs[0] >= 0) { // (nnlm_set_matrix_sparse_device counted them from its host copies of the pointers)
+        *value = h->min_obs[which];
+        return NNLM_OK;
+    }
     if (h->sparse || !h->A) {
         *value = -1.0;
         return NNLM_OK;
@@ -3960,6 +4261,8 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sparse_kl_form_w") == 0) *value = h->spkl_form[0];
     else if (strcmp(key, "sparse_kl_form_h") == 0) *value = h->spkl_form[1];
     else if (strcmp(key, "sparse_kl_short_max") == 0) *value = nnlm_spkl_short_max();
+    else if (strcmp(key, "sp_ingest_check_share") == 0) *value = nnlm_spi_check_share();
+    else if (strcmp(key, "sp_ingest_sort_tile") == 0) *value = nnlm_spi_sort_tile();
     else if (strcmp(key, "sparse_kl_batch") == 0) *value = (h->sparse && h->sp_kl && h->sp_batch) ? 1.0 : 0.0;
     else if (strcmp(key, "sparse_kl_batch_form_w") == 0) *value = h->spklb_form[0];
     else if (strcmp(key, "sparse_kl_batch_form_h") == 0) *value = h->spklb_form[1];

@@ -1,5 +1,5 @@
 // tu_sparse.hip -- the instantiations of the sparse-A kernels (k_sparse.h, k_sparse_batch.h, k_sparse_na.h, k_sparse_na_batch.h, k_sparse_kl.h,
-// k_sparse_kl_batch.h), see tu_sweepq.h.
+// k_sparse_kl_batch.h, k_sparse_ingest.h), see tu_sweepq.h.
 #include "tu_sweepq.h"
 #include "k_sparse.h"
 #include "k_sparse_batch.h"
@@ -7,6 +7,7 @@
 #include "k_sparse_na_batch.h"
 #include "k_sparse_kl.h"
 #include "k_sparse_kl_batch.h"
+#include "k_sparse_ingest.h"
 #include <cstdlib>
 
 // Lanes per worker: KP = 16 -> four workers per wavefront, KP = 32 -> two, otherwise one (KP = 48 leaves 16 lanes idle; rank > 64 is
@@ -245,4 +246,81 @@ void nnlm_tu_sp_kl_batch(const SpKlBatchArgs &a, int method, bool f64, int group
         if (f64) launch_sp_kl_batch<4, double>(a, group, st);
         else launch_sp_kl_batch<4, float>(a, group, st);
     }
+}
+
+// ---- ingest of a sparse matrix in device memory (k_sparse_ingest.h) ----
+int nnlm_spi_check_share(void) { return SPI_CHECK_SHARE; }
+int nnlm_spi_sort_tile(void) { return SPI_SORT_TILE; }
+int nnlm_spi_scan_tile(void) { return SPI_SCAN_TILE; }
+
+void nnlm_tu_spi_ptr(const void *ptr, bool i64, int lines, long long nnz, long long *out, long long *blockmin, hipStream_t st)
+{
+    const int nb = (lines + SPI_THREADS) / SPI_THREADS; // lines + 1 pointers
+    if (i64) spi_ptr_kernel<long long><<<nb, SPI_THREADS, 0, st>>>((const long long *)ptr, lines, nnz, out, blockmin);
+    else spi_ptr_kernel<int><<<nb, SPI_THREADS, 0, st>>>((const int *)ptr, lines, nnz, out, blockmin);
+}
+
+// f(I{}, S{}) for the caller's index and value types
+template <typename F> static void spi_with_types(bool i64, int dtype, F &&f)
+{
+    auto g = [&](auto i) {
+        switch (dtype) {
+        case 0: f(i, double{}); break;
+        case 1: f(i, float{}); break;
+        case 2: f(i, nnlm_f16{}); break;
+        default: f(i, nnlm_bf16{}); break;
+        }
+    };
+    if (i64) g((long long)0);
+    else g((int)0);
+}
+
+void nnlm_tu_spi_check(const long long *ptr, int lines, const void *idx, bool i64, const void *val, int dtype, bool f64, long long nnz, long long other,
+                       bool kl, int *idx_out, void *val_out, void *val_sort, int *line_out, long long *blockcode, double *blockstat, hipStream_t st)
+{
+    const int nb = (int)((nnz + SPI_CHECK_SHARE - 1) / SPI_CHECK_SHARE);
+    spi_with_types(i64, dtype, [&](auto i, auto s) {
+        typedef decltype(i) I;
+        typedef decltype(s) S;
+        if (f64)
+            spi_check_kernel<I, S, double><<<nb, SPI_THREADS, 0, st>>>(ptr, lines, (const I *)idx, (const S *)val, nnz, other, kl ? 1 : 0, idx_out,
+                                                                       (double *)val_out, (double *)val_sort, line_out, blockcode, blockstat);
+        else
+            spi_check_kernel<I, S, float><<<nb, SPI_THREADS, 0, st>>>(ptr, lines, (const I *)idx, (const S *)val, nnz, other, kl ? 1 : 0, idx_out,
+                                                                      (float *)val_out, (float *)val_sort, line_out, blockcode, blockstat);
+    });
+}
+
+void nnlm_tu_spi_fetch(const void *idx, bool i64, const void *val, int dtype, long long e, long long *i_out, double *v_out, hipStream_t st)
+{
+    spi_with_types(i64, dtype, [&](auto i, auto s) {
+        typedef decltype(i) I;
+        typedef decltype(s) S;
+        spi_fetch_kernel<I, S><<<1, 1, 0, st>>>((const I *)idx, (const S *)val, e, i_out, v_out);
+    });
+}
+
+void nnlm_tu_spi_count(const int *idx, long long nnz, long long *cnt, hipStream_t st)
+{
+    long long nb = (nnz + SPI_THREADS - 1) / SPI_THREADS;
+    if (nb > 16384) nb = 16384;
+    spi_count_kernel<<<(int)nb, SPI_THREADS, 0, st>>>(idx, nnz, (unsigned long long *)cnt);
+}
+
+void nnlm_tu_spi_scan(long long *x, long long len, long long *bsum, hipStream_t st)
+{
+    const int nb = (int)((len + SPI_SCAN_TILE - 1) / SPI_SCAN_TILE);
+    spi_scan_sums_kernel<<<nb, SPI_THREADS, 0, st>>>(x, len, bsum);
+    spi_scan_top_kernel<<<1, SPI_THREADS, 0, st>>>(bsum, nb);
+    spi_scan_apply_kernel<<<nb, SPI_THREADS, 0, st>>>(x, len, bsum);
+}
+
+void nnlm_tu_spi_sort_pass(const int *kin, const int *lin, const void *vin, int *kout, int *lout, void *vout, bool f64, long long nnz, int shift,
+                           long long *ghist, long long *bsum, hipStream_t st)
+{
+    const int nb = (int)((nnz + SPI_SORT_TILE - 1) / SPI_SORT_TILE);
+    spi_hist_kernel<<<nb, SPI_THREADS, 0, st>>>(kin, nnz, shift, ghist, nb);
+    nnlm_tu_spi_scan(ghist, 256LL * nb, bsum, st);
+    if (f64) spi_scatter_kernel<double><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const double *)vin, kout, lout, (double *)vout, nnz, shift, ghist, nb);
+    else spi_scatter_kernel<float><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const float *)vin, kout, lout, (float *)vout, nnz, shift, ghist, nb);
 }

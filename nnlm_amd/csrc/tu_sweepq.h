@@ -141,3 +141,22 @@ int nnlm_spkl_batch_group(void);
 void nnlm_tu_sp_kl_batch(const SpKlBatchArgs &a, int method, bool f64, int group, hipStream_t st);
 // the long form alone (sp_kl_solve_long_kernel over a.longc): a batch launches it once per active member, on that member's offsets
 void nnlm_tu_sp_kl_long(const SpKlArgs &a, int method, bool f64, hipStream_t st);
+
+// Ingest of a sparse matrix in device memory (k_sparse_ingest.h, tu_sparse.hip).  i64: the caller's integer type
+// (int64, else int32); dtype: the caller's NNLM_DT_* value type; f64: the mode's value type.
+int nnlm_spi_check_share(void); // entries per block of the entry check
+int nnlm_spi_sort_tile(void);   // entries per block of a radix pass
+int nnlm_spi_scan_tile(void);   // elements per block of the scans
+// out [lines + 1] = the pointers as int64; blockmin [(lines + 256) / 256] offence codes
+void nnlm_tu_spi_ptr(const void *ptr, bool i64, int lines, long long nnz, long long *out, long long *blockmin, hipStream_t st);
+// nnz > 0.  blockcode [nb], blockstat [nb][3], nb = ceil(nnz / nnlm_spi_check_share())
+void nnlm_tu_spi_check(const long long *ptr, int lines, const void *idx, bool i64, const void *val, int dtype, bool f64, long long nnz, long long other,
+                       bool kl, int *idx_out, void *val_out, void *val_sort, int *line_out, long long *blockcode, double *blockstat, hipStream_t st);
+void nnlm_tu_spi_fetch(const void *idx, bool i64, const void *val, int dtype, long long e, long long *i_out, double *v_out, hipStream_t st);
+void nnlm_tu_spi_count(const int *idx, long long nnz, long long *cnt, hipStream_t st);
+// x [len] -> its exclusive scan, in place; bsum: scratch of ceil(len / nnlm_spi_scan_tile()) elements
+void nnlm_tu_spi_scan(long long *x, long long len, long long *bsum, hipStream_t st);
+// One stable radix pass by (key >> shift) & 255 (kout == NULL: keys not written).  ghist: 256 ceil(nnz / nnlm_spi_sort_tile()) elements;
+// bsum: scratch of the scan of ghist
+void nnlm_tu_spi_sort_pass(const int *kin, const int *lin, const void *vin, int *kout, int *lout, void *vout, bool f64, long long nnz, int shift,
+                           long long *ghist, long long *bsum, hipStream_t st);
