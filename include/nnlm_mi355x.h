@@ -486,6 +486,11 @@ int nnlm_debug_set_cus(int cus);
 /* Test hook: handles created from now on launch xprod16_tn_kernel (the split-fp16 cross product) with `waves` = 8 or 10 wavefronts per
  * block -- 128- or 160-column tiles -- wherever that form exists (10: ranks up to 52); 0 = the launch plan decides. */
 int nnlm_debug_set_xprod_waves(int waves);
+/* Test hook: cache policy of the stream of A in the A-streaming cross products (xprod16_tn_kernel, xprod16_err_kernel, xprod_tn_kernel)
+ * of handles created from now on.  The requests for A of the contraction stages >= nt_from_stage (the global stage index: 64 fp32-mode /
+ * 32 strict-mode contraction elements each) are non-temporal: 0 = all of A, INT_MAX = none, -1 = the library's choice.  Values below -1
+ * are refused.  A cache policy changes no value: results are bit-identical for every setting. */
+int nnlm_debug_set_a_stream(int nt_from_stage);
 /* The launch plan of one xprod16_tn_kernel launch: ldc output columns (a multiple of 128), `stages` contraction stages of 64 elements,
  * rank k <= 64, `cus` compute units, force_waves as nnlm_debug_set_xprod_waves.  Pure function, works without a GPU.
  * out[0..6] = wavefronts per block, split-K slabs S, stages per slab, tiles, blocks (tiles x S), 4-row pieces of the factor image a
@@ -506,7 +511,8 @@ int nnlm_kl_plan(int p, int k, int precision, int mask_words, int out[8]);
 int nnlm_debug_alloc_limit(size_t bytes);
 /* Facts about the handle's last launches, for bench.py's kernel attribution: key = "cus" (compute units the launch policy
  * counts), "xprod_waves_w" / "xprod_waves_h" and "xprod_splits_w" / "xprod_splits_h" (wavefronts per block and split-K slabs of the last
- * xprod16_tn_kernel launch of the W / H half-step, 0 none yet), "xprod_splits_err" (slabs of the last xprod16_err_kernel launch, 0 none yet), "sweep_form_w" / "sweep_form_h" (SCD sweep of the last W / H half-step: 0 plain sweep_scd_q_kernel, 1 persistent
+ * xprod16_tn_kernel launch of the W / H half-step, 0 none yet), "xprod_splits_err" (slabs of the last xprod16_err_kernel launch, 0 none yet),
+ * "a_stream_nt_from" (the nt_from_stage -- see nnlm_debug_set_a_stream -- the last A-streaming cross-product launch was given, -1 none yet), "sweep_form_w" / "sweep_form_h" (SCD sweep of the last W / H half-step: 0 plain sweep_scd_q_kernel, 1 persistent
  * sweep_scd_qw_kernel -- both strict fp64 --, 2 sweep_scd_f_kernel, 3 sweep_row_kernel (fp32-operand mode: 3 while the launch is one
  * round of four-column wavefronts, at most 32 columns per CU), -1 none yet), "sweep_groups_w" /
  * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "lee_lanes_w" / "lee_lanes_h" and

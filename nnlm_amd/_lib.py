@@ -32,7 +32,7 @@ EXPORTS = [
     "nnlm_half_step", "nnlm_iterate", "nnlm_run", "nnlm_take_sweeps", "nnlm_errors", "nnlm_sync", "nnlm_profile_enable",
     "nnlm_profile_get", "nnlm_profile_reset", "nnlm_comm_unique_id", "nnlm_comm_init", "nnlm_comm_info",
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
-    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_xprod_plan", "nnlm_kl_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
+    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_debug_set_a_stream", "nnlm_xprod_plan", "nnlm_kl_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_matrix_csc_kl", "nnlm_c_nnmf_csc_kl", "nnlm_c_nnlm_csc_kl",
@@ -178,6 +178,8 @@ def load():
     lib.nnlm_debug_set_cus.argtypes = [C.c_int]
     lib.nnlm_debug_set_xprod_waves.restype = C.c_int
     lib.nnlm_debug_set_xprod_waves.argtypes = [C.c_int]
+    lib.nnlm_debug_set_a_stream.restype = C.c_int
+    lib.nnlm_debug_set_a_stream.argtypes = [C.c_int]
     lib.nnlm_xprod_plan.restype = C.c_int
     lib.nnlm_xprod_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip]
     lib.nnlm_kl_plan.restype = C.c_int
@@ -1094,7 +1096,8 @@ class Handle:
 
     def get_info(self, key):
         """cus, xprod_waves_w / xprod_waves_h and xprod_splits_w / xprod_splits_h (wavefronts per block and slabs of the last xprod16_tn_kernel
-        launch of each side), xprod_splits_err (slabs of the last fused xprod16_err_kernel launch), sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
+        launch of each side), xprod_splits_err (slabs of the last fused xprod16_err_kernel launch), a_stream_nt_from (first stage whose requests
+        for A were non-temporal in the last A-streaming cross product, -1 none yet), sweep_form_w / sweep_form_h (0 plain, 1 persistent -- strict fp64 --, 2 fp32 chain, -1 none yet), sweep_groups_w / sweep_groups_h,
         lee_lanes_w / lee_lanes_h and lee_regs_w / lee_regs_h (L and R of the last sweep_ls_kernel<R, L, 2> launch, -1 none yet),
         kl_form_w / kl_form_h (KL solver of the last half-step: 0 tile, 1 tile on its own starting states, 2 reg64, 3 streaming, -1 none yet),
         kl_pieces_w / kl_pieces_h and kl_cols_w / kl_cols_h (instantiated pieces per thread and columns per block of that launch as in
@@ -1152,6 +1155,15 @@ def debug_set_cus(cus: int):
 def debug_set_xprod_waves(waves: int):
     """Test hook: handles created from now on run the split-fp16 cross product with 8 or 10 wavefronts per block (0 = the plan decides)."""
     _check(load().nnlm_debug_set_xprod_waves(int(waves)))
+
+
+A_STREAM_NONE = 2**31 - 1  # debug_set_a_stream: no request for A is non-temporal
+
+
+def debug_set_a_stream(nt_from_stage: int):
+    """Test hook: handles created from now on issue the requests for A of the contraction stages >= nt_from_stage of the A-streaming cross
+    products non-temporally (0 = all of A, A_STREAM_NONE = none, -1 = the library's choice).  Results do not depend on it."""
+    _check(load().nnlm_debug_set_a_stream(int(nt_from_stage)))
 
 
 def xprod_plan(ldc, stages, k, cus, force_waves=0):

@@ -65,6 +65,13 @@ __device__ __forceinline__ void glds16_s(unsigned voff, unsigned long long sbase
 {
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
 }
+// The same request with the non-temporal cache policy: for bytes that ONE compute unit reads ONCE (the stream of A), never for an image every
+// block re-reads (the factor).  The A-streaming kernels choose between the two per stage: requests of the stages st >= nt_from_stage (the
+// global stage index, wave-uniform) take this form -- 0: all of A, INT_MAX: none.
+__device__ __forceinline__ void glds16_s_nt(unsigned voff, unsigned long long sbase, unsigned lds_dst)
+{
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" ::"v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
 
 // number of indices u in {wave, wave + 8, ...} below cnt
 __device__ static inline int strided_count(int wave, int cnt) { return (wave < cnt) ? (cnt - wave + XPROD_WAVES - 1) / XPROD_WAVES : 0; }
@@ -98,7 +105,8 @@ template <typename T, int NKQ, int KT = 0>
 __global__ __launch_bounds__(XPROD_THREADS) void xprod_tn_kernel(const T *__restrict__ A, int lda,
                                                                  const T *__restrict__ Yop, int ldy,
                                                                  double *__restrict__ Cx, int ldc, size_t slab_stride,
-                                                                 int stage_begin, int stage_end, int stages_per_split)
+                                                                 int stage_begin, int stage_end, int stages_per_split,
+                                                                 int nt_from_stage = 0x7fffffff) // (A requests of stages >= this: glds16_s_nt)
 {
     using M = Mfma<T>;
     using acc_t = typename M::acc_t;
@@ -142,9 +150,15 @@ __global__ __launch_bounds__(XPROD_THREADS) void xprod_tn_kernel(const T *__rest
     auto issue = [&](int st, unsigned char *buf) {
         const unsigned long long bA = (unsigned long long)st * XPROD_ROWB, bY = bA;
         const unsigned dst = lds0 + (unsigned)(buf - smem) + (unsigned)wave * 1024u;
+        if (st < nt_from_stage) { // (wave-uniform: a scalar branch around two copies of the request loop)
 #pragma unroll
-        for (int i = 0; i < XPROD_A_IMG_BYTES / 1024 / XPROD_WAVES; i++)
-            glds16_s(voffA, baseA + bA + (unsigned long long)i * 32ull * (unsigned long long)lda * sizeof(T), dst + (unsigned)i * 8192u);
+            for (int i = 0; i < XPROD_A_IMG_BYTES / 1024 / XPROD_WAVES; i++)
+                glds16_s(voffA, baseA + bA + (unsigned long long)i * 32ull * (unsigned long long)lda * sizeof(T), dst + (unsigned)i * 8192u);
+        } else {
+#pragma unroll
+            for (int i = 0; i < XPROD_A_IMG_BYTES / 1024 / XPROD_WAVES; i++)
+                glds16_s_nt(voffA, baseA + bA + (unsigned long long)i * 32ull * (unsigned long long)lda * sizeof(T), dst + (unsigned)i * 8192u);
+        }
 #pragma unroll
         for (int i = 0; i < (YI + XPROD_WAVES - 1) / XPROD_WAVES; i++)
             if (wave + XPROD_WAVES * i < YI)

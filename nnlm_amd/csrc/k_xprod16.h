@@ -61,7 +61,8 @@ __global__ __launch_bounds__(64 * NWV) void xprod16_tn_kernel(const uint32_t *__
                                                               const uint32_t *__restrict__ Y16, int ldy,   // ldy: elements per row
                                                               double *__restrict__ Cx, int ldc, int ncols, // ncols: columns of this launch, a multiple of 16
                                                               size_t slab_stride, int stage_begin, int stage_end, int stages_per_split,
-                                                              const int *__restrict__ scal_exp)
+                                                              const int *__restrict__ scal_exp,
+                                                              int nt_from_stage = 0x7fffffff) // (A requests of stages >= this: glds16_s_nt)
 {
     static_assert(NWV == 8 || NWV == 10, "8 or 10 wavefronts");
     static_assert(YP >= 1 && YP <= 4 * NKQ && YP > 4 * (NKQ - 1), "the loaded pieces reach into the last MFMA tile");
@@ -113,9 +114,14 @@ __global__ __launch_bounds__(64 * NWV) void xprod16_tn_kernel(const uint32_t *__
     auto issue = [&](int st, int bi) {
         const unsigned long long c0b = (unsigned long long)st * 256ull; // byte offset of the chunk
         const unsigned dst = lds0 + (unsigned)bi * (unsigned)BUF;
-        if (live) {
+        // A is read once, by this block alone: from stage nt_from_stage on its requests are non-temporal and leave the caches to what the
+        // step re-reads (the factor image below, the slabs); the comparison is wave-uniform, a scalar branch around two copies of the loop
+        if (live && st < nt_from_stage) {
 #pragma unroll
             for (int pc = 0; pc < 4; pc++) glds16_s(voffA[pc], baseA + c0b, dst + (unsigned)wave * 4096u + (unsigned)pc * 1024u);
+        } else if (live) {
+#pragma unroll
+            for (int pc = 0; pc < 4; pc++) glds16_s_nt(voffA[pc], baseA + c0b, dst + (unsigned)wave * 4096u + (unsigned)pc * 1024u);
         }
 #pragma unroll
         for (int i = 0; i < 2; i++)
@@ -335,7 +341,8 @@ __global__ __launch_bounds__(XPROD_THREADS) void xprod16_err_kernel(const uint32
                                                                     int stage_end, int stages_per_split, const int *__restrict__ scal_exp,
                                                                     const int *__restrict__ w_exp, int n_rows, int n_cols,
                                                                     double *__restrict__ partial, unsigned *__restrict__ zero_word,
-                                                                    const uint32_t *__restrict__ missT = nullptr, int wordsT = 0, int i_off = 0)
+                                                                    const uint32_t *__restrict__ missT = nullptr, int wordsT = 0, int i_off = 0,
+                                                                    int nt_from_stage = 0x7fffffff) // (A requests of stages >= this: glds16_s_nt)
 {
     constexpr int FL = XPROD_FLUSH_ELEMS / 64;
     constexpr int NC2 = NKQ > 2 ? 2 : 1;                                   // 32-wide chunks of kq that can be non-zero
@@ -380,8 +387,13 @@ __global__ __launch_bounds__(XPROD_THREADS) void xprod16_err_kernel(const uint32
         auto issue_a = [&](int st) {
             const unsigned long long c0b = (unsigned long long)st * 256ull;
             const unsigned dst = lds0 + (unsigned)((st - st0) % 3) * (unsigned)XPROD_A_IMG_BYTES + (unsigned)rg * 1024u;
+            if (st < nt_from_stage) { // (as in xprod16_tn_kernel: the stream of A non-temporal from that stage on, the factor images never)
 #pragma unroll
-            for (int i = 0; i < A_REQ; i++) glds16_s(voffA, baseA + c0b + (unsigned long long)i * 16ull * (unsigned long long)lda * 4ull, dst + (unsigned)i * 4096u);
+                for (int i = 0; i < A_REQ; i++) glds16_s(voffA, baseA + c0b + (unsigned long long)i * 16ull * (unsigned long long)lda * 4ull, dst + (unsigned)i * 4096u);
+            } else {
+#pragma unroll
+                for (int i = 0; i < A_REQ; i++) glds16_s_nt(voffA, baseA + c0b + (unsigned long long)i * 16ull * (unsigned long long)lda * 4ull, dst + (unsigned)i * 4096u);
+            }
         };
         auto issue_f = [&](int st) { // factor rows (Y, 64 columns j of the stage each) and factor columns (H, 64 kq each)
             const unsigned long long c0b = (unsigned long long)st * 256ull;

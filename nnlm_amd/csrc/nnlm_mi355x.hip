@@ -227,6 +227,8 @@ struct nnlm_handle {
     bool fuse_err = false;       // request: the next W half-step's cross product also evaluates the error sums of (W, H) now current
     int cus_device = 0;          // the device's CU count (cus may be the test hook's)
     int xprod_waves = 0;         // test hook (nnlm_debug_set_xprod_waves): block width of xprod16_tn_kernel, 0 = the plan decides
+    int a_stream = -1;           // test hook (nnlm_debug_set_a_stream): first stage whose A requests are non-temporal, -1 = the library's choice (a_stream_nt)
+    int a_stream_last = -1;      // what the last A-streaming cross-product launch was given (-1 = none yet)
     int xp_err_splits = 0;       // slabs of the last xprod16_err_kernel launch
     int xp_waves[2] = {0, 0}, xp_splits[2] = {0, 0}; // [which]: wavefronts per block and slabs of the last xprod16_tn_kernel launch
     int fused_nb = 0;            // answer: number of (sum of squares, KL) pairs it left in `partials` (0 = not fused)
@@ -415,6 +417,7 @@ extern "C" unsigned nnlm_trace_capacity(unsigned max_iter, unsigned trace)
 }
 
 static std::atomic<int> g_debug_cus{0}; // nnlm_debug_set_cus (test hook, read once per nnlm_create): compute units the launch policies of new handles count (0 = the device's)
+static std::atomic<int> g_debug_a_stream{-1}; // nnlm_debug_set_a_stream (test hook, read once per nnlm_create): first contraction stage whose requests for A are non-temporal, -1 = the library's choice (a_stream_nt)
 static std::atomic<int> g_debug_xprod_waves{0}; // nnlm_debug_set_xprod_waves (test hook, read once per nnlm_create): 8 | 10 wavefronts per block of xprod16_tn_kernel, 0 = the plan decides
 // Pinned bounce buffers of nnlm_set_matrix, kept between calls.  Pinning costs ~0.3 ms per MB: two fresh 64 MB buffers were ~40 ms of EVERY
 // upload (half of config 2's 78 ms, most of the 53 ms an 80 MB matrix took -- scripts/gpu_call_breakdown.py).  One pair per process, taken
@@ -513,6 +516,13 @@ extern "C" int nnlm_debug_set_xprod_waves(int waves)
     return NNLM_OK;
 }
 
+extern "C" int nnlm_debug_set_a_stream(int nt_from_stage)
+{
+    if (nt_from_stage < -1) return fail(nullptr, NNLM_ERR_ARG, "nnlm_debug_set_a_stream: %d (-1, or a stage >= 0)", nt_from_stage);
+    g_debug_a_stream = nt_from_stage;
+    return NNLM_OK;
+}
+
 extern "C" int nnlm_debug_set_cus(int cus)
 {
     if (cus < 0) return fail(nullptr, NNLM_ERR_ARG, "nnlm_debug_set_cus: %d", cus);
@@ -578,6 +588,7 @@ extern "C" int nnlm_create(nnlm_handle **out, int device, int precision)
         h->cus = h->cus_device = res.cus;
         if (const int dc = g_debug_cus.load(std::memory_order_relaxed); dc > 0) h->cus = dc;
         h->xprod_waves = g_debug_xprod_waves.load(std::memory_order_relaxed);
+        h->a_stream = g_debug_a_stream.load(std::memory_order_relaxed);
         h->stream = res.stream, h->stream_e = res.stream_e;
         h->ev_hdone = res.ev_hdone, h->ev_err = res.ev_err, h->ev_xdone = res.ev_xdone;
         h->scal = res.scal, h->sweeps = res.sweeps, h->host_res = res.host_res, h->sweeps_tmp = res.sweeps_tmp, h->sweepq_img = res.sweepq_img;
@@ -608,6 +619,7 @@ extern "C" int nnlm_create(nnlm_handle **out, int device, int precision)
     h->cus_device = h->cus;
     if (const int dc = g_debug_cus.load(std::memory_order_relaxed); dc > 0) h->cus = dc; // test hook (nnlm_debug_set_cus): the sweep's launch policy at small sizes
     h->xprod_waves = g_debug_xprod_waves.load(std::memory_order_relaxed);
+    h->a_stream = g_debug_a_stream.load(std::memory_order_relaxed);
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&h->stream_e, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_hdone, hipEventDisableTiming) != hipSuccess ||
@@ -2390,6 +2402,26 @@ static void with_nkq(int nkq, F &&f)
     }
 }
 
+// Cache policy of the stream of A in the three A-streaming cross products (xprod16_tn_kernel, xprod16_err_kernel, xprod_tn_kernel): the
+// requests of the contraction stages >= this one are non-temporal (glds16_s_nt, k_xprod.h) -- 0: all of A, INT_MAX: none, R in between:
+// the first 64 R contraction elements of every column keep the default policy.  Measured at config 2 (DESIGN.md section 4.1,
+// profiles/a_stream_policy_ab.md).  A kernel class keeps the policy only where its own launches were measurably shorter with it; the
+// others are launched with INT_MAX: the fused kernel (bound by its error wavefronts, not by the stream) and the strict kernel (bound by
+// the fp64 matrix pipe) gained nothing.  A pass whose bytes, together with the other half-step's pass over the other copy, fit the 256 MB
+// Infinity Cache finds them there in the next iteration and keeps the default policy too (4000 x 2000: 2 % slower non-temporally; 8000 x
+// 4000, 2 x 131 MB, no longer).  nnlm_debug_set_a_stream overrides all of it per handle.
+static constexpr int A_STREAM_NT_FROM = 16;
+static constexpr size_t A_STREAM_MIN_PASS_BYTES = (size_t)128 << 20;
+enum AStreamClass { A_STREAM_PLAIN = 0, A_STREAM_FUSED = 1, A_STREAM_STRICT = 2 }; // xprod16_tn_kernel, xprod16_err_kernel, xprod_tn_kernel
+static constexpr bool A_STREAM_CLASS_NT[3] = {true, false, false};
+static int a_stream_nt(nnlm_handle *h, AStreamClass c, const HalfPlan &p)
+{
+    // (a stage is 256 bytes of every column in all three kernels)
+    const size_t pass_bytes = (size_t)p.tiles_x * 16 * p.nwv * (size_t)(p.stage_end - p.stage_begin) * XPROD_ROWB;
+    const int own = (A_STREAM_CLASS_NT[c] && pass_bytes > A_STREAM_MIN_PASS_BYTES) ? A_STREAM_NT_FROM : INT_MAX;
+    return h->a_stream_last = (h->a_stream >= 0 ? h->a_stream : own);
+}
+
 // xprod_tn_kernel (k_xprod.h) over rows [0, 16 NKQ (+ KT tail rows)) of the fixed factor Y into the slabs at C (the rank > 64 loops:
 // one launch per 64 rows of Y and C)
 template <typename T, int NKQ, int KT = 0>
@@ -2399,7 +2431,7 @@ static void launch_xprod_tn(nnlm_handle *h, const T *Amat, int lda, const T *Y, 
     const int lds = xprod_tn_lds_bytes(16 * (NKQ + (KT > 0 ? 1 : 0)));
     set_dyn_lds((const void *)xprod_tn_kernel<T, NKQ, KT>, lds, "xprod_tn_kernel");
     xprod_tn_kernel<T, NKQ, KT><<<grid, XPROD_THREADS, lds, h->stream>>>(Amat + (size_t)p.col_off * lda, lda, Y, ldy, C + p.col_off, ldc, slab_stride,
-                                                                          p.stage_begin, p.stage_end, p.sps);
+                                                                          p.stage_begin, p.stage_end, p.sps, a_stream_nt(h, A_STREAM_STRICT, p));
 }
 
 // Strict mode, rank <= 64 (the masters are the operands: Wop aliases W64).  MFMA tiles / VALU tail rows for rank k: k = 16*NKQ + rem;
@@ -2430,7 +2462,7 @@ static void launch_xprod16_nwy(nnlm_handle *h, const Side &s, const HalfPlan &p,
     set_dyn_lds((const void *)xprod16_tn_kernel<NKQ, NWV, YP>, lds, "xprod16_tn_kernel");
     xprod16_tn_kernel<NKQ, NWV, YP><<<grid, 64 * NWV, lds, h->stream>>>(s.A16 + (size_t)p.col_off * s.ldy, s.ldy, h->Y16 + (size_t)q0 * s.ldy, s.ldy,
                                                                         h->Cx + (size_t)q0 * s.ldc + p.col_off, s.ldc, p.cols, s.slab_stride,
-                                                                        p.stage_begin, p.stage_end, p.sps, h->scal_exp);
+                                                                        p.stage_begin, p.stage_end, p.sps, h->scal_exp, a_stream_nt(h, A_STREAM_PLAIN, p));
 }
 // The instantiations: all 4 NKQ factor pieces in both widths for NKQ <= 3; NKQ = 4 with all 16 pieces (8 wavefronts only: the 160-column
 // ring does not fit) and with the 13 pieces of k = 49 .. 52 in both widths (rows >= k of the split copy are zero: factor16_kernel).
@@ -2494,13 +2526,13 @@ static void launch_xprod16_err_m(nnlm_handle *h, const HalfPlan &p)
         xprod16_err_kernel<NKQ, true><<<grid, XPROD_THREADS, lds, h->stream>>>(h->A16T, h->mpad, h->Y16, h->mpad, h->H16c, h->W16c, h->Cx, h->npad,
                                                                                (size_t)16 * NKQ * h->npad, p.stage_begin, p.stage_end, p.sps, h->scal_exp,
                                                                                h->scal_exp + 2, h->n, h->m, h->partials, h->err_zero_word, h->missT,
-                                                                               h->mpad / 32, p.col_off);
+                                                                               h->mpad / 32, p.col_off, a_stream_nt(h, A_STREAM_FUSED, p));
     } else {
         set_dyn_lds((const void *)xprod16_err_kernel<NKQ, false>, lds, "xprod16_err_kernel");
         xprod16_err_kernel<NKQ, false><<<grid, XPROD_THREADS, lds, h->stream>>>(h->A16T, h->mpad, h->Y16, h->mpad, h->H16c, h->W16c, h->Cx, h->npad,
                                                                                 (size_t)16 * NKQ * h->npad, p.stage_begin, p.stage_end, p.sps, h->scal_exp,
                                                                                 h->scal_exp + 2, h->n, h->m, h->partials, h->err_zero_word, nullptr, 0,
-                                                                                p.col_off);
+                                                                                p.col_off, a_stream_nt(h, A_STREAM_FUSED, p));
     }
     h->err_zero_word = nullptr;
     h->fused_nb = p.tiles_x * p.S;
@@ -4235,6 +4267,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "xprod_splits_w") == 0) *value = h->xp_splits[0];
     else if (strcmp(key, "xprod_splits_h") == 0) *value = h->xp_splits[1];
     else if (strcmp(key, "xprod_splits_err") == 0) *value = h->xp_err_splits; // (xprod16_err_kernel: the W half-step of a trace iteration)
+    else if (strcmp(key, "a_stream_nt_from") == 0) *value = h->a_stream_last; // (last A-streaming cross product, any of the three kernels; -1 = none yet)
     else if (strcmp(key, "sweep_form_w") == 0) *value = h->sweep_form[0]; // (0 / 1 strict kernels, 2 k_sweep_f.h, 3 k_sweep_r.h)
     else if (strcmp(key, "sweep_form_h") == 0) *value = h->sweep_form[1];
     else if (strcmp(key, "sweep_groups_w") == 0) *value = h->sweep_groups[0];

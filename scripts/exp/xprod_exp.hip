@@ -3,11 +3,13 @@
 // launches for {8, 10} wavefronts per block x {all 16, the 13 needed at k = 50} factor pieces, each at the slab counts that fill the
 // device best, and print the weight of a factor byte against a byte of A that the four times imply (XPLAN_Y_WEIGHT in nnlm_mi355x.hip).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -DXPROD_BLOCKS scripts/exp/xprod_exp.hip -o scripts/exp/xprod_blocks_exp
+// `xprod_blocks_exp loop`: the shipped plans on two alternating split copies, one row per cache policy of the stream of A (loop_mode below).
 #ifdef XPROD_BLOCKS
 #include "../../nnlm_amd/csrc/k_xprod16.h"
 #include <cstdio>
 #include <cmath>
 #include <algorithm>
+#include <string>
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 struct Times { float mean, sd, mn; };
@@ -35,8 +37,61 @@ template <int NWV, int YP> static Times run16b(const uint32_t *A, int lda, const
     for (float x : t) v += (x - m) * (x - m);
     return {(float)m, (float)std::sqrt(v / (reps - 1)), *std::min_element(t.begin(), t.end())};
 }
-int main()
+// `xprod_blocks_exp loop`: the cache state of the iteration loop instead of a single-buffer replay.  Two separate split copies (818 MB each,
+// as A16 and A16T); the benchmark's H launch (160-column blocks, 4 slabs) runs on one and its W launch (160-column blocks, 2 slabs) on the
+// other, alternately, 30 timed pairs after 3 warm-up pairs, once per cache policy of the stream of A: nt_from_stage = INT_MAX (default
+// policy), 0 (all of A non-temporal) and R in between (the stages < R of slab 0 keep the default policy: 256 R bytes of every column).
+static int loop_mode()
 {
+    const int npad = 20224, mpad = 10112, pairs = 30, warm = 3;
+    const size_t abytes = (size_t)npad * mpad * 4;
+    uint32_t *A[2], *Y; double *Cx; int *sc;
+    CK(hipMalloc(&A[0], abytes)); CK(hipMalloc(&A[1], abytes)); CK(hipMalloc(&Y, (size_t)64 * npad * 4)); CK(hipMalloc(&Cx, (size_t)4 * 64 * npad * 8));
+    CK(hipMemset(A[0], 0x3c, abytes)); CK(hipMemset(A[1], 0x3c, abytes)); CK(hipMemset(Y, 0x3c, (size_t)64 * npad * 4));
+    CK(hipMalloc(&sc, 8)); CK(hipMemset(sc, 0, 8));
+    constexpr int NWV = 10, YP = 13;
+    const int lds = xprod16_lds_bytes(NWV, 4, YP);
+    CK(hipFuncSetAttribute((const void *)xprod16_tn_kernel<4, NWV, YP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    struct { const char *name; int len, cols, S; } L[2] = {{"H half-step (10112 cols x 316 stages, S = 4)", npad, mpad, 4}, {"W half-step (20224 cols x 158 stages, S = 2)", mpad, npad, 2}};
+    auto launch = [&](int l, int nt_from) {
+        const int stages = L[l].len / 64, sps = (stages + L[l].S - 1) / L[l].S, tiles = (L[l].cols + 16 * NWV - 1) / (16 * NWV);
+        xprod16_tn_kernel<4, NWV, YP><<<dim3(tiles, (stages + sps - 1) / sps), 64 * NWV, lds>>>(A[l], L[l].len, Y, L[l].len, Cx, L[l].cols, L[l].cols, (size_t)64 * L[l].cols, 0,
+                                                                                             stages, sps, sc, nt_from);
+    };
+    const double gb = (double)abytes / 1e9;
+    std::vector<hipEvent_t> ev(2 * pairs + 1);
+    for (auto &evt : ev) CK(hipEventCreate(&evt));
+    printf("| launch | nt_from_stage | mean ms | sd | min ms | TB/s of A (mean) |\n|---|---|---|---|---|---|\n");
+    for (int nt_from : {0x7fffffff, 0, 4, 8, 12, 16, 32, 64}) {
+        for (int i = 0; i < warm; i++) launch(0, nt_from), launch(1, nt_from);
+        CK(hipDeviceSynchronize());
+        CK(hipEventRecord(ev[0]));
+        for (int i = 0; i < pairs; i++) {
+            launch(0, nt_from);
+            CK(hipEventRecord(ev[2 * i + 1]));
+            launch(1, nt_from);
+            CK(hipEventRecord(ev[2 * i + 2]));
+        }
+        CK(hipEventSynchronize(ev[2 * pairs]));
+        CK(hipGetLastError());
+        for (int l = 0; l < 2; l++) {
+            std::vector<float> t(pairs);
+            for (int i = 0; i < pairs; i++) CK(hipEventElapsedTime(&t[i], ev[2 * i + l], ev[2 * i + l + 1]));
+            double m = 0, v = 0;
+            for (float x : t) m += x;
+            m /= pairs;
+            for (float x : t) v += (x - m) * (x - m);
+            char nm[16];
+            if (nt_from == 0x7fffffff) snprintf(nm, sizeof nm, "INT_MAX");
+            else snprintf(nm, sizeof nm, "%d", nt_from);
+            printf("| %s | %s | %.4f | %.4f | %.4f | %.2f |\n", L[l].name, nm, m, std::sqrt(v / (pairs - 1)), *std::min_element(t.begin(), t.end()), gb / m);
+        }
+    }
+    return 0;
+}
+int main(int argc, char **argv)
+{
+    if (argc > 1 && std::string(argv[1]) == "loop") return loop_mode();
     const int npad = 20224, mpad = 10112, reps = 30;
     uint32_t *A, *Y; double *Cx; int *sc;
     CK(hipMalloc(&A, (size_t)npad * mpad * 4)); CK(hipMalloc(&Y, (size_t)64 * npad * 4)); CK(hipMalloc(&Cx, (size_t)16 * 64 * npad * 8));
