@@ -427,6 +427,50 @@ int nnlm_c_nnmf_holdout_batch(const double *A, int n, int m, const long long *co
                               double *target_error, double *average_epoch, int *n_trace, unsigned *n_iteration, int *warned,
                               double *holdout_mse, double *holdout_mkl, const nnlm_callbacks *cb);
 
+/* ------------------------------------------------------------------------------------------
+ * Truncated SVD of the resident matrix and the NNDSVD start (Boutsidis & Gallopoulos 2008) made from it: a deterministic, data-driven
+ * start for W and H, and a decomposition that is a product of its own (scree, rank-k baseline).  DESIGN section 4.22.
+ * Randomised subspace iteration with a sketch of width l and `power_iters` power iterations, 2 power_iters + 2 passes over A through the
+ * cross products of the half-steps (split-fp16 in NNLM_PREC_F32, strict fp64 in NNLM_PREC_F64, the SpMM on a sparse handle, one launch
+ * per 64 rows beyond l = 64): Y = omega A^T, Q = orth(Y); power_iters times Z = orth(Q A), Q = orth(Z A^T); B = Q A, B B^T = V L V^T,
+ * sigma = sqrt(L) descending, U = V^T Q, Vt = Sigma^-1 V^T B.  orth is Gram-based and runs twice: G = X X^T = E L E^T (cyclic Jacobi in
+ * fp64 on the host, fixed sweep order), X <- diag(L_i^-1/2 where L_i > 1e-12 L_max, else 0) E^T X: a direction that is dropped (every A of
+ * rank below l drops some) becomes a zero row and stays one; in the last step such a direction has sigma = 0 and a zero row of Vt.
+ * The library draws nothing: omega (l x m, laid out as nnlm_set_factors takes H: column-major, l rows) comes from the caller.  The sign
+ * of a triplet is unspecified but joint for u_j and v_j.  No atomics on data: two calls with one omega give identical bits.
+ * ---------------------------------------------------------------------------------------- */
+/* Needs a matrix on the handle.  Leaves the decomposition resident (U [LP][npad], Vt [LP][mpad] in fp64 on the device, sigma on the host)
+ * until the next matrix, and leaves the handle WITHOUT factors, as after nnlm_set_matrix (the factor buffers were its workspace).
+ * Supported: a dense finite A however it arrived, and a sparse A whose absent entries are zeros (all four doors and the device ingest
+ * that leaves those handles), both arithmetic modes.  NNLM_ERR_UNSUPPORTED, named in the message: a matrix with missing entries (NaN
+ * upload, a non-empty hold-out set, the absent = missing doors), a handle with a communicator.  NNLM_ERR_ARG: l outside 1 .. min(n, m), a
+ * NULL or non-finite omega.  No width is refused: the rotation kernel narrows its column tile as l grows (32 columns up to l = 512, 16 up
+ * to 848, 8 up to 1280) and works out of place beyond; the host's Jacobi, O(l^3) per sweep, is what bounds l in practice.
+ * nnlm_get_info: "svd_width" (l, -1 none), "svd_kept" (directions the last orth kept), "svd_rotate_form" (column tile of the last
+ * rotation: 32, 16 or 8; 0 out of place; -1 none yet), "svd_ms_cross" / "svd_ms_gram" / "svd_ms_rotate" / "svd_ms_eig" / "svd_ms_wait" /
+ * "svd_ms_setup" / "svd_ms_total" (host milliseconds of the last call by phase: cross products, Grams, rotations, host
+ * eigendecompositions, waits and transfers, setting and freeing the rank-l factor buffers, the whole call; with nnlm_profile_enable
+ * every phase waits for its kernels, so the first three hold their device time). */
+int nnlm_svd(nnlm_handle *h, unsigned l, unsigned power_iters, const double *omega);
+/* Test hook: the form of the rotations of nnlm_svd calls from now on (process-global, as the other nnlm_debug_* settings): 32, 16 or 8 =
+ * that column tile wherever it fits the width, 0 = out of place, -1 = the width decides.  The forms give identical bits. */
+int nnlm_debug_set_svd_rotate(int form);
+/* The first k <= l triplets: sigma [k], U n x k, Vt k x m (column-major); any output may be NULL. */
+int nnlm_get_svd(nnlm_handle *h, unsigned k, double *sigma, double *U, double *Vt);
+/* NNDSVD from the first k <= l triplets; leaves exactly the state nnlm_set_factors(h, k, W, H, NULL, NULL) leaves for these W, H.
+ * Component 0: sqrt(sigma_0) |u_0|, sqrt(sigma_0) |v_0|.  Component j >= 1: with the positive and negative parts of u_j, v_j and
+ * p = |u+| |v+|, g = |u-| |v-|, the positive pair if p >= g, else the negative pair; W[:, j] = sqrt(sigma_j t) part_u / |part_u|, H[j, :]
+ * likewise, t the chosen product; sigma_j t = 0 gives a zero column and row.  variant 0 (nndsvd) leaves the zeros: fine for the SCD
+ * methods, but Lee's multiplicative updates (methods 2 and 4) keep a zero forever and KL loss divides by W H.  variant 1 (nndsvda)
+ * replaces every exact zero of W and H by mean(A) over all n m entries (absent entries of a sparse A count as zeros), summed in fp64 in
+ * a fixed order from the resident values -- in NNLM_PREC_F32 those are the fp32 roundings of A.  NNLM_ERR_ARG: no decomposition on the
+ * handle, k = 0 or k > l, variant outside {0, 1}. */
+int nnlm_set_factors_nndsvd(nnlm_handle *h, unsigned k, int variant);
+/* nnlm_set_factors_batch with member b started from the NNDSVD of the first k[b] triplets: bit for bit the first k[b] components of
+ * nnlm_set_factors_nndsvd at the largest rank (component j depends on triplet j alone), so one decomposition serves a rank sweep.
+ * Needs max k[b] <= l (NNLM_ERR_ARG); every rule of nnlm_set_factors_batch holds (rank sum <= 64, the handle's own batch refusals). */
+int nnlm_set_factors_nndsvd_batch(nnlm_handle *h, unsigned B, const unsigned *k, int variant);
+
 /* Per-kernel device timing (HIP events on the handle's stream) for bench.py's roofline block.
  * names: "xprod_h" (A-streaming W^T A), "xprod_w" (A H^T), "xprod_w_err" (the same with the fused error sums), "gram", "sweep_h",
  * "sweep_w", "errors" (a separate pass over A), "err_reduce" (reduction of the fused error sums), "allgather", "allreduce", "unpack";

@@ -44,7 +44,9 @@ EXPORTS = [
     "nnlm_set_matrix_csc_kl_batch", "nnlm_c_nnmf_csc_kl_batch",
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
     "nnlm_set_matrix_sparse_device", "nnlm_debug_sparse_resident",
+    "nnlm_svd", "nnlm_get_svd", "nnlm_set_factors_nndsvd", "nnlm_set_factors_nndsvd_batch", "nnlm_debug_set_svd_rotate",
 ]
+NNDSVD_VARIANTS = {"nndsvd": 0, "nndsvda": 1}
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
 BY = {"column": 0, "row": 1}
 
@@ -233,6 +235,11 @@ def load():
     lib.nnlm_debug_sparse_resident.argtypes = [vp, C.c_int, lp, ip, dp]
     lib.nnlm_predict_entries.restype = C.c_int
     lib.nnlm_predict_entries.argtypes = [vp, C.c_longlong, ip, ip, dp]
+    lib.nnlm_svd.argtypes = [vp, C.c_uint, C.c_uint, dp]
+    lib.nnlm_get_svd.argtypes = [vp, C.c_uint, dp, dp, dp]
+    lib.nnlm_debug_set_svd_rotate.argtypes = [C.c_int]
+    lib.nnlm_set_factors_nndsvd.argtypes = [vp, C.c_uint, C.c_int]
+    lib.nnlm_set_factors_nndsvd_batch.argtypes = [vp, C.c_uint, up, C.c_int]
     lib.nnlm_top_n.restype = C.c_int
     lib.nnlm_top_n.argtypes = [vp, C.c_int, C.c_int, ip, C.c_longlong, C.c_int, ip, dp]
     _lib = lib
@@ -1059,6 +1066,37 @@ class Handle:
                                           _ip(warned), C.byref(callbacks) if callbacks is not None else None))
         return _batch_traces(self.ks, cap, mse, mkl, terr, ep, n_trace, n_it, warned)
 
+    def svd(self, l, power_iters, omega):
+        """Truncated SVD of the resident matrix by randomised subspace iteration (nnlm_svd): sketch width l, omega l x m supplied by the
+        caller (the library draws nothing).  The decomposition stays on the handle; the handle is left without factors."""
+        l = int(l)
+        om = _f64(omega)
+        if l > 0 and om.size != l * self.m:
+            raise NnlmError(ERR_ARG, f"omega has {om.size} entries, a sketch of width {l} needs {l} x {self.m}")
+        self._ck(self._lib.nnlm_svd(self._h, l, int(power_iters), _dp(om)))
+        self.k, self._batch = 0, False
+
+    def get_svd(self, k):
+        """(U n x k, sigma k, Vt k x m) of the resident decomposition."""
+        k = int(k)
+        s, U, Vt = np.zeros(k), np.zeros((self.n, k), order="F"), np.zeros((k, self.m), order="F")
+        self._ck(self._lib.nnlm_get_svd(self._h, k, _dp(s), _dp(U), _dp(Vt)))
+        return np.ascontiguousarray(U), s, np.ascontiguousarray(Vt)
+
+    def set_factors_nndsvd(self, k, variant="nndsvd"):
+        """NNDSVD start from the first k resident triplets; variant "nndsvd" (zeros stay: not for Lee's updates or KL loss) or "nndsvda"
+        (zeros filled with mean(A)), or the C code 0 / 1."""
+        v = NNDSVD_VARIANTS[variant] if isinstance(variant, str) else int(variant)
+        self._ck(self._lib.nnlm_set_factors_nndsvd(self._h, int(k), v))
+        self.k, self._batch = int(k), False
+
+    def set_factors_nndsvd_batch(self, ks, variant="nndsvd"):
+        """Batched factorisation whose member b starts from the NNDSVD of the first ks[b] resident triplets."""
+        ks = _batch_ranks(ks)
+        v = NNDSVD_VARIANTS[variant] if isinstance(variant, str) else int(variant)
+        self._ck(self._lib.nnlm_set_factors_nndsvd_batch(self._h, len(ks), ks.ctypes.data_as(C.POINTER(C.c_uint)), v))
+        self.k, self.ks, self._batch = int(ks.sum()), [int(k) for k in ks], True
+
     def take_sweeps(self, reset=True):
         v = C.c_longlong(0)
         self._ck(self._lib.nnlm_take_sweeps(self._h, C.byref(v), int(reset)))
@@ -1105,7 +1143,10 @@ class Handle:
         sp_ingest_check_share / sp_ingest_sort_tile (stored entries per workgroup of the entry check / of a radix pass of
         set_matrix_sparse_device),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
-        column / a row of a dense matrix)."""
+        column / a row of a dense matrix),
+        svd_width / svd_kept (sketch width of the resident decomposition and directions its last orth kept, -1 none), svd_rotate_form
+        (column tile of its last rotation, 0 out of place), svd_ms_cross / svd_ms_gram / svd_ms_rotate / svd_ms_eig / svd_ms_wait /
+        svd_ms_setup / svd_ms_total (host milliseconds of the last svd() by phase)."""
         v = C.c_double(0)
         self._ck(self._lib.nnlm_get_info(self._h, key.encode(), C.byref(v)))
         return v.value
@@ -1150,6 +1191,11 @@ def debug_exchange(handles, which, stage):
 def debug_set_cus(cus: int):
     """Test hook: handles created from now on plan their launches for `cus` compute units (0 = the device's own count)."""
     _check(load().nnlm_debug_set_cus(int(cus)))
+
+
+def debug_set_svd_rotate(form: int):
+    """Test hook: form of the rotations of Handle.svd from now on: 32, 16, 8 (column tile, where it fits), 0 (out of place), -1 (the width decides)."""
+    _check(load().nnlm_debug_set_svd_rotate(int(form)))
 
 
 def debug_set_xprod_waves(waves: int):

@@ -537,10 +537,218 @@ def _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, m
     return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
 
 
+# ------------------------------------------------------------------------------------------------
+# truncated SVD of A and the NNDSVD start
+# ------------------------------------------------------------------------------------------------
+SVD_INITS = ("nndsvd", "nndsvda")
+
+
+def _svd_init_arg(init, who):
+    """A string init names an NNDSVD variant."""
+    if init not in SVD_INITS:
+        raise NnlmStop("%s: init = %r is not a start this library knows; a string init is one of %s." % (who, init, ", ".join(map(repr, SVD_INITS))))
+    return init
+
+
+def _svd_width(k, oversample, power_iters, n, m, who):
+    try:
+        k, oversample, power_iters = int(k), int(oversample), int(power_iters)
+    except (TypeError, ValueError):
+        raise NnlmStop("%s: k, the oversampling and the power iterations must be integers" % who) from None
+    if k < 1 or k > min(n, m):
+        raise NnlmStop("%s: k = %d outside 1 .. min(n, m) = %d: a matrix has no more singular triplets than that." % (who, k, min(n, m)))
+    if oversample < 0 or power_iters < 0:
+        raise NnlmStop("%s: the oversampling and the power iterations must be >= 0" % who)
+    return min(k + oversample, n, m), power_iters
+
+
+def _svd_omega(l, m, g):
+    """The l x m sketch matrix, uniform on (-1, 1), filled column by column as reformat_input fills H."""
+    return (2.0 * g.random(l * m) - 1.0).reshape((l, m), order="F")
+
+
+def _svd_refuse_missing(what, who):
+    raise NnlmStop("%s: %s; the truncated SVD and the NNDSVD start need a matrix without missing entries." % (who, what))
+
+
+def _svd_ingest(A, h, who, loss="mse", kl=False, batch=False, parts=None):
+    """A of any supported kind into the handle h, absent entries of a sparse A zeros -> the `matrix` of _prepare_nnmf."""
+    if parts is not None:
+        mat = _sparse_device_matrix(parts, h, "zero", kl, batch)
+    elif _lib.is_device_array(A):
+        mat = _device_matrix(A, h)
+        if h.matrix_info()["any_missing"]:
+            _svd_refuse_missing("A has non-finite (NA, NaN or +-Inf) entries", who)
+    elif is_sparse(A):
+        c = _sparse_input(A, "A", loss, sparse_kl=kl)
+        mat = dict(A=c, n=c.shape[0], m=c.shape[1], min_k=min(c.shape))
+        door = {(False, False): h.set_matrix_csc, (False, True): h.set_matrix_csc_batch, (True, False): h.set_matrix_csc_kl,
+                (True, True): h.set_matrix_csc_kl_batch}[(bool(kl), bool(batch))]
+        door(c.indptr, c.indices, c.data, c.shape)
+    else:
+        mat = _nnmf_matrix(A, loss)
+        if not np.isfinite(mat["A"]).all():
+            _svd_refuse_missing("A has non-finite (NA, NaN or +-Inf) entries", who)
+        h.set_matrix(mat["A"])
+    return mat
+
+
+def _precision_arg(precision):
+    if precision is None:
+        return _env_precision()
+    table = {"f32": _lib.PREC_F32, "fp32": _lib.PREC_F32, "f64": _lib.PREC_F64, "fp64": _lib.PREC_F64,
+             _lib.PREC_F32: _lib.PREC_F32, _lib.PREC_F64: _lib.PREC_F64}
+    if precision not in table:
+        raise NnlmStop("precision must be None (NNLM_PRECISION decides), 'f32' or 'f64' (got %r)" % (precision,))
+    return table[precision]
+
+
+def truncated_svd(A, k, oversample=10, power_iters=2, rng=None, precision=None):
+    """The leading k singular triplets of A on the GPU -> (U n x k, s descending, Vt k x m), by randomised subspace iteration with a
+    sketch of width l = min(k + oversample, n, m) and ``power_iters`` power iterations: 2 power_iters + 2 passes over A through the
+    library's cross products, l x l eigendecompositions on the host.  The sketch matrix is 2 rng.random(l m) - 1; nothing else is
+    random, and two calls with equal ``rng`` give identical bits.  The sign of a triplet is unspecified (joint for u_j and v_j).
+
+    ``A``: a host array, a sparse object with tocsc() (absent entries are zeros), a tensor in device memory or a sparse CSC / CSR tensor
+    of the GPU.  ``precision``: "f32" (split-fp16 cross products, about 22 bits of A) or "f64"; None: what NNLM_PRECISION names.
+    Use: a scree of the singular values beside nnmf_cv; the error of the rank-k SVD, sum(s[k:]**2), as the floor for any rank-k model."""
+    who = "truncated_svd"
+    parts = _sparse_device_parts(A, who)
+    prec = _precision_arg(precision)
+    on_device = parts is not None or _lib.is_device_array(A)
+    if not on_device and not is_sparse(A):
+        shape = np.shape(A)
+        if len(shape) != 2:
+            raise NnlmStop("A must be a matrix")
+        _svd_width(k, oversample, power_iters, shape[0], shape[1], who)
+        if not np.isfinite(np.asarray(A, dtype=np.float64)).all():
+            _svd_refuse_missing("A has non-finite (NA, NaN or +-Inf) entries", who)
+    g = rng or np.random.default_rng()
+    with _lib.Handle(_device_index(A) if on_device else int(os.environ.get("NNLM_DEVICE", "0") or 0), prec) as h:
+        mat = _svd_ingest(A, h, who, parts=parts)
+        l, q = _svd_width(k, oversample, power_iters, mat["n"], mat["m"], who)
+        h.svd(l, q, _svd_omega(l, mat["m"], g))
+        return h.get_svd(int(k))
+
+
+def _svd_init_refusals(who, init, loss, mask, absent, sparse_A, sparse_kl):
+    """What a string init cannot be combined with, named before any device is touched."""
+    if not _is_empty(mask) and any(not _is_empty(v) for v in dict(mask).values()):
+        raise NnlmStop("%s: init = %r cannot be combined with masks: the start is made from the SVD of A, not from masked blocks." % (who, init))
+    if absent == "missing":
+        raise NnlmStop("%s: init = %r needs absent = 'zero': a matrix whose absent entries are missing has no SVD here." % (who, init))
+    if loss == "mkl" and not sparse_A:
+        raise NnlmStop("%s: init = %r with loss = 'mkl' on a dense A is not supported; use loss = 'mse', or a sparse count matrix with "
+                       "sparse_kl and init = 'nndsvda'." % (who, init))
+    if loss == "mkl" and sparse_A and not sparse_kl:
+        raise NnlmStop("Sparse A is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'.")
+    if loss == "mkl" and init == "nndsvd":
+        raise NnlmStop("%s: init = 'nndsvd' leaves exact zeros in W and H, which KL loss cannot start from; use init = 'nndsvda'." % who)
+
+
+def _nnmf_svd_init(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
+                   show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts, oversample, power_iters):
+    """nnmf(init = "nndsvd" | "nndsvda"): ingest, svd, set_factors_nndsvd, run and export on one Handle, for every kind of A."""
+    who = "nnmf"
+    init = _svd_init_arg(init, who)
+    loss = _match_arg(loss, ("mse", "mkl"), "loss")
+    on_device = parts is not None or _lib.is_device_array(A)
+    sparse_A = parts is not None or is_sparse(A)
+    absent = _match_arg(absent, ("zero", "missing"), "absent") if sparse_A else "zero"
+    _svd_init_refusals(who, init, loss, mask, absent, sparse_A, sparse_kl)
+    kl = bool(sparse_kl) and loss == "mkl"
+    if not on_device and not sparse_A and np.ndim(A) == 2 and not np.isfinite(np.asarray(A, dtype=np.float64)).all():
+        _svd_refuse_missing("A has non-finite (NA, NaN or +-Inf) entries", who)
+    torch = _tensor_lib(A)
+    g = rng or np.random.default_rng()
+    t0 = time.perf_counter()
+    with _lib.Handle(_device_index(A) if on_device else int(os.environ.get("NNLM_DEVICE", "0") or 0), _env_precision()) as h:
+        mat = _svd_ingest(A, h, who, loss, kl, False, parts)
+        n, m = mat["n"], mat["m"]
+        l, q = _svd_width(k, oversample, power_iters, n, m, who)
+        omega = _svd_omega(l, m, g)  # (drawn before anything else consumes the generator)
+        args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, None, None, W_norm, check_k, max_iter, rel_tol, n_threads, trace,
+                                     verbose, show_warning, inner_max_iter, inner_rel_tol, np.random.default_rng(0), matrix=mat, absent="zero",
+                                     sparse_kl=kl)
+        ctx["init"] = init
+        ctx["sparse_kl"] = kl
+        K = args[1]
+        cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
+        h.svd(l, q, omega)
+        h.set_factors_nndsvd(K, init)
+        out = h.run(*args[6:10], *args[11:], callbacks=cb)
+        if torch is not None:
+            Wo = torch.empty((n, K), dtype=torch.float64, device=A.device)
+            Ho = torch.empty((K, m), dtype=torch.float64, device=A.device)
+            h.get_factors_device(Wo, Ho)
+            out["W"], out["H"] = Wo, Ho
+        else:
+            out["W"], out["H"] = h.get_factors()
+    return finish_nnmf(out, ctx, run_time=time.perf_counter() - t0)
+
+
+def _nnmf_batch_svd_init(A, ks, nrun, init, g, opts, unsupported, missing_door, kl_door, parts):
+    """nnmf_batch(init = "nndsvd" | "nndsvda"): ONE decomposition at the top rank for all members (component j of the start depends on
+    triplet j alone), then the batch on the same handle."""
+    who = "nnmf_batch"
+    if nrun != 1:
+        raise _lib.NnlmError(_lib.ERR_ARG, "%s: init = %r is deterministic: nrun = %d members of one rank would be identical (use nrun = 1)"
+                             % (who, init, nrun))
+    if missing_door:
+        raise unsupported("init = %r is not supported with sparse_batch = 'missing': a matrix whose absent entries are missing has no SVD here" % init)
+    if kl_door and init == "nndsvd":
+        raise unsupported("init = 'nndsvd' leaves exact zeros in W and H, which KL loss cannot start from; use init = 'nndsvda'")
+    opts = dict(opts)
+    oversample, power_iters = opts.pop("svd_oversample", 10), opts.pop("svd_power_iters", 2)
+    on_device = parts is not None or _lib.is_device_array(A)
+    if not on_device and not is_sparse(A) and np.ndim(A) == 2 and not np.isfinite(np.asarray(A, dtype=np.float64)).all():
+        raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A")
+    with _lib.Handle(_device_index(A) if on_device else int(os.environ.get("NNLM_DEVICE", "0") or 0), _env_precision()) as h:
+        try:
+            mat = _svd_ingest(A, h, who, "mkl" if kl_door else "mse", kl_door, True, parts)
+        except NnlmStop as e:
+            if "non-finite" in str(e):
+                raise unsupported("A has missing (NA, NaN or +-Inf) entries; the batched factorisation needs a finite A") from None
+            raise
+        n, m = mat["n"], mat["m"]
+        l, q = _svd_width(max(ks), oversample, power_iters, n, m, who)
+        omega = _svd_omega(l, m, g)
+        opts["absent"] = "zero"
+        prep = []
+        for kb in ks:
+            args, ctx, mat = _prepare_nnmf(A, kb, init=None, rng=np.random.default_rng(0), matrix=mat, **opts)
+            ctx["init"] = init
+            if kl_door:
+                ctx["sparse_kl"] = True
+            prep.append((args, ctx))
+        a0 = prep[0][0]
+        cb = _lib.make_callbacks(print_fn=(lambda s: print(s, end="")) if prep[0][1]["verbose"] == 2 else None)
+        t0 = time.perf_counter()
+        h.svd(l, q, omega)
+        h.set_factors_nndsvd_batch(ks, init)
+        outs = h.run_batch(*a0[6:10], *a0[11:], callbacks=cb)
+        torch = _tensor_lib(A)
+        for o, (W, H) in zip(outs, h.get_factors_batch()):
+            o["W"], o["H"] = (W, H) if torch is None else (torch.from_numpy(W).to(A.device), torch.from_numpy(H).to(A.device))
+        run_time = time.perf_counter() - t0
+    res = [finish_nnmf(o, p[1], run_time=run_time) for o, p in zip(outs, prep)]
+    best = int(np.argmin([r["target_loss"][-1] if len(r["target_loss"]) else np.inf for r in res]))
+    return res, best
+
+
 def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
          check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=0, show_warning=True,
-         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False):
+         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False, svd_oversample=10, svd_power_iters=2):
     """Non-negative matrix factorisation A ~ W H on the MI355X (drop-in for R's NNLM::nnmf, R/nnmf.R:135-225).
+
+    ``init`` = "nndsvd" or "nndsvda": a deterministic, data-driven start (Boutsidis & Gallopoulos 2008) from a truncated SVD of A made on
+    the GPU (truncated_svd(): sketch width min(k + svd_oversample, n, m), svd_power_iters power iterations, the sketch matrix drawn from
+    ``rng`` -- the only random numbers of such a fit).  Every kind of A (host array, sparse object, device tensor, sparse device tensor)
+    then runs on one handle in the arithmetic mode NNLM_PRECISION names: A is uploaded once, decomposed, started and fitted there.
+    "nndsvd" leaves exact zeros in W and H: fine for method "scd", but Lee's multiplicative updates keep a zero forever -- use
+    "nndsvda" (zeros replaced by mean(A)) with method "lee".  Refused with a string init (NnlmStop): masks, absent = "missing", an A
+    with non-finite entries, loss "mkl" on a dense A, and "nndsvd" with loss "mkl" (sparse_kl: "nndsvda" only).  Known profiles are
+    entries of an init dict and so cannot be combined with it.
 
     ``verbose`` defaults to 0 here (R: 1 = progress bar); ``rng`` seeds the default random init (R uses its global RNG).
     ``absent`` (sparse A only): "zero" -- absent entries are zeros; "missing" -- they are missing and the fit runs over the stored
@@ -563,6 +771,9 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     sparse layouts (COO, BSR, BSC) and sparse tensors in host memory are refused by name.
     """
     parts = _sparse_device_parts(A, "nnmf")
+    if isinstance(init, str):
+        return _nnmf_svd_init(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
+                              show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts, svd_oversample, svd_power_iters)
     if parts is not None or _lib.is_device_array(A):
         return _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
                             show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts)
@@ -617,12 +828,21 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
     or "lee"): per half-step one solver launch over the lines of at most 256 stored entries for all members; member b is bit for bit
     nnmf(A, k_b, loss = 'mkl', sparse_kl = True) from the same start.  loss = 'mse' with it behaves as ``sparse_batch`` = True.  A dense
     A and absent = 'missing' are refused; without it loss = 'mkl' is refused as before.
+
+    ``init`` = "nndsvd" or "nndsvda" starts every member from the NNDSVD of ONE truncated SVD of A, made at the width min(max(k) +
+    svd_oversample, n, m) (options svd_oversample = 10, svd_power_iters = 2; the sketch matrix comes from ``rng``): member b takes the
+    first k_b triplets, so a rank sweep ``k = range(1, 11)`` costs one decomposition, not ten.  A then runs on one handle in the mode
+    NNLM_PRECISION names.  nrun > 1 is refused (NNLM_ERR_ARG: the members would be identical); sparse_batch = True is taken,
+    sparse_batch = "kl" with "nndsvda" only, sparse_batch = "missing" is refused.
     """
     missing_door = _sparse_batch_arg(sparse_batch, "nnmf_batch")
     kl_door = sparse_batch == "kl" if isinstance(sparse_batch, str) else False
     sparse_batch = bool(sparse_batch)
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
+    svd_init = None
+    if isinstance(init, str):  # one truncated SVD of A starts every member
+        svd_init, init = _svd_init_arg(init, "nnmf_batch"), None
     if init is not None:
         if isinstance(init, dict) or len(init) != B:
             raise _lib.NnlmError(_lib.ERR_ARG, "init must be a list of %d dicts {'W': ..., 'H': ...}, one per member" % B)
@@ -651,6 +871,13 @@ def nnmf_batch(A, k, nrun=1, init=None, rng=None, sparse_batch=False, **nnmf_opt
                           "absent entries are zeros")
     if sum(ks) > _lib.BATCH_MAX:
         raise unsupported("the ranks sum to %d; a batch holds at most %d" % (sum(ks), _lib.BATCH_MAX))
+    if svd_init is not None:
+        opts = dict(nnmf_options)
+        opts.setdefault("verbose", 0)
+        return _nnmf_batch_svd_init(A, ks, int(nrun), svd_init, rng or np.random.default_rng(), opts, unsupported, missing_door, kl_door, parts)
+    for key in ("svd_oversample", "svd_power_iters"):
+        if key in nnmf_options:
+            raise _lib.NnlmError(_lib.ERR_ARG, "nnmf_batch: %s belongs to init = 'nndsvd' / 'nndsvda'" % key)
     on_device = _lib.is_device_array(A)
     shape = tuple(A.shape) if isinstance(A, np.ndarray) or on_device else np.shape(A)
     if on_device and init is not None:
@@ -867,6 +1094,9 @@ def nnmf_cv(A, k, nrun=1, holdout=0.1, rng=None, init=None, sparse_batch=False, 
     Returns a dict: fits (nnmf results with holdout_mse / holdout_mkl added), k (rank per member), holdout_mse, holdout_mkl (arrays),
     best (index of the lowest holdout_mse, the first on ties), holdout ({"indptr", "indices", "shape"}: the pattern used)."""
     missing_door = _sparse_batch_arg(sparse_batch, "nnmf_cv")
+    if isinstance(init, str):
+        raise _lib.NnlmError(_lib.ERR_UNSUPPORTED, "nnmf_cv: init = %r is not supported: the fit runs on a matrix whose held-out entries are "
+                                                   "missing, and a matrix with missing entries has no SVD here" % init)
     ks = _batch_rank_list(k, nrun)
     B = len(ks)
     if init is not None:

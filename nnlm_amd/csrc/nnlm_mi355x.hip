@@ -24,6 +24,7 @@
 #include "k_xprod.h"
 #include "k_xprod16.h"
 #include "tu_sweepq.h"
+#include "tu_svd.h"
 #include "tu_topn.h"
 
 #include <dlfcn.h>
@@ -31,6 +32,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -263,6 +265,18 @@ struct nnlm_handle {
     void *ho_val = nullptr;
 
     int topn_slices = 0; // candidate slices of the last topn_kernel launch (nnlm_get_info "topn_slices")
+
+    // truncated SVD of the resident matrix (nnlm_svd): the leading svd_l triplets, one row per triplet as the factor
+    // masters keep their components; they live as long as the matrix.  svd_l = 0: none
+    int svd_l = 0, svd_LP = 0, svd_kept = 0; // sketch width, its padding to 16, directions the last orth kept
+    double *svdU = nullptr, *svdVt = nullptr; // [svd_LP][npad], [svd_LP][mpad]
+    std::vector<double> svd_sigma;            // [svd_l], descending
+    double svd_mean = 0.0;                    // mean(A) over all n m entries, from the resident values (the nndsvda fill)
+    bool svd_mean_known = false;
+    double svd_ms[7] = {0};                   // host milliseconds of the last nnlm_svd: cross products, Grams, rotations, host eigendecompositions,
+                                              // waits and transfers, the whole call, setting and freeing the rank-l factor buffers (the device's
+                                              // share is in the first three only with profiling on)
+    int svd_form = -1;                        // form of the last rotation (nnlm_svd_rotate_form), -1 none yet
 
     // profiling
     bool prof = false;
@@ -761,8 +775,19 @@ static void free_factors(nnlm_handle *h)
     h->k = 0;
 }
 
+static void free_svd(nnlm_handle *h)
+{
+    hipFree(h->svdU);
+    hipFree(h->svdVt);
+    h->svdU = h->svdVt = nullptr;
+    h->svd_l = h->svd_LP = h->svd_kept = 0;
+    h->svd_sigma.clear();
+    h->svd_mean_known = false;
+}
+
 static void free_matrix(nnlm_handle *h)
 {
+    free_svd(h); // (a decomposition describes the matrix it was made from)
     for (int o = 0; o < 2; o++) {
         hipFree(h->na_ptr[o]);
         hipFree(h->na_meta[o]);
@@ -4306,6 +4331,16 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sp_gram_workers") == 0) *value = h->spg_workers;
     else if (strcmp(key, "sp_gram_batch_pairs") == 0) *value = h->bspg_pairs;
     else if (strcmp(key, "topn_slices") == 0) *value = h->topn_slices;
+    else if (strcmp(key, "svd_width") == 0) *value = h->svd_l > 0 ? h->svd_l : -1;
+    else if (strcmp(key, "svd_kept") == 0) *value = h->svd_l > 0 ? h->svd_kept : -1;
+    else if (strcmp(key, "svd_ms_cross") == 0) *value = h->svd_ms[0];
+    else if (strcmp(key, "svd_ms_gram") == 0) *value = h->svd_ms[1];
+    else if (strcmp(key, "svd_ms_rotate") == 0) *value = h->svd_ms[2];
+    else if (strcmp(key, "svd_ms_eig") == 0) *value = h->svd_ms[3];
+    else if (strcmp(key, "svd_ms_wait") == 0) *value = h->svd_ms[4];
+    else if (strcmp(key, "svd_ms_total") == 0) *value = h->svd_ms[5];
+    else if (strcmp(key, "svd_ms_setup") == 0) *value = h->svd_ms[6];
+    else if (strcmp(key, "svd_rotate_form") == 0) *value = h->svd_form;
     else return fail(h, NNLM_ERR_ARG, "nnlm_get_info: unknown key '%s'", key);
     return NNLM_OK;
 }
@@ -4699,6 +4734,8 @@ static int batch_ranks(nnlm_handle *h, const char *who, const char *need, unsign
     return NNLM_OK;
 }
 
+static int batch_setup(nnlm_handle *h, unsigned B, const unsigned *k, const std::vector<int> &off);
+
 extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned *k, const double *W, const double *H)
 {
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors_batch: set the matrix first");
@@ -4722,6 +4759,12 @@ extern "C" int nnlm_set_factors_batch(nnlm_handle *h, unsigned B, const unsigned
     // (W: the members' n x k_b blocks one after another ARE the stacked n x K matrix)
     rc = set_factors_impl(h, K, W, H ? Hs.data() : nullptr, nullptr, nullptr, 64);
     if (rc != NNLM_OK) return rc;
+    return batch_setup(h, B, k, off);
+}
+
+// The batch's own state behind stacked factors of rank off[B] (set with 64 padding rows): the members' offsets and workspaces
+static int batch_setup(nnlm_handle *h, unsigned B, const unsigned *k, const std::vector<int> &off)
+{
     h->bB = (int)B;
     h->bk.assign(k, k + B);
     h->boff = off;
@@ -4761,6 +4804,8 @@ extern "C" int nnlm_get_factors_batch(nnlm_handle *h, double *W, double *H)
     }
     return NNLM_OK;
 }
+
+#include "host_svd.h"
 
 // The tile pairs of sp_gram_batch_kernel (k_sparse_na_batch.h) for the active members of a stack: bit pi (upper pairs ta <= tb, ta-major,
 // NT = KP / 16 tiles a side) is set when the 16 x 16 pair meets some active member's diagonal block [off_b, off_b + k_b)^2; *tiles: the
