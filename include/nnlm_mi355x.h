@@ -119,6 +119,20 @@ int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, const int *ro
                             int *n_trace, unsigned *n_iteration, int *warned,
                             const nnlm_callbacks *cb);
 
+/* nnlm_c_nnmf_csc_missing with one weight per stored entry (see nnlm_set_matrix_csc_weighted): weight[nnz] in the order of x, and
+ * absent_missing = 1 (absent entries missing: weighted NMF) or 0 (absent entries are zeros of weight 1: implicit feedback); the other
+ * arguments are those of nnlm_c_nnmf_csc_missing.  Methods 1 and 2, k <= 64. */
+int nnlm_c_nnmf_csc_weighted(int n, int m, const long long *colptr, const int *rowidx, const double *x, const double *weight,
+                             int absent_missing, unsigned k,
+                             const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                             const double alpha[3], const double beta[3],
+                             unsigned max_iter, double rel_tol, int n_threads, int verbose, int show_warning,
+                             unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace,
+                             double *W_out, double *H_out,
+                             double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                             int *n_trace, unsigned *n_iteration, int *warned,
+                             const nnlm_callbacks *cb);
+
 /*
  * Replaces c_nnlm (reference src/nnlm.cpp:4-53; signature src/RcppExports.cpp:10-27).
  *   x n x p, y n x q (may contain missing), mask p x q or NULL, beta0 p x q or NULL (-> U(0,1) init).
@@ -145,6 +159,13 @@ int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, const long lon
                             const double alpha[3], const int *mask, const double *beta0,
                             unsigned max_iter, double rel_tol, int n_threads, int method,
                             double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
+/* nnlm_c_nnlm_csc_missing with one weight per stored entry of y (weight[nnz], absent_missing as in nnlm_c_nnmf_csc_weighted): the
+ * weighted fold-in of new columns.  Methods 1 and 2, p <= 64. */
+int nnlm_c_nnlm_csc_weighted(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                             const double *weight, int absent_missing,
+                             const double alpha[3], const int *mask, const double *beta0,
+                             unsigned max_iter, double rel_tol, int n_threads, int method,
+                             double *coefficient, int *n_iteration, const nnlm_callbacks *cb);
 
 /* ------------------------------------------------------------------------------------------
  * Resident API: the same path with A kept in HBM across calls.  The one-shot entries are thin
@@ -213,6 +234,22 @@ int nnlm_set_matrix_csc_kl_batch(nnlm_handle *h, int n, int m, const long long *
  * and 2, both modes, ranks 1..64, masks and known profiles.  NNLM_ERR_UNSUPPORTED: methods 3 and 4, rank > 64 (nnlm_set_factors),
  * nnlm_comm_init, nnlm_debug_partial and the batch entries (their door: nnlm_set_matrix_csc_missing_batch). */
 int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x);
+/* Per-entry weights on a sparse A: the CSC contract and validation of nnlm_set_matrix_csc / nnlm_set_matrix_csc_missing plus
+ * weight[nnz], one weight c_e per stored entry in the order of x -- not NULL, every weight finite and >= 0 (NNLM_ERR_ARG names the first
+ * offender; a weight of 0 is legal); NNLM_PREC_F32 applies the range rules to c a as to a.  absent_missing = 1: an absent entry is
+ * missing (weighted NMF on the stored entries); absent_missing = 0: an absent entry is a zero of weight 1 (implicit feedback, Hu, Koren
+ * & Volinsky 2008: c = 1 + alpha r on the stored entries).  The loss is 1/2 sum over the observed entries of c (a - (WH))^2 + the
+ * reference's penalties; a half-step is the reference's update_with_missing() / update() on the column problem whose rows are scaled by
+ * sqrt(c): per column G_j = c0 G_full + sum over its stored entries of (c_e - c0) y y^T and b_j = sum of c_e a_e y (c0 = the weight of
+ * an absent entry), then the per-column solvers of the NA path; nothing n x m sized.  The handle is the one the unweighted door leaves
+ * for the same absent semantics -- nnlm_matrix_info's N (nnz, a weight-0 entry counted, or n m), check_k, nnlm_top_n's exclusion and
+ * nnlm_predict_entries -- plus the weights and the products c a in both orientations; kl_const is the weighted constant.  Traces:
+ * mse = sum c (a - wh)^2 / N, mkl = kl_const + sum c (-(a + eps) log(wh + eps) + wh) / N over the observed entries.  With every weight
+ * 1 and absent_missing = 1 all results equal nnlm_set_matrix_csc_missing's bit for bit.  Methods 1 and 2, both modes, ranks 1..64,
+ * masks, known profiles, all three penalties.  NNLM_ERR_UNSUPPORTED: methods 3 and 4, rank > 64, the batch entries, nnlm_comm_init,
+ * nnlm_debug_partial, nnlm_svd and the NNDSVD starts.  nnlm_get_info: "sparse_weighted". */
+int nnlm_set_matrix_csc_weighted(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x,
+                                 const double *weight, int absent_missing);
 /* nnlm_set_matrix_csc_missing for restarts, rank sweeps and rank selection: the same contract and validation, with an optional HOLD-OUT
  * pattern ho_colptr[m + 1] / ho_rowidx[] -- a canonical CSC pattern that must be a subset of the stored pattern; ho_colptr == NULL: no
  * hold-out set.  Held-out entries leave the stored set on the host before the CSC and the CSR are built; their values stay on the device

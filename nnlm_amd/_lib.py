@@ -44,6 +44,7 @@ EXPORTS = [
     "nnlm_set_matrix_csc_kl_batch", "nnlm_c_nnmf_csc_kl_batch",
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
     "nnlm_set_matrix_sparse_device", "nnlm_debug_sparse_resident",
+    "nnlm_set_matrix_csc_weighted", "nnlm_c_nnmf_csc_weighted", "nnlm_c_nnlm_csc_weighted",
     "nnlm_svd", "nnlm_get_svd", "nnlm_set_factors_nndsvd", "nnlm_set_factors_nndsvd_batch", "nnlm_debug_set_svd_rotate",
 ]
 NNDSVD_VARIANTS = {"nndsvd": 0, "nndsvda": 1}
@@ -127,6 +128,13 @@ def load():
         getattr(lib, name + "_missing").argtypes = getattr(lib, name).argtypes
         getattr(lib, name + "_kl").restype = C.c_int  # (absent entries zeros, KL loss too: the same arguments)
         getattr(lib, name + "_kl").argtypes = getattr(lib, name).argtypes
+    # per-entry weights: weight, absent_missing behind x / yx
+    lib.nnlm_set_matrix_csc_weighted.restype = C.c_int
+    lib.nnlm_set_matrix_csc_weighted.argtypes = lib.nnlm_set_matrix_csc.argtypes + [dp, C.c_int]
+    lib.nnlm_c_nnmf_csc_weighted.restype = C.c_int
+    lib.nnlm_c_nnmf_csc_weighted.argtypes = lib.nnlm_c_nnmf_csc.argtypes[:5] + [dp, C.c_int] + lib.nnlm_c_nnmf_csc.argtypes[5:]
+    lib.nnlm_c_nnlm_csc_weighted.restype = C.c_int
+    lib.nnlm_c_nnlm_csc_weighted.argtypes = lib.nnlm_c_nnlm_csc.argtypes[:7] + [dp, C.c_int] + lib.nnlm_c_nnlm_csc.argtypes[7:]
     lib.nnlm_create.restype = C.c_int
     lib.nnlm_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int]
     lib.nnlm_destroy.restype = None
@@ -771,11 +779,29 @@ def c_nnmf_csc_kl(indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, ma
                      n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
 
 
+def _weights(weights, nnz):
+    """One fp64 weight per stored entry, in the order of the values (the library checks the values themselves)."""
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+    if w.size != nnz:
+        raise ValueError("weights has %d entries, the matrix stores %d" % (w.size, nnz))
+    return w
+
+
+def c_nnmf_csc_weighted(indptr, indices, data, weights, absent_missing, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads,
+                        verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks=None):
+    """c_nnmf_csc with one weight >= 0 per stored entry (in the order of data).  absent_missing: an absent entry is missing (True:
+    weighted NMF on the stored entries) or a zero of weight 1 (False: implicit feedback).  Methods 1 and 2, k <= 64."""
+    wt = _weights(weights, np.size(data))
+    return _nnmf_csc(load().nnlm_c_nnmf_csc_weighted, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol,
+                     n_threads, verbose, show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks,
+                     _extra=(_dp(wt), 1 if absent_missing else 0))
+
+
 def _nnmf_csc(entry, indptr, indices, data, shape, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,
-              inner_max_iter, inner_rel_tol, method, trace, callbacks):
+              inner_max_iter, inner_rel_tol, method, trace, callbacks, _extra=()):
     n, m = (int(v) for v in shape)
     ptr, idx, val = _csc_arrays(indptr, indices, data)
-    return _nnmf(entry, (n, m, _lp(ptr), _ip(idx), _dp(val)), n, m, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose,
+    return _nnmf(entry, (n, m, _lp(ptr), _ip(idx), _dp(val)) + tuple(_extra), n, m, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose,
                  show_warning, inner_max_iter, inner_rel_tol, method, trace, callbacks)
 
 
@@ -797,14 +823,22 @@ def c_nnlm_csc_kl(x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, m
                      n_threads, method, callbacks)
 
 
-def _nnlm_csc(entry, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks):
+def c_nnlm_csc_weighted(x, y_indptr, y_indices, y_data, weights, absent_missing, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads,
+                        method, callbacks=None):
+    """c_nnlm_csc with one weight >= 0 per stored entry of y (absent_missing as in c_nnmf_csc_weighted): the weighted fold-in; p <= 64."""
+    wt = _weights(weights, np.size(y_data))
+    return _nnlm_csc(load().nnlm_c_nnlm_csc_weighted, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol,
+                     n_threads, method, callbacks, _extra=(_dp(wt), 1 if absent_missing else 0))
+
+
+def _nnlm_csc(entry, x, y_indptr, y_indices, y_data, y_shape, alpha, mask, beta0, max_iter, rel_tol, n_threads, method, callbacks, _extra=()):
     x = _f64(x)
     n, p = x.shape
     if int(y_shape[0]) != n:
         raise ValueError("y has %d rows, x has %d" % (int(y_shape[0]), n))
     q = int(y_shape[1])
     ptr, idx, val = _csc_arrays(y_indptr, y_indices, y_data)
-    return _nnlm(entry, (_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val)), p, q, alpha, mask, beta0, max_iter, rel_tol, n_threads, method,
+    return _nnlm(entry, (_dp(x), n, p, q, _lp(ptr), _ip(idx), _dp(val)) + tuple(_extra), p, q, alpha, mask, beta0, max_iter, rel_tol, n_threads, method,
                  callbacks)
 
 
@@ -880,6 +914,15 @@ class Handle:
         ptr, idx, val = _csc_arrays(indptr, indices, data)
         n, m = (int(v) for v in shape)
         self._ck(self._lib.nnlm_set_matrix_csc_missing(self._h, n, m, _lp(ptr), _ip(idx), _dp(val)))
+        self.n, self.m = n, m
+
+    def set_matrix_csc_weighted(self, indptr, indices, data, weights, shape, absent_missing=True):
+        """Sparse A of shape (n, m) as CSC arrays with one weight >= 0 per stored entry (in the order of data; None: a NULL pointer, which
+        the library refuses).  absent_missing: an absent entry is missing (True) or a zero of weight 1 (False)."""
+        ptr, idx, val = _csc_arrays(indptr, indices, data)
+        wt = None if weights is None else _weights(weights, val.size)
+        n, m = (int(v) for v in shape)
+        self._ck(self._lib.nnlm_set_matrix_csc_weighted(self._h, n, m, _lp(ptr), _ip(idx), _dp(val), _dp(wt), 1 if absent_missing else 0))
         self.n, self.m = n, m
 
     def set_matrix_csc_missing_batch(self, indptr, indices, data, shape, holdout=None):

@@ -109,6 +109,55 @@ def _absent_arg(absent, x, name):
     return absent
 
 
+# ------------------------------------------------------------------------------------------------
+# per-entry weights on a sparse A (nnlm_set_matrix_csc_weighted)
+# ------------------------------------------------------------------------------------------------
+def _weights_refusals(who, name, x, loss, sparse_kl, init=None):
+    """What `weights` cannot be combined with, each refused by name."""
+    if _lib.is_device_array(x) or str(getattr(x, "layout", "")).startswith("torch.sparse_"):
+        raise NnlmStop("%s: weights cannot be combined with a %s in device memory (dense or sparse tensor); pass a host sparse matrix "
+                       "(an object with tocsc())." % (who, name))
+    if not is_sparse(x):
+        raise NnlmStop("%s: weights need a sparse %s (an object with tocsc()): one weight per stored entry; weights on a dense matrix are "
+                       "not supported." % (who, name))
+    if loss == "mkl" or sparse_kl:
+        raise NnlmStop("%s: weights are supported for loss = 'mse' only (not loss = 'mkl' / sparse_kl)." % who)
+    if isinstance(init, str):
+        raise NnlmStop("%s: weights cannot be combined with init = %r: a matrix with per-entry weights has no SVD start here." % (who, init))
+
+
+def _weights_arg(weights, A, c, who):
+    """One fp64 weight per stored entry of the canonical CSC c = as_csc(A), in the order of c.data.  weights: an object with tocsc()
+    whose canonical pattern equals c's, or a 1-D array of length nnz aligned with c.data -- the latter only when A was canonical already
+    (as_csc neither reordered nor merged anything: otherwise the alignment is not defined)."""
+    n, m = c.shape
+    if is_sparse(weights):
+        w = as_csc(weights)
+        if tuple(w.shape) != (n, m):
+            raise NnlmStop("%s: weights is %d x %d, the matrix %d x %d." % (who, w.shape[0], w.shape[1], n, m))
+        if not np.array_equal(w.indptr, c.indptr) or not np.array_equal(w.indices, c.indices):
+            for j in range(m):
+                a0, a1, b0, b1 = c.indptr[j], c.indptr[j + 1], w.indptr[j], w.indptr[j + 1]
+                if a1 - a0 != b1 - b0 or not np.array_equal(c.indices[a0:a1], w.indices[b0:b1]):
+                    raise NnlmStop("%s: the stored pattern of weights differs from the matrix's (first in column %d): one weight per stored "
+                                   "entry is needed." % (who, j))
+        wd = w.data
+    else:
+        wd = np.asarray(weights, dtype=np.float64)
+        if wd.ndim != 1 or wd.size != c.data.size:
+            raise NnlmStop("%s: weights must be a sparse matrix with the matrix's stored pattern, or a 1-D array with one weight per stored "
+                           "entry (%d); got shape %s." % (who, c.data.size, wd.shape))
+        raw = A.tocsc()
+        if not (np.array_equal(np.asarray(raw.indptr, dtype=np.int64), c.indptr) and np.asarray(raw.indices).size == c.indices.size
+                and np.array_equal(np.asarray(raw.indices, dtype=np.int64), c.indices)):
+            raise NnlmStop("%s: a weights array is aligned with the stored entries of a canonical CSC, but the matrix is not canonical "
+                           "(unsorted or duplicate entries were reordered / merged); pass weights as a sparse matrix of the same pattern." % who)
+    wd = np.ascontiguousarray(wd, dtype=np.float64)
+    if not np.all(np.isfinite(wd)) or np.any(wd < 0):
+        raise NnlmStop("%s: weights must be finite and >= 0." % who)
+    return wd
+
+
 def _stored_counts(c):
     """Stored entries per row and per column of a CSC."""
     n, m = c.shape
@@ -738,8 +787,16 @@ def _nnmf_batch_svd_init(A, ks, nrun, init, g, opts, unsupported, missing_door, 
 
 def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, W_norm=-1,
          check_k=True, max_iter=500, rel_tol=1e-4, n_threads=1, trace=None, verbose=0, show_warning=True,
-         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False, svd_oversample=10, svd_power_iters=2):
+         inner_max_iter=None, inner_rel_tol=1e-9, rng=None, absent="zero", sparse_kl=False, svd_oversample=10, svd_power_iters=2,
+         weights=None):
     """Non-negative matrix factorisation A ~ W H on the MI355X (drop-in for R's NNLM::nnmf, R/nnmf.R:135-225).
+
+    ``weights`` (host sparse A, loss "mse", k <= 64): one weight c >= 0 per stored entry -- a sparse matrix with A's stored pattern, or a
+    1-D array aligned with the stored entries of a canonical A.  The loss is 1/2 sum of c (a - (WH))^2 over the observed entries + the
+    penalties.  With absent = "missing" the observed entries are the stored ones (weighted NMF: inverse-variance weights, down-weighted
+    doubtful ratings).  With absent = "zero" every entry is observed and an absent one is a zero of weight 1: implicit feedback (Hu,
+    Koren & Volinsky 2008: store r with weight 1 + alpha r).  The traces are the weighted sums over N = nnz (missing) or n m (zero).
+    Refused by name: a dense A, a tensor in device memory, loss "mkl" / sparse_kl, a string init.
 
     ``init`` = "nndsvd" or "nndsvda": a deterministic, data-driven start (Boutsidis & Gallopoulos 2008) from a truncated SVD of A made on
     the GPU (truncated_svd(): sketch width min(k + svd_oversample, n, m), svd_power_iters power iterations, the sketch matrix drawn from
@@ -770,6 +827,8 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     as_csc() repairs on the host is refused here, with the library's message.  W and H come back as fp64 tensors on A's device.  Other
     sparse layouts (COO, BSR, BSC) and sparse tensors in host memory are refused by name.
     """
+    if weights is not None:
+        _weights_refusals("nnmf", "A", A, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl, init)
     parts = _sparse_device_parts(A, "nnmf")
     if isinstance(init, str):
         return _nnmf_svd_init(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
@@ -782,7 +841,11 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random(), print_fn=(lambda s: print(s, end="")) if ctx["verbose"] == 2 else None)
     t0 = time.perf_counter()
-    if isinstance(args[0], CSC):
+    if weights is not None:
+        c = args[0]
+        wd = _weights_arg(weights, A, c, "nnmf")
+        out = _lib.c_nnmf_csc_weighted(c.indptr, c.indices, c.data, wd, ctx["absent"] == "missing", c.shape, *args[1:], callbacks=cb)
+    elif isinstance(args[0], CSC):
         entry = _lib.c_nnmf_csc_missing if ctx["absent"] == "missing" else (_lib.c_nnmf_csc_kl if ctx["sparse_kl"] else _lib.c_nnmf_csc)
         out = entry(*args[0], *args[1:], callbacks=cb)
     else:
@@ -1252,11 +1315,36 @@ def prepare_nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mas
     return args, ctx
 
 
+def _weighted_mse_mkl(x, y, coef, wd, missing):
+    """The weighted error summary of nnlm(weights=): MSE = sum c (y - x beta)^2 / N and MKL = (sum c ((y + eps) log(y + eps) - y) + sum c
+    (-(y + eps) log(pred + eps) + pred)) / N over the observed entries -- the stored ones (N = nnz), or all n q with weight 1 and y = 0
+    at the absent ones (N = n q).  Nothing n x q sized: the absent entries' sums come from the Gram of x and the sums of x and beta."""
+    eps = 1e-16
+    n, q = y.shape
+    cols = np.repeat(np.arange(q), np.diff(y.indptr))
+    rows = np.asarray(y.indices, dtype=np.int64)
+    pred = np.einsum("ek,ek->e", x[rows], coef.T[cols]) if cols.size else np.zeros(0)
+    a = y.data
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sq = float(np.sum(wd * (a - pred) ** 2))
+        kl = float(np.sum(wd * ((a + eps) * np.log(a + eps) - a))) + float(np.sum(wd * (-(a + eps) * np.log(pred + eps) + pred)))
+        N = float(a.size)
+        if not missing:  # the absent entries: weight 1, y = 0 -- sum pred^2, sum eps log eps - eps log(pred + eps) + pred (the log term <= 3.7e-15 each, left out)
+            sq += max(0.0, float(np.sum((x.T @ x) * (coef @ coef.T))) - float(np.sum(pred ** 2)))
+            N = float(n) * float(q)
+            kl += (N - a.size) * (eps * np.log(eps)) + float(x.sum(axis=0) @ coef.sum(axis=1)) - float(np.sum(pred))
+        if np.any(a < 0) or np.any(pred < 0):
+            kl = float("nan")
+    return {"MSE": sq / N if N else float("nan"), "MKL": kl / N if N else float("nan")}
+
+
 def finish_nnlm(sol, ctx):
     """R/nnlm.R:122-144."""
     coef = np.array(sol["coefficient"])
     x, y, alpha, loss = ctx["x"], ctx["y"], ctx["alpha"], ctx["loss"]
-    if isinstance(y, CSC) and ctx.get("absent") == "missing":  # (mse_mkl with na.rm over the stored entries only: nothing n x q sized)
+    if ctx.get("weights") is not None:
+        err = _weighted_mse_mkl(x, y, coef, ctx["weights"], ctx.get("absent") == "missing")
+    elif isinstance(y, CSC) and ctx.get("absent") == "missing":  # (mse_mkl with na.rm over the stored entries only: nothing n x q sized)
         cols = np.repeat(np.arange(y.shape[1]), np.diff(y.indptr))
         pred = np.einsum("ek,ek->e", x[np.asarray(y.indices, dtype=np.int64)], coef.T[cols]) if cols.size else np.zeros(0)
         err = mse_mkl(y.data, pred, na_rm=True, show_warning=False)
@@ -1274,25 +1362,36 @@ def finish_nnlm(sol, ctx):
 
 
 def nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, check_x=True, max_iter=10000,
-         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None, absent="zero", sparse_kl=False):
+         rel_tol=1e-12, n_threads=1, show_warning=True, rng=None, absent="zero", sparse_kl=False, weights=None):
     """Non-negative linear model y ~ x beta on the MI355X (drop-in for R's NNLM::nnlm, R/nnlm.R:70-145).
+
+    ``weights`` (host sparse y, loss "mse", at most 64 columns of x): one weight >= 0 per stored entry of y, as for nnmf(); the error
+    summary is then the weighted one (MSE = sum c (y - x beta)^2 / N over the observed entries, N = nnz or n q).
 
     ``absent`` (sparse y only): "zero" -- absent entries are zeros; "missing" -- they are missing, each column of beta is fitted to the
     stored entries of its column of y only (square loss, at most 64 columns of x).
     ``sparse_kl`` (sparse y, absent = "zero"): True admits loss = 'mkl' (stored values >= 0, at most 64 columns of x); see nnmf()."""
+    if weights is not None:
+        _weights_refusals("nnlm", "y", y, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl)
     args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning, absent, sparse_kl)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random())
+    if weights is not None:
+        c = args[1]
+        ctx["weights"] = wd = _weights_arg(weights, y, c, "nnlm")
+        sol = _lib.c_nnlm_csc_weighted(args[0], c.indptr, c.indices, c.data, wd, ctx["absent"] == "missing", c.shape, *args[2:], callbacks=cb)
+        return finish_nnlm(sol, ctx)
     if isinstance(args[1], CSC):
         entry = _lib.c_nnlm_csc_missing if ctx["absent"] == "missing" else (_lib.c_nnlm_csc_kl if ctx["sparse_kl"] else _lib.c_nnlm_csc)
         return finish_nnlm(entry(args[0], *args[1], *args[2:], callbacks=cb), ctx)
     return finish_nnlm(_lib.c_nnlm(*args, callbacks=cb), ctx)
 
 
-def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=None, absent="zero", **kw):
+def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=None, absent="zero", weights=None, **kw):
     """S3 predict.nnmf, R/nnmf_methods.R:22-48.  ``_nnlm`` lets the CPU tests substitute the solver.  ``absent = "missing"`` with a
     sparse ``newdata`` and which = "H" is the recommender's fold-in of new users: their H columns fitted to their stored scores only
-    (which = "W": new rows, the same over their stored entries; which = "A" returns W H and ignores ``absent``)."""
+    (which = "W": new rows, the same over their stored entries; which = "A" returns W H and ignores ``absent``).  ``weights``: one
+    weight per stored entry of a sparse ``newdata``, as for nnlm() -- the weighted fold-in (which = "H" only)."""
     which = _match_arg(which, ("A", "W", "H"), "which")
     method = method or object["options"]["method"]
     loss = loss or object["options"]["loss"]
@@ -1317,6 +1416,10 @@ def predict_nnmf(object, newdata=None, which="A", method=None, loss=None, _nnlm=
         nd = np.asarray(nd, dtype=np.float64)
     if which == "A":
         return object["W"] @ object["H"]
+    if weights is not None and which == "W":
+        raise NnlmStop("predict_nnmf: weights are supported with which = 'H' (the fold-in of new columns) only.")
+    if weights is not None and which == "H":
+        kw["weights"] = weights
     if which == "W":
         out = solver(object["H"].T, nd.T, method=method, loss=loss, **kw)
         out["coefficients"] = np.asarray(out["coefficients"]).T

@@ -254,6 +254,7 @@ extern "C" int nnlm_svd(nnlm_handle *h, unsigned l_, unsigned power_iters, const
     const char *who = "nnlm_svd";
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "%s: set the matrix first", who);
     if (h->sharded) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a handle with a communicator is not supported (the decomposition runs on one GPU)", who);
+    if (h->sparse && h->sp_weighted) return weighted_refusal(h, who, "the truncated SVD (and the NNDSVD starts from it)");
     if (h->sparse && h->sp_missing)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix whose absent entries are missing has no SVD here (absent entries must be zeros)", who);
     if (h->holdout && h->ho_nnz > 0)
@@ -378,6 +379,7 @@ static int nndsvd_build(nnlm_handle *h, const char *who, const std::vector<Nndsv
 static int nndsvd_refusal(nnlm_handle *h, const char *who, unsigned kmax, int variant)
 {
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "%s: set the matrix first", who);
+    if (h->sparse && h->sp_weighted) return weighted_refusal(h, who, "an NNDSVD start");
     if (h->svd_l < 1) return fail(h, NNLM_ERR_ARG, "%s: no decomposition on the handle (call nnlm_svd first)", who);
     if (variant != 0 && variant != 1) return fail(h, NNLM_ERR_ARG, "%s: variant must be 0 (nndsvd) or 1 (nndsvda), got %d", who, variant);
     if (kmax > (unsigned)h->svd_l) return fail(h, NNLM_ERR_ARG, "%s: rank %u exceeds the sketch width l = %d of the decomposition", who, kmax, h->svd_l);

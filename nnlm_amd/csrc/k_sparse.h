@@ -215,11 +215,10 @@ __global__ __launch_bounds__(256) void sp_rowsum_partial_kernel(const double *__
 // out[0] = S1 + max(0, <W^T W, H H^T> - S2)  (sum of squares over all n x m entries; the zeros contribute wh^2)
 // out[1] = S3 + sum_q (sum_i W_iq)(sum_j H_qj)  (KL sum; the zeros' -eps log(wh + eps) <= 3.7e-15 per entry is left out)
 // s = {S1, S2, S3}; GW, GH [KP][KP]; wsum, hsum [KP].  One block, fixed order.
-__global__ __launch_bounds__(256) void sp_err_final_kernel(const double *__restrict__ s, const double *__restrict__ GW, const double *__restrict__ GH,
-                                                           const double *__restrict__ wsum, const double *__restrict__ hsum, int k, int KP,
-                                                           double *__restrict__ out)
+// (thread 0 gets *G = <W^T W, H H^T> and *SW = sum_q wsum[q] hsum[q]; 256 threads, all of them call)
+__device__ static inline void sp_err_final_sums(const double *__restrict__ GW, const double *__restrict__ GH, const double *__restrict__ wsum,
+                                                const double *__restrict__ hsum, int k, int KP, double (*red)[4], double *G, double *SW)
 {
-    __shared__ double red[2][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double gg = 0.0, sw = 0.0;
     for (int e = threadIdx.x; e < k * k; e += 256) {
@@ -233,10 +232,94 @@ __global__ __launch_bounds__(256) void sp_err_final_kernel(const double *__restr
     if (lane == 0) red[0][wave] = gg, red[1][wave] = sw;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double G = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        const double SW = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        *G = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+        *SW = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+    }
+}
+__global__ __launch_bounds__(256) void sp_err_final_kernel(const double *__restrict__ s, const double *__restrict__ GW, const double *__restrict__ GH,
+                                                           const double *__restrict__ wsum, const double *__restrict__ hsum, int k, int KP,
+                                                           double *__restrict__ out)
+{
+    __shared__ double red[2][4];
+    double G = 0.0, SW = 0.0;
+    sp_err_final_sums(GW, GH, wsum, hsum, k, KP, red, &G, &SW);
+    if (threadIdx.x == 0) {
         const double zeros = G - s[1];
         out[0] = s[0] + (zeros > 0.0 ? zeros : 0.0);
         out[1] = s[2] + SW;
+    }
+}
+
+// Per-entry weights (nnlm_set_matrix_csc_weighted): sp_errors_kernel with the weight c of each stored entry beside its value, same worker
+// split and reduction order.  partial[block] = {sum c r^2, sum wh^2, sum c (-(a + eps) log(wh + eps)), sum c wh, sum wh}.  A weight of
+// exactly 1 changes no bit of the sums it shares with sp_errors_kernel (c r, then fma(c r, r, s): 1 * r is exact).
+template <typename T, int LW>
+__global__ __launch_bounds__(256) void sp_errors_weighted_kernel(const long long *__restrict__ ptr, const int *__restrict__ idx,
+                                                                 const T *__restrict__ val, const T *__restrict__ wt, int ncols, long long nnz,
+                                                                 long long chunk, int nworkers, const double *__restrict__ Wrow, int KP, int k,
+                                                                 const double *__restrict__ H, int ldh, double *__restrict__ partial)
+{
+    constexpr int NG = 64 / LW;
+    const int lane = threadIdx.x & 63, ql = lane % LW, wave = threadIdx.x >> 6;
+    const int w = (blockIdx.x * 4 + wave) * NG + lane / LW;
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (w < nworkers) {
+        long long e0, e1;
+        sp_worker_range(nnz, chunk, w, &e0, &e1);
+        if (e0 < e1) {
+            int c = sp_lower_bound(ptr, ncols, e0 + 1) - 1; // the column holding e0 (last c with ptr[c] <= e0)
+            long long cend = ptr[c + 1];
+            for (long long e = e0; e < e1; e++) {
+                while (e >= cend) cend = ptr[++c + 1];
+                const int i = idx[e];
+                double d = 0.0;
+                for (int q = ql; q < k; q += LW) d = __builtin_fma(Wrow[(size_t)i * KP + q], H[(size_t)q * ldh + c], d);
+#pragma unroll
+                for (int o = LW / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, LW);
+                if (ql == 0) {
+                    const double av = (double)val[e], cv = (double)wt[e];
+                    const double r = av - d;
+                    s[0] = __builtin_fma(cv * r, r, s[0]);
+                    s[1] = __builtin_fma(d, d, s[1]);
+                    const double ca = cv * (av + NNLM_TINY); // (the plain kernel's expression from here on: the same contraction)
+                    s[2] += -ca * nnlm_log_pos(d + NNLM_TINY);
+                    s[3] += cv * d;
+                    s[4] += d;
+                }
+            }
+        }
+    }
+    __shared__ double red[5][4];
+#pragma unroll
+    for (int c = 0; c < 5; c++) {
+        s[c] = wave_sum(s[c]);
+        if (lane == 0) red[c][wave] = s[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int c = threadIdx.x;
+        partial[5 * (size_t)blockIdx.x + c] = ((red[c][0] + red[c][1]) + red[c][2]) + red[c][3];
+    }
+}
+
+// The error block of a weighted handle: s = the five sums of sp_errors_weighted_kernel.  miss: the stored entries are all there is.
+// Otherwise an absent entry is a zero of weight 1: the sums over all n x m entries as in sp_err_final_kernel, the stored entries' own
+// terms re-weighted (s3 - s4 = sum (c - 1) wh).
+__global__ __launch_bounds__(256) void sp_err_final_weighted_kernel(const double *__restrict__ s, const double *__restrict__ GW,
+                                                                    const double *__restrict__ GH, const double *__restrict__ wsum,
+                                                                    const double *__restrict__ hsum, int k, int KP, int miss, double *__restrict__ out)
+{
+    __shared__ double red[2][4];
+    double G = 0.0, SW = 0.0;
+    if (!miss) sp_err_final_sums(GW, GH, wsum, hsum, k, KP, red, &G, &SW);
+    if (threadIdx.x == 0) {
+        if (miss) {
+            out[0] = s[0];
+            out[1] = s[2] + s[3];
+        } else {
+            const double zeros = G - s[1];
+            out[0] = s[0] + (zeros > 0.0 ? zeros : 0.0);
+            out[1] = (s[2] + SW) + (s[3] - s[4]);
+        }
     }
 }

@@ -21,6 +21,13 @@
 // two fp32 numbers is exact in fp64, so both modes form and accumulate every product in fp64 -- at least as accurate as the split-fp16
 // form of na_gram_f16_kernel).  Empty columns get G = 0 (nothing observed: the solvers see TINY I + the regularisation, as on the dense
 // NA path and in the reference).
+//
+// Weighted form (WT; nnlm_set_matrix_csc_weighted): stored entry e has weight c_e >= 0, an absent entry weight c0 = 0 (missing) or 1 (a
+// zero), and column j needs  G_j = c0 G_full + sum over its stored entries of (c_e - c0) y_row(e) y_row(e)^T.  A lane loads the weight of
+// its stored row beside the row's index, forms c_e - c0 in fp64 and scales ONE operand of each product with it; segments, worker ranges
+// and summation order are those of the plain form, and a weight of exactly 1 with c0 = 0 changes no bit (y * 1.0 is exact).  c0 = 1: the
+// shared Gram (launch_gram's, raw) is added once per column -- at the store of a one-segment column (an empty column gets G_full: under
+// the zero semantics it is a real all-zero column), by the fix-up for a long one.
 #pragma once
 #include "common.h"
 #include "tu_sweepq.h"
@@ -38,7 +45,7 @@ __device__ static inline int spg_lower_bound(const long long *__restrict__ ptr, 
     return lo;
 }
 
-template <typename T, int NT>
+template <typename T, int NT, bool WT = false>
 __global__ __launch_bounds__(256) void sp_gram_kernel(const SpGramArgs a)
 {
     constexpr int KP = 16 * NT, NP = NT * (NT + 1) / 2;
@@ -48,6 +55,7 @@ __global__ __launch_bounds__(256) void sp_gram_kernel(const SpGramArgs a)
     const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w >= a.nworkers) return; // whole wavefront
     const T *Y = (const T *)a.Y;
+    const T *wt = (const T *)a.wt;
     const long long E0 = a.ptr[a.c0], E1 = a.ptr[a.c1];
     long long e0 = E0 + (long long)w * a.chunk, e1 = e0 + a.chunk;
     if (e0 > E1) e0 = E1;
@@ -59,10 +67,12 @@ __global__ __launch_bounds__(256) void sp_gram_kernel(const SpGramArgs a)
         for (int i = 0; i < NP; i++) acc[i] = typename M::acc_t{0, 0, 0, 0};
         for (long long e = st; e < en; e += 4 * GR) {
             int ri[GR];
+            double cw[GR]; // (WT only) c_e - c0 of the lane's stored row
 #pragma unroll
             for (int u = 0; u < GR; u++) {
                 const long long r = e + 4 * u + lg;
                 ri[u] = r < en ? a.idx[r] : -1;
+                if (WT) cw[u] = r < en ? (double)wt[r] - a.cw0 : 0.0;
             }
             double y[GR][NT];
 #pragma unroll
@@ -73,12 +83,15 @@ __global__ __launch_bounds__(256) void sp_gram_kernel(const SpGramArgs a)
             for (int u = 0; u < GR; u++) {
                 int pi = 0;
 #pragma unroll
-                for (int ta = 0; ta < NT; ta++)
+                for (int ta = 0; ta < NT; ta++) {
+                    const double ya = WT ? y[u][ta] * cw[u] : y[u][ta];
 #pragma unroll
-                    for (int tb = ta; tb < NT; tb++, pi++) acc[pi] = M::mma(y[u][ta], y[u][tb], acc[pi]);
+                    for (int tb = ta; tb < NT; tb++, pi++) acc[pi] = M::mma(ya, y[u][tb], acc[pi]);
+                }
             }
         }
         double *out = is_long ? a.seg + (size_t)(a.segoff[c] - a.segoff[a.c0] + s) * KP * KP : a.G + (size_t)(c - a.c0) * KP * KP;
+        const double *gf = (WT && !is_long) ? a.Gfull : nullptr; // (a long column: the fix-up adds it, once)
         int pi = 0;
 #pragma unroll
         for (int ta = 0; ta < NT; ta++)
@@ -87,7 +100,7 @@ __global__ __launch_bounds__(256) void sp_gram_kernel(const SpGramArgs a)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int i = 16 * ta + M::row_of(lane, r), j = 16 * tb + l15;
-                    if (i <= j) out[i * KP + j] = acc[pi][r]; // (upper triangle: the solvers read G[min][max])
+                    if (i <= j) out[i * KP + j] = gf ? gf[i * KP + j] + acc[pi][r] : acc[pi][r]; // (upper triangle: the solvers read G[min][max])
                 }
     };
     int c = spg_lower_bound(a.ptr, a.c0, a.c1, e0);
@@ -125,6 +138,7 @@ __global__ __launch_bounds__(256) void sp_gram_fixup_kernel(const SpGramArgs a, 
         if (e / KP > e % KP) continue; // (upper triangle only)
         double v = src[e];
         for (long long t = 1; t < ns; t++) v += src[(size_t)t * KP * KP + e];
+        if (a.Gfull) v += a.Gfull[e]; // (weighted form, absent entries zeros: + the shared Gram, once)
         out[e] = v;
     }
 }

@@ -174,6 +174,12 @@ struct nnlm_handle {
     // of each column (segoff) and the list of the long columns.  Per orientation and budget: the column chunks whose Grams are held at
     // once; the buffer they share (freed with the factors)
     bool sp_missing = false;
+    // per-entry weights on the stored entries (nnlm_set_matrix_csc_weighted): the handle of the unweighted door for the same absent
+    // semantics, plus the weights and the premultiplied values c_e a_e in both orientations (mode's type) and the per-orientation
+    // tables of the per-column path, which every square-loss half-step of such a handle takes (half_step_sparse_missing)
+    bool sp_weighted = false;
+    void *sp_cwt = nullptr, *sp_rwt = nullptr; // weights, CSC / CSR order
+    void *sp_cwa = nullptr, *sp_rwa = nullptr; // c_e a_e, CSC / CSR order
     // sparse A loaded for KL loss (nnlm_set_matrix_csc_kl, k_sparse_kl.h): a sparse handle whose methods 3 and 4 run.  Per orientation (0: rows
     // of A for the W half-step, 1: columns for the H half-step) the lines of more than SPKL_SHORT_MAX stored entries, on the device
     bool sp_kl = false;
@@ -303,6 +309,13 @@ static int fail(nnlm_handle *h, int code, const char *fmt, ...)
     if (h) h->err = buf;
     g_attr_err = hipSuccess; // (a refused attribute latched on the way here belongs to this failure, not to a later launch)
     return code;
+}
+
+// What a handle with per-entry weights (nnlm_set_matrix_csc_weighted) does not do: square loss, methods 1 and 2, rank <= 64, one fit
+static int weighted_refusal(nnlm_handle *h, const char *who, const char *what)
+{
+    return fail(h, NNLM_ERR_UNSUPPORTED, "%s: %s is not supported on a matrix with per-entry weights (nnlm_set_matrix_csc_weighted: square loss, "
+                                         "methods 1 and 2, rank <= %d, single fits on one GPU)", who, what, NNLM_KQ_MAX);
 }
 
 template <typename... P>
@@ -830,6 +843,12 @@ static void free_matrix(nnlm_handle *h)
         h->spg_plan_cap[o] = 0;
     }
     h->sp_missing = false;
+    hipFree(h->sp_cwt);
+    hipFree(h->sp_rwt);
+    hipFree(h->sp_cwa);
+    hipFree(h->sp_rwa);
+    h->sp_cwt = h->sp_rwt = h->sp_cwa = h->sp_rwa = nullptr;
+    h->sp_weighted = false;
     for (int o = 0; o < 2; o++) {
         hipFree(h->spkl_longc[o]);
         h->spkl_longc[o] = nullptr;
@@ -1511,15 +1530,38 @@ static int csc_check(nnlm_handle *h, int n, int m, const long long *colptr, cons
     return NNLM_OK;
 }
 
-// nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is
+// One value array of a sparse handle in the mode's type, from its fp64 host copy (nnz + slack elements, as sp_upload sizes them)
+template <typename T> static int sp_upload_values(nnlm_handle *h, void **dst, const double *src, long long nnz)
+{
+    const size_t vb = (size_t)nnz * sizeof(T) + 64;
+    HIPCHK(h, hipMalloc(dst, vb));
+    h->sp_bytes += vb;
+    if (nnz > 0) {
+        std::vector<T> v((size_t)nnz);
+        for (long long e = 0; e < nnz; e++) v[e] = (T)src[e];
+        HIPCHK(h, hipMemcpy(*dst, v.data(), (size_t)nnz * sizeof(T), hipMemcpyHostToDevice));
+    }
+    return NNLM_OK;
+}
+
+// nnlm_set_matrix_csc and nnlm_set_matrix_csc_missing: one contract, one body; `absent_missing` chooses what an absent entry is.
+// weight != NULL (nnlm_set_matrix_csc_weighted): one weight c_e >= 0 per stored entry, in the order of x.  The handle is the one the
+// unweighted door leaves for the same absent semantics (N, check_k, structure), plus the weights and the products c_e a_e (formed in
+// fp64 here) in both orientations, the per-orientation tables of the per-column path for either semantics, and the weighted KL constant.
 static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing,
-                               const char *who, bool kl = false)
+                               const char *who, bool kl = false, const double *weight = nullptr)
 {
     const int rcc = csc_check(h, n, m, colptr, rowidx, x, absent_missing, who, kl);
     if (rcc != NNLM_OK) return rcc;
     const long long nnz = colptr[m];
+    if (weight)
+        for (int j = 0; j < m; j++)
+            for (long long e = colptr[j]; e < colptr[j + 1]; e++)
+                if (!std::isfinite(weight[e]) || weight[e] < 0.0)
+                    return fail(h, NNLM_ERR_ARG, "%s: weight %g of entry %lld (row %d, column %d) is not a finite number >= 0", who, weight[e], e,
+                                rowidx[e], j);
     std::vector<long long> rptr((size_t)n + 1, 0);
-    double over = 0.0, mx = 0.0, klc = 0.0;
+    double over = 0.0, mx = 0.0, wmx = 0.0, klc = 0.0;
     for (int j = 0; j < m; j++)
         for (long long e = colptr[j]; e < colptr[j + 1]; e++) {
             const int i = rowidx[e];
@@ -1528,17 +1570,31 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
             if (std::fabs(v) > 3.4028234663852886e38) over += 1.0;
             const double fv = std::fabs((double)(float)v);
             if (fv > mx) mx = fv;
-            klc += (v + NNLM_TINY) * std::log(v + NNLM_TINY) - v; // src/nnmf.cpp:70,73 over the non-zeros
+            if (!weight) {
+                klc += (v + NNLM_TINY) * std::log(v + NNLM_TINY) - v; // src/nnmf.cpp:70,73 over the non-zeros
+                continue;
+            }
+            // (the fp32 range rules hold for c a as for a -- the cross product reads it -- and for c itself; a weight of 1 changes nothing)
+            const double c = weight[e], ca = c * v;
+            if (std::fabs(v) <= 3.4028234663852886e38 && (std::fabs(ca) > 3.4028234663852886e38 || c > 3.4028234663852886e38)) over += 1.0;
+            const double fca = std::fabs((double)(float)ca);
+            if (fca > wmx) wmx = fca;
+            klc += c * ((v + NNLM_TINY) * std::log(v + NNLM_TINY) - v);
         }
     if (h->prec == NNLM_PREC_F32 && over > 0.0)
-        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
-                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over);
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A%s exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
+                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over,
+                    weight ? " (or their weights, or weight * A)" : "");
     if (h->prec == NNLM_PREC_F32 && mx > 0.0 && mx < 7.8886090522101181e-31)
         return fail(h, NNLM_ERR_UNSUPPORTED, "max |A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale A or use "
                                              "the strict fp64 mode", mx);
+    if (weight && h->prec == NNLM_PREC_F32 && wmx > 0.0 && wmx < 7.8886090522101181e-31)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "max |weight * A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale "
+                                             "or use the strict fp64 mode", wmx);
     for (int i = 0; i < n; i++) rptr[(size_t)i + 1] += rptr[i];
     std::vector<int> cidx((size_t)nnz);
-    std::vector<double> rval((size_t)nnz);
+    std::vector<double> rval((size_t)nnz), cwa, rwt, rwa; // (weighted: c a in CSC order; c and c a permuted to the CSR exactly as rval)
+    if (weight) cwa.resize((size_t)nnz), rwt.resize((size_t)nnz), rwa.resize((size_t)nnz);
     {
         std::vector<long long> next(rptr.begin(), rptr.end() - 1);
         for (int j = 0; j < m; j++)
@@ -1546,6 +1602,7 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
                 const long long d = next[rowidx[e]]++;
                 cidx[d] = j;
                 rval[d] = x[e];
+                if (weight) rwt[d] = weight[e], cwa[e] = rwa[d] = weight[e] * x[e];
             }
     }
     HIPCHK(h, hipSetDevice(h->device));
@@ -1564,7 +1621,30 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
         free_matrix(h);
         return rc;
     }
-    return sp_finish(h, who, colptr, rptr.data(), klc, absent_missing, kl);
+    if (!weight) return sp_finish(h, who, colptr, rptr.data(), klc, absent_missing, kl);
+    auto up = [&](void **dst, const double *src) {
+        return h->prec == NNLM_PREC_F64 ? sp_upload_values<double>(h, dst, src, nnz) : sp_upload_values<float>(h, dst, src, nnz);
+    };
+    int rw = up(&h->sp_cwt, weight);
+    if (rw == NNLM_OK) rw = up(&h->sp_rwt, rwt.data());
+    if (rw == NNLM_OK) rw = up(&h->sp_cwa, cwa.data());
+    if (rw == NNLM_OK) rw = up(&h->sp_rwa, rwa.data());
+    if (rw != NNLM_OK) {
+        free_matrix(h);
+        return rw;
+    }
+    rw = sp_finish(h, who, colptr, rptr.data(), klc, absent_missing, false); // (klc: the weighted sum -> kl_const_w)
+    if (rw != NNLM_OK) return rw;
+    if (!absent_missing) { // the per-column path runs for the zero semantics too: its tables
+        rw = spg_layout(h, 1, colptr, m);
+        if (rw == NNLM_OK) rw = spg_layout(h, 0, rptr.data(), n);
+        if (rw != NNLM_OK) {
+            free_matrix(h);
+            return rw;
+        }
+    }
+    h->sp_weighted = true;
+    return NNLM_OK;
 }
 
 extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
@@ -1575,6 +1655,15 @@ extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long
 extern "C" int nnlm_set_matrix_csc_missing(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
 {
     return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, true, "nnlm_set_matrix_csc_missing");
+}
+
+extern "C" int nnlm_set_matrix_csc_weighted(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x,
+                                            const double *weight, int absent_missing)
+{
+    const char *who = "nnlm_set_matrix_csc_weighted";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!weight) return fail(h, NNLM_ERR_ARG, "%s: weight is NULL (one weight per stored entry, in the order of x)", who);
+    return set_matrix_csc_impl(h, n, m, colptr, rowidx, x, absent_missing != 0, who, false, weight);
 }
 
 extern "C" int nnlm_set_matrix_csc_kl(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
@@ -2059,6 +2148,7 @@ struct Side {
     const long long *sp_ptr;  // sparse A: CSC (H half-step) or CSR (W half-step)
     const int *sp_idx;
     const void *sp_val;
+    const void *sp_wt, *sp_wa; // weighted handle: the weights and the products c a in the orientation's order (else NULL)
     int prof_xprod, prof_sweep, prof_spmm;
 };
 
@@ -2075,6 +2165,7 @@ static Side side_of(const nnlm_handle *h, int which)
         s.bits = h->miss;
         s.A16 = h->A16;
         s.sp_ptr = h->sp_cptr; s.sp_idx = h->sp_ridx; s.sp_val = h->sp_cval;
+        s.sp_wt = h->sp_cwt; s.sp_wa = h->sp_cwa;
         s.prof_xprod = P_XPROD_H; s.prof_sweep = P_SWEEP_H; s.prof_spmm = P_SPMM_H;
     } else {
         s.Y = h->H64; s.ldy = h->mpad; s.p = h->m;
@@ -2085,6 +2176,7 @@ static Side side_of(const nnlm_handle *h, int which)
         s.bits = h->missT;
         s.A16 = h->A16T;
         s.sp_ptr = h->sp_rptr; s.sp_idx = h->sp_cidx; s.sp_val = h->sp_rval;
+        s.sp_wt = h->sp_rwt; s.sp_wa = h->sp_rwa;
         s.prof_xprod = h->fuse_err ? P_XPROD_W_ERR : P_XPROD_W; s.prof_sweep = P_SWEEP_W; s.prof_spmm = P_SPMM_W;
     }
     if (!h->any_missing) s.bits = nullptr;
@@ -2237,7 +2329,7 @@ static int factors_alloc(nnlm_handle *h, int k, int row_pad)
             HIPCHK(h, hipMalloc(&h->sp_eG, ((size_t)2 * KP * KP + 2 * KP + 8) * 8));
             const size_t eb = (size_t)(nnlm_sp_workers(h->nnz, KP, h->cus_device) / (64 / nnlm_sp_lanes(KP)) + 3) / 4;
             const size_t rb = (big + 2047) / 2048;
-            HIPCHK(h, hipMalloc(&h->sp_epart, (3 * eb > KP * rb ? 3 * eb : KP * rb) * 8 + 64));
+            HIPCHK(h, hipMalloc(&h->sp_epart, (5 * eb > KP * rb ? 5 * eb : KP * rb) * 8 + 64)); // (five per workgroup: the weighted error block)
         }
     }
     h->wcur = 0;
@@ -2293,6 +2385,7 @@ extern "C" int nnlm_set_factors(nnlm_handle *h, unsigned k_, const double *W, co
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: set the matrix first");
     const int k = (int)k_;
     if (k < 1) return fail(h, NNLM_ERR_ARG, "nnlm_set_factors: rank k must be >= 1");
+    if (h->sparse && h->sp_weighted && k > NNLM_KQ_MAX) return weighted_refusal(h, "nnlm_set_factors", "a rank above 64");
     if (h->sparse && h->sp_missing && k > NNLM_KQ_MAX)
         return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_set_factors: rank %d on a sparse matrix whose absent entries are missing: the rank is at most %d", k,
                     NNLM_KQ_MAX);
@@ -2327,6 +2420,7 @@ extern "C" int nnlm_set_factors_device(nnlm_handle *h, unsigned k_, const nnlm_d
     if (!has_matrix(h)) return fail(h, NNLM_ERR_ARG, "%s: set the matrix first", who);
     const int k = (int)k_;
     if (k < 1) return fail(h, NNLM_ERR_ARG, "%s: rank k must be >= 1", who);
+    if (h->sparse && h->sp_weighted && k > NNLM_KQ_MAX) return weighted_refusal(h, who, "a rank above 64");
     if (h->sparse && h->sp_missing && k > NNLM_KQ_MAX)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: rank %d on a sparse matrix whose absent entries are missing: the rank is at most %d", who, k, NNLM_KQ_MAX);
     HIPCHK(h, hipSetDevice(h->device));
@@ -2935,8 +3029,13 @@ static void launch_colsolve_m(const SweepArgs &a, size_t g_stride, hipStream_t s
 }
 
 // F32 mode, SCD: colsolve_row_kernel (k_colsolve_row.h, tu_colsolve.hip): four columns per wavefront, the step's delta by DPP row broadcast
+// Not for per-entry weights with absent entries zeros: there every Gram carries the shared Gram of ALL rows while b_j sums over the few
+// stored ones, so from a distant start the scaled gradient is hundreds of times the solution (6.7 against 0.02 with one stored entry
+// among 4000 zeros) and a gradient carried in fp32 leaves 1.3e-4 on it, beyond the mode's 1e-4 -- that path solves in fp64
+// (colsolve_strict_kernel) in both modes.
 static bool colsolve_fast_ok(const nnlm_handle *h, int method)
 {
+    if (h->sparse && h->sp_weighted && !h->sp_missing) return false;
     return method == 1 && h->prec == NNLM_PREC_F32 && h->k <= NNLM_KQ_MAX;
 }
 
@@ -3371,7 +3470,7 @@ static void sp_cross(nnlm_handle *h, const Side &s)
         SpmmArgs a;
         a.ptr = s.sp_ptr;
         a.idx = s.sp_idx;
-        a.val = s.sp_val;
+        a.val = h->sp_weighted ? s.sp_wa : s.sp_val; // (per-entry weights: b_j sums c_e a_e y_row(e) -- the same kernel on c a)
         a.Y = h->sp_Y;
         a.nnz = h->nnz;
         a.ncols = s.ncols;
@@ -3442,9 +3541,17 @@ static int spg_prepare(nnlm_handle *h, int o, size_t slot)
 // the cross product of the zero semantics (it sums over the stored entries either way), then chunk by chunk the per-column Grams over the
 // stored rows (sp_gram_kernel + its fix-up) and the dense NA path's per-column solvers on them (launch_colsolve, unchanged).  Nothing
 // max(n, m) x KP^2 sized is held: a chunk's Grams live in spg_buf, and the solvers find column col at (col - gcol0) * KP^2 (gcol0 = c0).
+// Per-entry weights (nnlm_set_matrix_csc_weighted): the reference's half-step on the column problem whose rows are scaled by sqrt(c) --
+// G_j = c0 G_full + sum over the stored entries of (c_e - c0) y y^T, b_j = sum of c_e a_e y, c0 = 0 (absent = missing) or 1 (absent =
+// zero: the shared Gram of the fixed factor is formed first, raw, and the Gram kernels add it once per column).
 static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method,
                                     bool speculative)
 {
+    const bool shared_gram = h->sp_weighted && !h->sp_missing;
+    if (shared_gram) {
+        ProfScope ps(h, P_GRAM, h->stream);
+        launch_gram(h, s, 0, s.p);
+    }
     sp_cross(h, s);
     if (speculative) HIPCHK(h, hipEventRecord(h->ev_xdone, h->stream));
     h->cur_which = s.which;
@@ -3460,6 +3567,11 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
     g.Y = h->sp_Y;
     g.segoff = h->spg_segoff[o];
     g.G = h->spg_buf; // [chunk columns][slot], then the chunk's segment slots
+    if (h->sp_weighted) {
+        g.wt = s.sp_wt;
+        g.cw0 = shared_gram ? 1.0 : 0.0;
+        g.Gfull = shared_gram ? h->Graw : nullptr;
+    }
     const std::vector<long long> &hp = h->spg_hptr[o];
     for (const SpgChunk &ch : h->spg_plan[o]) {
         {
@@ -3544,9 +3656,15 @@ static int half_step_sparse_kl(nnlm_handle *h, const Side &s, const double reg[3
 static int half_step_sparse(nnlm_handle *h, const Side &s, const double reg[3], unsigned inner_max_iter, double inner_rel_tol, int method, bool speculative)
 {
     if (method >= 3 && h->sp_kl) return half_step_sparse_kl(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
+    if (method >= 3 && h->sp_weighted) return weighted_refusal(h, "half_step", "methods 3 and 4 (KL loss)");
     if (method >= 3)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     // (every entry stored: the reference's update(), src/update_with_missing.cpp:3-55 -- the shared Gram of the zero semantics)
+    // (per-entry weights: every column has a Gram of its own whatever an absent entry is, and whether or not anything is absent)
+    if (h->sp_weighted) {
+        if (h->k > NNLM_KQ_MAX) return weighted_refusal(h, "half_step", "a rank above 64");
+        return half_step_sparse_missing(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
+    }
     if (h->sp_missing && h->any_missing) return half_step_sparse_missing(h, s, reg, inner_max_iter, inner_rel_tol, method, speculative);
     {
         ProfScope ps(h, P_GRAM, h->stream);
@@ -3919,6 +4037,7 @@ extern "C" int nnlm_half_step(nnlm_handle *h, int which, const double reg[3], un
 extern "C" int nnlm_debug_partial(nnlm_handle *h, int which, double *G_out, double *C_out)
 {
     if (!h || !h->W64) return fail(h, NNLM_ERR_ARG, "nnlm_debug_partial: matrix and factors must be set first");
+    if (h->sparse && h->sp_weighted) return weighted_refusal(h, "nnlm_debug_partial", "the partial-sum hook");
     if (h->sparse) return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_debug_partial: the handle holds a sparse matrix (the hook reads the dense split-K slabs)");
     if (which != 0 && which != 1) return fail(h, NNLM_ERR_ARG, "nnlm_debug_partial: which must be 0 or 1");
     const double z[3] = {0, 0, 0};
@@ -4069,11 +4188,18 @@ static int errors_launch(nnlm_handle *h, hipStream_t st, bool with_sweeps, int f
         long long chunk = (h->nnz + nw - 1) / nw;
         if (chunk < 1) chunk = 1;
         const int eb = (nw / (64 / nnlm_sp_lanes(KP)) + 3) / 4;
-        nnlm_tu_sp_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, chunk, nw, h->sp_Wrow, KP, h->k, h->H64, h->mpad,
-                          h->sp_epart, eb, h->sp_missing, st);
-        reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)eb, 3, S);
-        if (h->sp_missing) nnlm_tu_sp_err_final_missing(S, h->scal, st);
-        else nnlm_tu_sp_err_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->scal, st);
+        if (h->sp_weighted) { // five weighted sums over the stored entries; the zeros of the zero semantics have weight 1 (k_sparse.h)
+            nnlm_tu_sp_errors_weighted(h->sp_cptr, h->sp_ridx, h->sp_cval, h->sp_cwt, h->prec == NNLM_PREC_F64, m, h->nnz, chunk, nw, h->sp_Wrow, KP,
+                                       h->k, h->H64, h->mpad, h->sp_epart, eb, st);
+            reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)eb, 5, S);
+            nnlm_tu_sp_err_final_weighted(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->sp_missing, h->scal, st);
+        } else {
+            nnlm_tu_sp_errors(h->sp_cptr, h->sp_ridx, h->sp_cval, h->prec == NNLM_PREC_F64, m, h->nnz, chunk, nw, h->sp_Wrow, KP, h->k, h->H64,
+                              h->mpad, h->sp_epart, eb, h->sp_missing, st);
+            reduce_partials_kernel<<<1, REDUCE_THREADS, 0, st>>>(h->sp_epart, (size_t)eb, 3, S);
+            if (h->sp_missing) nnlm_tu_sp_err_final_missing(S, h->scal, st);
+            else nnlm_tu_sp_err_final(S, G, G + (size_t)KP * KP, sums, sums + KP, h->k, KP, h->scal, st);
+        }
     } else {
         ProfScope ps(h, P_ERRORS, st);
         const uint32_t *miss = h->any_missing ? h->miss : nullptr;
@@ -4241,6 +4367,7 @@ extern "C" int nnlm_comm_init(nnlm_handle *h, const char id[NNLM_COMM_ID_BYTES],
 {
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "nnlm_comm_init: handle is NULL");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(h, NNLM_ERR_ARG, "nnlm_comm_init: bad rank %d of %d", rank, nranks);
+    if (h->sparse && h->sp_weighted) return weighted_refusal(h, "nnlm_comm_init", "a communicator (multi-GPU)");
     if (h->sparse && h->sp_kl)
         return fail(h, NNLM_ERR_UNSUPPORTED, "nnlm_comm_init: the handle holds a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl); the sparse KL "
                                              "path is single-GPU only");
@@ -4313,6 +4440,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "matrix_min_col_observed") == 0) return observed_min(h, 0, value);
     else if (strcmp(key, "matrix_min_row_observed") == 0) return observed_min(h, 1, value);
     else if (strcmp(key, "matrix_absent_missing") == 0) *value = (h->sparse && h->sp_missing) ? 1.0 : 0.0;
+    else if (strcmp(key, "sparse_weighted") == 0) *value = (h->sparse && h->sp_weighted) ? 1.0 : 0.0;
     else if (strcmp(key, "sparse_kl") == 0) *value = (h->sparse && h->sp_kl) ? 1.0 : 0.0;
     else if (strcmp(key, "sparse_batch") == 0) *value = (h->sparse && h->sp_batch) ? 1.0 : 0.0;
     else if (strcmp(key, "sp_batch_waves") == 0) *value = h->sparse ? nnlm_spb_waves(h->nnz, h->cus) : 0;
@@ -4579,6 +4707,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
                 n_trace, n_iteration, warned, cb};
     int rc = L.check("nnlm_run");
     if (rc != NNLM_OK) return rc;
+    if (h->sparse && method >= 3 && h->sp_weighted) return weighted_refusal(h, "nnlm_run", "methods 3 and 4 (KL loss)");
     if (h->sparse && method >= 3 && !h->sp_kl)
         return fail(h, NNLM_ERR_UNSUPPORTED, "method %d (KL loss) is not available for a sparse matrix: use loss = 'mse' (methods 1, 2) or a dense matrix", method);
     if (h->sparse && method >= 3 && h->k > NNLM_KQ_MAX) return spkl_rank_refusal(h, "nnlm_run");
@@ -4705,6 +4834,7 @@ extern "C" int nnlm_run(nnlm_handle *h, const double alpha[3], const double beta
 static_assert(SPB_BATCH_MAX == BATCH_MAX, "sp_batch_errors_kernel keeps one LDS slot per member");
 static int batch_refusal(nnlm_handle *h, const char *who)
 {
+    if (h->sparse && h->sp_weighted) return weighted_refusal(h, who, "the batched factorisation");
     if (h->sparse && h->sp_kl && !h->sp_batch)
         return fail(h, NNLM_ERR_UNSUPPORTED, "%s: a sparse matrix loaded for KL loss (nnlm_set_matrix_csc_kl) is not supported by the batched factorisation "
                                              "(dense A, square loss only)", who);
@@ -5757,6 +5887,20 @@ extern "C" int nnlm_c_nnmf_csc_missing(int n, int m, const long long *colptr, co
                        method, trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
 }
 
+extern "C" int nnlm_c_nnmf_csc_weighted(int n, int m, const long long *colptr, const int *rowidx, const double *x, const double *weight,
+                                        int absent_missing, unsigned k, const double *W_init, const double *H_init, const int *Wm, const int *Hm,
+                                        const double alpha[3], const double beta[3], unsigned max_iter, double rel_tol, int n_threads, int verbose,
+                                        int show_warning, unsigned inner_max_iter, double inner_rel_tol, int method, unsigned trace, double *W_out,
+                                        double *H_out, double *mse_error, double *mkl_error, double *target_error, double *average_epoch,
+                                        int *n_trace, unsigned *n_iteration, int *warned, const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    return c_nnmf_body("nnlm_c_nnmf_csc_weighted", colptr,
+                       [&](nnlm_handle *h) { return nnlm_set_matrix_csc_weighted(h, n, m, colptr, rowidx, x, weight, absent_missing); }, n, m, k,
+                       W_init, H_init, Wm, Hm, alpha, beta, max_iter, rel_tol, verbose, show_warning, inner_max_iter, inner_rel_tol, method,
+                       trace, W_out, H_out, mse_error, mkl_error, target_error, average_epoch, n_trace, n_iteration, warned, cb);
+}
+
 template <typename SetMatrix>
 static int c_nnlm_body(const char *who, const void *y, SetMatrix set_matrix, const double *x, int n, int p, int q, const double alpha[3],
                        const int *mask, const double *beta0, unsigned max_iter, double rel_tol, int method, double *coefficient, int *n_iteration,
@@ -5819,5 +5963,15 @@ extern "C" int nnlm_c_nnlm_csc_missing(const double *x, int n, int p, int q, con
     (void)n_threads;
     return c_nnlm_body("nnlm_c_nnlm_csc_missing", ycolptr, [&](nnlm_handle *h) { return nnlm_set_matrix_csc_missing(h, n, q, ycolptr, yrowidx, yx); },
                        x, n, p, q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
+}
+extern "C" int nnlm_c_nnlm_csc_weighted(const double *x, int n, int p, int q, const long long *ycolptr, const int *yrowidx, const double *yx,
+                                        const double *weight, int absent_missing, const double alpha[3], const int *mask, const double *beta0,
+                                        unsigned max_iter, double rel_tol, int n_threads, int method, double *coefficient, int *n_iteration,
+                                        const nnlm_callbacks *cb)
+{
+    (void)n_threads;
+    return c_nnlm_body("nnlm_c_nnlm_csc_weighted", ycolptr,
+                       [&](nnlm_handle *h) { return nnlm_set_matrix_csc_weighted(h, n, q, ycolptr, yrowidx, yx, weight, absent_missing); }, x, n, p,
+                       q, alpha, mask, beta0, max_iter, rel_tol, method, coefficient, n_iteration, cb);
 }
 #undef CHK

@@ -67,6 +67,32 @@ void nnlm_tu_sp_errors(const long long *ptr, const int *idx, const void *val, bo
     else launch_sp_errors_t<float, false>(ptr, idx, val, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
 }
 
+template <typename T>
+static void launch_sp_errors_weighted_t(const long long *ptr, const int *idx, const void *val, const void *wt, int ncols, long long nnz, long long chunk,
+                                        int nworkers, const double *Wrow, int KP, int k, const double *H, int ldh, double *partial, int nblocks,
+                                        hipStream_t st)
+{
+    const T *v = (const T *)val, *c = (const T *)wt;
+    switch (nnlm_sp_lanes(KP)) {
+    case 16: sp_errors_weighted_kernel<T, 16><<<nblocks, 256, 0, st>>>(ptr, idx, v, c, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    case 32: sp_errors_weighted_kernel<T, 32><<<nblocks, 256, 0, st>>>(ptr, idx, v, c, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    default: sp_errors_weighted_kernel<T, 64><<<nblocks, 256, 0, st>>>(ptr, idx, v, c, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial); break;
+    }
+}
+// (the caller sizes `partial`: 5 doubles per workgroup)
+void nnlm_tu_sp_errors_weighted(const long long *ptr, const int *idx, const void *val, const void *wt, bool f64, int ncols, long long nnz,
+                                long long chunk, int nworkers, const double *Wrow, int KP, int k, const double *H, int ldh, double *partial,
+                                int nblocks, hipStream_t st)
+{
+    if (f64) launch_sp_errors_weighted_t<double>(ptr, idx, val, wt, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+    else launch_sp_errors_weighted_t<float>(ptr, idx, val, wt, ncols, nnz, chunk, nworkers, Wrow, KP, k, H, ldh, partial, nblocks, st);
+}
+void nnlm_tu_sp_err_final_weighted(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP,
+                                   bool miss, double *out, hipStream_t st)
+{
+    sp_err_final_weighted_kernel<<<1, 256, 0, st>>>(s, GW, GH, wsum, hsum, k, KP, miss ? 1 : 0, out);
+}
+
 void nnlm_tu_sp_rowsums(const double *X, int ld, int ncols, int KP, double *partial, int nblocks, hipStream_t st)
 {
     sp_rowsum_partial_kernel<<<nblocks, 256, 0, st>>>(X, ld, ncols, KP, partial);
@@ -127,6 +153,11 @@ int nnlm_spg_workers(long long nnz, int cus)
 template <int NT> static void launch_sp_gram(const SpGramArgs &a, bool f64, hipStream_t st)
 {
     const int nb = (a.nworkers + 3) / 4;
+    if (a.wt) { // (per-entry weights: the WT form)
+        if (f64) sp_gram_kernel<double, NT, true><<<nb, 256, 0, st>>>(a);
+        else sp_gram_kernel<float, NT, true><<<nb, 256, 0, st>>>(a);
+        return;
+    }
     if (f64) sp_gram_kernel<double, NT><<<nb, 256, 0, st>>>(a);
     else sp_gram_kernel<float, NT><<<nb, 256, 0, st>>>(a);
 }

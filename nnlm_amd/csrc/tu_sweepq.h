@@ -68,6 +68,10 @@ struct SpGramArgs {
     int nworkers;
     double *G;              // [c1 - c0][KP][KP] per-column Grams (upper triangle)
     double *seg;            // segment sums of the launch's long columns, [segoff[c1] - segoff[c0]][KP][KP]
+    // weighted form (nnlm_set_matrix_csc_weighted): G_j = cw0 G_full + sum over the stored entries e of (wt[e] - cw0) y y^T
+    const void *wt = nullptr;      // [nnz] T, weight of each stored entry (NULL: the unweighted kernel)
+    double cw0 = 0.0;              // weight of an absent entry: 0 (missing) or 1 (a zero)
+    const double *Gfull = nullptr; // cw0 = 1: the shared Gram of the fixed factor [KP][KP], added once per column
 };
 // workers (one wavefront each) of one Gram launch over nnz stored entries: ~256 each, at most 16 wavefronts per CU
 int nnlm_spg_workers(long long nnz, int cus);
@@ -76,6 +80,15 @@ void nnlm_tu_sp_gram(const SpGramArgs &a, int NKQ, bool f64, hipStream_t st);
 void nnlm_tu_sp_gram_fixup(const SpGramArgs &a, const int *longc, int nlong, int KP, hipStream_t st);
 // out[0] = S1, out[1] = S3 + S2 (sum of squares, KL sum over the stored entries)
 void nnlm_tu_sp_err_final_missing(const double *s, double *out, hipStream_t st);
+// Per-entry weights (nnlm_set_matrix_csc_weighted): wt [nnz] T beside val; partial holds FIVE sums per workgroup --
+// {sum c r^2, sum wh^2, sum c (-(a + eps) log(wh + eps)), sum c wh, sum wh} over the stored entries
+void nnlm_tu_sp_errors_weighted(const long long *ptr, const int *idx, const void *val, const void *wt, bool f64, int ncols, long long nnz,
+                                long long chunk, int nworkers, const double *Wrow, int KP, int k, const double *H, int ldh, double *partial,
+                                int nblocks, hipStream_t st);
+// s = those five sums.  miss: out[0] = s0, out[1] = s2 + s3.  Otherwise (absent entries are zeros of weight 1)
+// out[0] = s0 + max(0, <W^T W, H H^T> - s1), out[1] = s2 + sum_q (sum_i W_iq)(sum_j H_qj) + (s3 - s4)
+void nnlm_tu_sp_err_final_weighted(const double *s, const double *GW, const double *GH, const double *wsum, const double *hsum, int k, int KP,
+                                   bool miss, double *out, hipStream_t st);
 
 // Batched factorisation on such a matrix (k_sparse_na_batch.h): the Grams of all members in one launch.  g.Y is the row copy at the
 // STACKED KP; column c's Grams take `slot` doubles of g.G (member b's at goff_b, compact at its own KP_b), a segment of a long column
