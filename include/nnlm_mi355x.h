@@ -590,6 +590,11 @@ int nnlm_kl_plan(int p, int k, int precision, int mask_words, int out[8]);
  * "do not fit" when they exceed `bytes` (0 = no limit): the half-step then takes its smaller-footprint path -- the streaming kernel
  * over column chunks -- exactly as it does when hipMalloc itself says no. */
 int nnlm_debug_alloc_limit(size_t bytes);
+/* Test hook: while `on` is not 0, a per-column Gram buffer (missing values: the dense path's buffer of one KP x KP block per column, the
+ * chunk buffer of the sparse doors whose absent entries are missing or weighted) is filled with 0xFF bytes -- every double a NaN -- when
+ * it is allocated, on the handle's stream, ahead of its first use.  The Gram kernels write the upper triangle up to k of a block and
+ * nothing else; results must not depend on what the rest holds.  Off (the default) it costs one branch per allocation. */
+int nnlm_debug_poison_workspaces(int on);
 /* Facts about the handle's last launches, for bench.py's kernel attribution: key = "cus" (compute units the launch policy
  * counts), "xprod_waves_w" / "xprod_waves_h" and "xprod_splits_w" / "xprod_splits_h" (wavefronts per block and split-K slabs of the last
  * xprod16_tn_kernel launch of the W / H half-step, 0 none yet), "xprod_splits_err" (slabs of the last xprod16_err_kernel launch, 0 none yet),
@@ -599,7 +604,13 @@ int nnlm_debug_alloc_limit(size_t bytes);
  * "sweep_groups_h" (column groups -- form 2: wavefronts -- per workgroup of that launch), "lee_lanes_w" / "lee_lanes_h" and
  * "lee_regs_w" / "lee_regs_h" (Lee's multiplicative updates at ranks up to 64: lanes per column L -- 4, 2 or 1, chosen from the END column
  * of the launch -- and coordinate registers per lane R of the sweep_ls_kernel<R, L, 2> launch of the last W / H half-step, -1 none
- * yet), "kl_form_w" / "kl_form_h" (KL solver of the last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
+ * yet), "na_solver_w" / "na_solver_h" (square loss with missing values -- every column solves with a Gram of its own --: family of the last
+ * per-column solver launch of the W / H half-step: 0 colsolve_row_kernel, 1 colsolve_strict_kernel, 2 colsolve_ls_kernel, 3
+ * sweep_generic_kernel with per-column Grams (rank > 64), -1 none yet), "na_solver_kr_w" / "na_solver_kr_h" (the KR of that instantiation;
+ * colsolve_ls_kernel: 16 NKQ; sweep_generic_kernel: k), "na_gram_w" / "na_gram_h" (family of the last per-column Gram launch of the W / H
+ * half-step: 0 na_gram_f16_kernel, 1 na_gram_lds_kernel, 2 na_gram_lds_kernel in its tail form, 3 sp_gram_kernel, 4
+ * na_gram_generic_kernel, -1 none yet), "na_gram_nt_w" / "na_gram_nt_h" (the NT / NKQ of that instantiation),
+ * "kl_form_w" / "kl_form_h" (KL solver of the last W / H half-step: 0 kl_tile_kernel on the starting states of the wh_store GEMM, 1 kl_tile_kernel forming its own starting states
  * -- no room for the matrix-sized buffer --, 2 kl_reg64_kernel (strict), 3 kl_stream_kernel over column chunks, -1 none yet),
  * "kl_pieces_w" / "kl_pieces_h" and "kl_cols_w" / "kl_cols_h" (instantiated pieces per thread and columns per block of the kl_tile_kernel
  * or kl_reg64_kernel launch of the last W / H half-step -- out[2] and out[3] of nnlm_kl_plan --, 0 when it streamed, -1 none yet),

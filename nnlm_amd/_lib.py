@@ -32,7 +32,7 @@ EXPORTS = [
     "nnlm_half_step", "nnlm_iterate", "nnlm_run", "nnlm_take_sweeps", "nnlm_errors", "nnlm_sync", "nnlm_profile_enable",
     "nnlm_profile_get", "nnlm_profile_reset", "nnlm_comm_unique_id", "nnlm_comm_init", "nnlm_comm_info",
     "nnlm_shard_range", "nnlm_shard_cols", "nnlm_debug_partial", "nnlm_debug_phase", "nnlm_debug_exchange",
-    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_debug_set_a_stream", "nnlm_xprod_plan", "nnlm_kl_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_release_caches",
+    "nnlm_comm_set_form", "nnlm_debug_set_cus", "nnlm_debug_set_xprod_waves", "nnlm_debug_set_a_stream", "nnlm_xprod_plan", "nnlm_kl_plan", "nnlm_get_info", "nnlm_debug_alloc_limit", "nnlm_debug_poison_workspaces", "nnlm_release_caches",
     "nnlm_set_matrix_csc", "nnlm_c_nnmf_csc", "nnlm_c_nnlm_csc",
     "nnlm_set_matrix_csc_missing", "nnlm_c_nnmf_csc_missing", "nnlm_c_nnlm_csc_missing",
     "nnlm_set_matrix_csc_kl", "nnlm_c_nnmf_csc_kl", "nnlm_c_nnlm_csc_kl",
@@ -196,6 +196,8 @@ def load():
     lib.nnlm_kl_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip]
     lib.nnlm_debug_alloc_limit.restype = C.c_int
     lib.nnlm_debug_alloc_limit.argtypes = [C.c_size_t]
+    lib.nnlm_debug_poison_workspaces.restype = C.c_int
+    lib.nnlm_debug_poison_workspaces.argtypes = [C.c_int]
     lib.nnlm_release_caches.restype = C.c_int
     lib.nnlm_release_caches.argtypes = []
     lib.nnlm_get_info.restype = C.c_int
@@ -1183,6 +1185,10 @@ class Handle:
         kl_form_w / kl_form_h (KL solver of the last half-step: 0 tile, 1 tile on its own starting states, 2 reg64, 3 streaming, -1 none yet),
         kl_pieces_w / kl_pieces_h and kl_cols_w / kl_cols_h (instantiated pieces per thread and columns per block of that launch as in
         kl_plan(); 0 streaming, -1 none yet),
+        na_solver_w / na_solver_h and na_solver_kr_w / na_solver_kr_h (missing values: family -- 0 colsolve_row, 1 colsolve_strict, 2
+        colsolve_ls, 3 sweep_generic -- and KR of the last per-column solver launch, -1 none yet), na_gram_w / na_gram_h and na_gram_nt_w /
+        na_gram_nt_h (family -- 0 na_gram_f16, 1 na_gram_lds, 2 its tail form, 3 sp_gram, 4 na_gram_generic -- and NT of the last
+        per-column Gram launch, -1 none yet),
         sp_ingest_check_share / sp_ingest_sort_tile (stored entries per workgroup of the entry check / of a radix pass of
         set_matrix_sparse_device),
         matrix_nnz (-1 for a dense matrix), matrix_bytes, matrix_min_col_observed / matrix_min_row_observed (fewest finite entries of a
@@ -1277,6 +1283,12 @@ def kl_plan(p, k, precision, mask_words=0):
 def debug_alloc_limit(nbytes: int):
     """Test hook: matrix-sized KL workspaces beyond `nbytes` "do not fit" (0 = no limit) -> the streaming path over column chunks."""
     _check(load().nnlm_debug_alloc_limit(int(nbytes)))
+
+
+def debug_poison_workspaces(on: int):
+    """Test hook: while on, a newly allocated per-column Gram buffer (missing values) is filled with 0xFF bytes -- NaN in every double the
+    Gram kernels do not write.  Process-global; reset it in a `finally`."""
+    _check(load().nnlm_debug_poison_workspaces(int(on)))
 
 
 def comm_unique_id() -> bytes:

@@ -192,7 +192,8 @@ __global__ __launch_bounds__(256, (KR * CPL > 208) ? 1 : 2) void colsolve_row_ke
         for (int rr = 0; rr < CPL; rr++) {
             const int q = CPL * l + rr;
             if (lv[rr]) {
-                const double xo = (msk[rr] || skip) ? a.X[(size_t)q * a.ldx + col] : (double)xfin[rr]; // (masked: the fp64 input, unchanged)
+                // (masked, or no sweep ran -- an inner limit of 0 --: the fp64 input, unchanged, not its fp32 rounding)
+                const double xo = (msk[rr] || skip || t_col == 0) ? a.X[(size_t)q * a.ldx + col] : (double)xfin[rr];
                 a.Xout[(size_t)q * a.ldo + (col - a.ocol0)] = xo;
                 if (a.op_mode == 1) {
                     if (a.op_f64) ((double *)a.op)[(size_t)q * a.op_ld + col] = xo;

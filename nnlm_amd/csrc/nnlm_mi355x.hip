@@ -98,6 +98,10 @@ struct nnlm_handle {
     int sweep_form[2] = {-1, -1}, sweep_groups[2] = {0, 0}; // per half-step (0: W, 1: H): form of its last SCD sweep launch (0 plain, 1 persistent) and
                                                              // column groups per workgroup (nnlm_get_info)
     int lee_lanes[2] = {-1, -1}, lee_regs[2] = {-1, -1};    // per half-step: L and R of its last sweep_ls_kernel<R, L, 2> launch (nnlm_get_info)
+    // per half-step, the last launches with per-column Grams (missing values; nnlm_get_info "na_solver_*", "na_gram_*"): the solver's family
+    // (0 colsolve_row_kernel, 1 colsolve_strict_kernel, 2 colsolve_ls_kernel, 3 sweep_generic_kernel) and KR, the Gram kernel's family
+    // (0 na_gram_f16_kernel, 1 na_gram_lds_kernel, 2 its tail form, 3 sp_gram_kernel, 4 na_gram_generic_kernel) and NT / NKQ
+    int na_solver[2] = {-1, -1}, na_solver_kr[2] = {-1, -1}, na_gram[2] = {-1, -1}, na_gram_nt[2] = {-1, -1};
     int prec = NNLM_PREC_F32;
     hipStream_t stream = nullptr;   // main: cross products, solvers
     hipStream_t stream_e = nullptr; // error block, concurrent with the (speculative) next W half-step
@@ -534,6 +538,22 @@ extern "C" int nnlm_debug_alloc_limit(size_t bytes)
 {
     g_debug_alloc_limit = bytes;
     return NNLM_OK;
+}
+
+static std::atomic<int> g_debug_poison{0}; // nnlm_debug_poison_workspaces (test hook): new per-column Gram buffers are filled with 0xFF bytes (every double a NaN)
+
+extern "C" int nnlm_debug_poison_workspaces(int on)
+{
+    g_debug_poison = on ? 1 : 0;
+    return NNLM_OK;
+}
+
+// A per-column Gram buffer that was just allocated: the Gram kernels write the upper triangle up to k of every KP x KP block and nothing
+// else, so the rest holds whatever the allocation held.  The test hook makes that NaN, on the handle's stream, ahead of the first use.
+static hipError_t poison_new_gram(void *p, size_t bytes, hipStream_t st)
+{
+    if (!g_debug_poison.load(std::memory_order_relaxed)) return hipSuccess;
+    return hipMemsetAsync(p, 0xFF, bytes, st);
 }
 
 extern "C" int nnlm_debug_set_xprod_waves(int waves)
@@ -3040,29 +3060,37 @@ static bool colsolve_fast_ok(const nnlm_handle *h, int method)
 }
 
 template <int NKQ>
-static void launch_colsolve_strict_m(const SweepArgs &a, size_t g_stride, hipStream_t s)
+static int launch_colsolve_strict_m(const SweepArgs &a, size_t g_stride, hipStream_t s) // returns the KR of its instantiation
 {
     const int nb = (a.ncols - a.col0 + 3) / 4;
-    if (nb <= 0) return;
     constexpr int KS = NKQ > 1 ? 16 * (NKQ - 1) + 4 : 16;
     if (NKQ > 1 && a.k <= KS) {
+        if (nb <= 0) return KS;
         if (a.mask) colsolve_strict_kernel<NKQ, true, KS><<<nb, 256, 0, s>>>(a, g_stride);
         else colsolve_strict_kernel<NKQ, false, KS><<<nb, 256, 0, s>>>(a, g_stride);
-        return;
+        return KS;
     }
+    if (nb <= 0) return 16 * NKQ;
     if (a.mask) colsolve_strict_kernel<NKQ, true><<<nb, 256, 0, s>>>(a, g_stride);
     else colsolve_strict_kernel<NKQ, false><<<nb, 256, 0, s>>>(a, g_stride);
+    return 16 * NKQ;
 }
 static void launch_colsolve(nnlm_handle *h, int method, const SweepArgs &a, size_t g_stride)
 {
     if (colsolve_fast_ok(h, method)) {
+        h->na_solver[h->cur_which] = 0;
+        h->na_solver_kr[h->cur_which] = a.k <= 48 ? 16 * ((a.k + 15) / 16) : (a.k <= 50 ? 50 : 64); // (the classes of nnlm_tu_colsolve_row)
         nnlm_tu_colsolve_row(a, g_stride, h->stream);
         return;
     }
     // SCD in the reference's arithmetic (strict mode): the unrolled lane-local form; Lee's updates: colsolve_lee_kernel
+    h->na_solver[h->cur_which] = method == 1 ? 1 : 2;
     with_nkq(h->NKQ, [&](auto N) {
-        if (method == 1) launch_colsolve_strict_m<N>(a, g_stride, h->stream);
-        else launch_colsolve_m<N>(a, g_stride, h->stream);
+        if (method == 1) h->na_solver_kr[h->cur_which] = launch_colsolve_strict_m<N>(a, g_stride, h->stream);
+        else {
+            launch_colsolve_m<N>(a, g_stride, h->stream);
+            h->na_solver_kr[h->cur_which] = 16 * N;
+        }
     });
 }
 
@@ -3117,7 +3145,11 @@ static int ensure_yrow(nnlm_handle *h)
 }
 static int ensure_gcols(nnlm_handle *h)
 {
-    if (!h->Gcols) HIPCHK(h, hipMalloc(&h->Gcols, (size_t)(h->n > h->m ? h->n : h->m) * h->KP * h->KP * 8));
+    if (!h->Gcols) {
+        const size_t bytes = (size_t)(h->n > h->m ? h->n : h->m) * h->KP * h->KP * 8;
+        HIPCHK(h, hipMalloc(&h->Gcols, bytes));
+        HIPCHK(h, poison_new_gram(h->Gcols, bytes, h->stream));
+    }
     return NNLM_OK;
 }
 static int ensure_sg_slabs(nnlm_handle *h)
@@ -3157,6 +3189,7 @@ static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1, const d
         // [p + 64 rows][64 hi | 64 lo halves]; rows p .. are zero (the kernel's "no row" index)
         factor16c_kernel<<<p / 64 + 1, 256, 0, h->stream>>>(Y, s.ldy, p, h->k, maxw, h->scal_exp + 3, (uint32_t *)h->Yrow);
         const int nb = (nc + 3) / 4;
+        h->na_gram[s.which] = 0, h->na_gram_nt[s.which] = h->NKQ;
         with_nkq(h->NKQ, [&](auto N) {
             na_gram_f16_kernel<N><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const uint32_t *)h->Yrow, p, h->scal_exp + 3, Gfull, h->Gcols, c1, c0, h->k);
         });
@@ -3167,6 +3200,7 @@ static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1, const d
     if (generic_rank(h)) { // rank > 64: k_generic.h
         const int lds = 16 * h->KP * 8;
         na_gram_generic_kernel<<<nc, 256, lds, h->stream>>>(ptr, meta, idx, h->Yrow, h->KP, Gfull, h->Gcols, c0);
+        h->na_gram[s.which] = 4, h->na_gram_nt[s.which] = h->NKQ;
         return NNLM_OK;
     }
     // strict mode: fp64 rows gathered by LDS-DMA, v_mfma_f64_16x16x4_f64 (k_missing.h, na_gram_lds_kernel); tail form for k = 16 j + 1, + 2
@@ -3175,6 +3209,7 @@ static int launch_na_gram(nnlm_handle *h, const Side &s, int c0, int c1, const d
     const bool tl = h->NKQ >= 2 && (ntail == 1 || ntail == 2);
     with_nkq(h->NKQ, [&](auto N) {
         auto go = [&](auto nt, auto tail) {
+            h->na_gram[s.which] = tail ? 2 : 1, h->na_gram_nt[s.which] = nt; // (the instantiation itself)
             na_gram_lds_kernel<double, nt, tail><<<nb, 256, 0, h->stream>>>(ptr, meta, idx, (const double *)h->Yrow, Gfull, h->Gcols, c1, c0, h->k);
         };
         if constexpr (N == 1) go(N, std::false_type{});
@@ -3533,6 +3568,7 @@ static int spg_prepare(nnlm_handle *h, int o, size_t slot)
         h->spg_buf_bytes = 0;
         HIPCHK(h, hipMalloc(&h->spg_buf, need));
         h->spg_buf_bytes = need;
+        HIPCHK(h, poison_new_gram(h->spg_buf, need, h->stream));
     }
     return NNLM_OK;
 }
@@ -3585,6 +3621,7 @@ static int half_step_sparse_missing(nnlm_handle *h, const Side &s, const double 
             g.chunk = (nnz + g.nworkers - 1) / g.nworkers;
             if (g.chunk < 1) g.chunk = 1;
             nnlm_tu_sp_gram(g, h->NKQ, h->prec == NNLM_PREC_F64, h->stream);
+            h->na_gram[o] = 3, h->na_gram_nt[o] = h->NKQ;
             nnlm_tu_sp_gram_fixup(g, h->spg_longc[o] + ch.l0, ch.l1 - ch.l0, KP, h->stream);
         }
         ProfScope ps(h, s.prof_sweep);
@@ -3998,6 +4035,7 @@ static int half_step_solve(nnlm_handle *h, const Side &s, const double reg[3], u
             if (generic_rank(h)) {
                 int rcs = launch_sweep_generic(h, method, a, (size_t)h->KP * h->KP);
                 if (rcs != NNLM_OK) return rcs;
+                h->na_solver[s.which] = 3, h->na_solver_kr[s.which] = h->k;
             } else
                 launch_colsolve(h, method, a, (size_t)h->KP * h->KP);
         } else if (a.ncols > a.col0) {
@@ -4428,6 +4466,14 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "lee_lanes_h") == 0) *value = h->lee_lanes[1];
     else if (strcmp(key, "lee_regs_w") == 0) *value = h->lee_regs[0];
     else if (strcmp(key, "lee_regs_h") == 0) *value = h->lee_regs[1];
+    else if (strcmp(key, "na_solver_w") == 0) *value = h->na_solver[0]; // (last launches with per-column Grams: see nnlm_handle::na_solver)
+    else if (strcmp(key, "na_solver_h") == 0) *value = h->na_solver[1];
+    else if (strcmp(key, "na_solver_kr_w") == 0) *value = h->na_solver_kr[0];
+    else if (strcmp(key, "na_solver_kr_h") == 0) *value = h->na_solver_kr[1];
+    else if (strcmp(key, "na_gram_w") == 0) *value = h->na_gram[0];
+    else if (strcmp(key, "na_gram_h") == 0) *value = h->na_gram[1];
+    else if (strcmp(key, "na_gram_nt_w") == 0) *value = h->na_gram_nt[0];
+    else if (strcmp(key, "na_gram_nt_h") == 0) *value = h->na_gram_nt[1];
     else if (strcmp(key, "kl_form_w") == 0) *value = h->kl_form[0];
     else if (strcmp(key, "kl_form_h") == 0) *value = h->kl_form[1];
     else if (strcmp(key, "kl_pieces_w") == 0) *value = h->kl_pieces[0]; // (instantiated pieces per thread / columns per block of the last
@@ -5129,7 +5175,9 @@ static int batch_half_step(nnlm_handle *h, int which, const double reg[3], unsig
         if (!h->Gcols) {
             int kpm = 16;
             for (int b = 0; b < h->bB; b++) kpm = kpm > 16 * ((h->bk[b] + 15) / 16) ? kpm : 16 * ((h->bk[b] + 15) / 16);
-            HIPCHK(h, hipMalloc(&h->Gcols, (size_t)(h->n > h->m ? h->n : h->m) * kpm * kpm * 8));
+            const size_t bytes = (size_t)(h->n > h->m ? h->n : h->m) * kpm * kpm * 8;
+            HIPCHK(h, hipMalloc(&h->Gcols, bytes));
+            HIPCHK(h, poison_new_gram(h->Gcols, bytes, h->stream));
         }
     }
     // 1. one cross product for all members: split-fp16 copy of the whole stacked factor (ONE scale, max over all members), then the

@@ -202,7 +202,7 @@ def oracle_chain(ref, k, variant, w_setting, h_setting=None, reverse=False, n=N)
     return W, itw, H, ith
 
 
-def stop_slack(ref, c, which, X, X_ref, W_fixed, setting, bar):
+def stop_slack(ref, c, which, X, X_ref, W_fixed, setting, bar, oracles=None):
     """For the fp32-operand mode at the LOOSE setting.  There the sweep at which a column stops is tolerance-only.  The
     quantity compared with the tolerance is the largest relative change of a sweep, max over the coordinates of 2 |d| / (x + x' + eps),
     and a coordinate that enters or leaves zero changes by 2 whatever its size: whether a coordinate at a thousandth of the column's
@@ -212,11 +212,13 @@ def stop_slack(ref, c, which, X, X_ref, W_fixed, setting, bar):
     column by percents; no fp32 chain can promise otherwise.  So where a factor misses the bar against the oracle's result, every
     column (of the solved factor X; `which` = 0: rows of W, 1: columns of H) that misses it is held to the bar against the oracle's own
     trajectory -- the oracle's column after exactly t sweeps, t = 1 .. the limit -- at the sweep that fits best.
-    Returns (relative Frobenius deviation under that allowance, the columns that took another sweep than the oracle's stopping sweep)."""
+    Returns (relative Frobenius deviation under that allowance, the columns that took another sweep than the oracle's stopping sweep).
+    oracles: (oracle_w, oracle_h) of another family of cases with the signatures of this module's (tests/na_solver_cases.py)."""
     inner, tol = setting
+    ow, oh = oracles or (oracle_w, oracle_h)
     traj = []
     for t in range(inner + 1):  # the oracle's factor after exactly t sweeps of every live column (a negative tolerance never stops)
-        traj.append(oracle_w(ref, c, t, -1.0)[0] if which == 0 else oracle_h(ref, c, W_fixed, t, -1.0)[0].T)
+        traj.append(ow(ref, c, t, -1.0)[0] if which == 0 else oh(ref, c, W_fixed, t, -1.0)[0].T)
     G, R = (X, X_ref) if which == 0 else (X.T, X_ref.T)  # one column of the half-step per row
     total, flipped = 0.0, []
     for j in range(G.shape[0]):
