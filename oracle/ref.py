@@ -40,6 +40,8 @@ def lib():
         _LIB.ref_update.argtypes = [dp, dp, dp, ip, dp, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_double, C.c_int, C.c_int]
         _LIB.ref_update_with_missing.restype = C.c_int
         _LIB.ref_update_with_missing.argtypes = _LIB.ref_update.argtypes
+        _LIB.ref_scd_ls_update.restype = C.c_int
+        _LIB.ref_scd_ls_update.argtypes = [dp, dp, dp, ip, C.c_int, C.c_uint, C.c_double]
     return _LIB
 
 
@@ -74,6 +76,16 @@ def update(H, Wt, A, mask, beta, max_iter, rel_tol, method, n_threads=0, missing
     fn = lib().ref_update_with_missing if missing else lib().ref_update
     it = fn(_dp(H), _dp(Wt), _dp(A), _ip(mk), _dp(b), k, n, m, int(max_iter), float(rel_tol), int(n_threads), int(method))
     return H, it
+
+
+def scd_ls_update(Hj, WtW, mu, mask, max_iter, rel_tol):
+    """The per-column SCD solver on a given Gram (src/base_algorithms.cpp:3-37), the signature of nnlm_oracle.scd_ls_update: Hj (k,) and
+    mu (k,), contiguous fp64, are updated in place; WtW symmetric k x k; mask (k,) or None.  Returns the sweeps."""
+    k = Hj.shape[0]
+    assert Hj.dtype == np.float64 and mu.dtype == np.float64 and Hj.flags.c_contiguous and mu.flags.c_contiguous and WtW.shape == (k, k)
+    G = _f(WtW)
+    mk = None if mask is None or np.size(mask) == 0 else np.array(np.asarray(mask).reshape(k) != 0, dtype=np.int32)
+    return int(lib().ref_scd_ls_update(_dp(Hj), _dp(G), _dp(mu), _ip(mk), k, int(max_iter), float(rel_tol)))
 
 
 def c_nnmf(A, k, W, H, Wm, Hm, alpha, beta, max_iter, rel_tol, n_threads, verbose, show_warning,

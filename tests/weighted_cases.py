@@ -72,9 +72,9 @@ def dense_parts(S, weights, absent):
     return A, C, obs
 
 
-def half_step(H, Wt, A, C, obs, mask, reg, max_iter, rel_tol, method, missing):
+def half_step(H, Wt, A, C, obs, mask, reg, max_iter, rel_tol, method, missing, counts=None):
     """One half-step for H (k x m) with Wt (k x n) fixed: the C oracle on the sqrt(c)-scaled one-column problem of every column.
-    Returns (H_new, sweeps)."""
+    Returns (H_new, sweeps).  counts: a list that receives the sweeps of every column."""
     H = np.array(H, dtype=np.float64, copy=True)
     Wt = np.asarray(Wt, dtype=np.float64)
     total = 0
@@ -87,6 +87,8 @@ def half_step(H, Wt, A, C, obs, mask, reg, max_iter, rel_tol, method, missing):
         hj, it = ref.update(H[:, j:j + 1], Wt * sc[None, :], y[:, None], mj, reg, max_iter, rel_tol, method, missing=missing)
         H[:, j] = hj[:, 0]
         total += it
+        if counts is not None:
+            counts.append(int(it))
     return H, total
 
 
