@@ -367,6 +367,34 @@ int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_sparse *A, int 
  * by rows, ptr_out [n + 1], idx_out = columns; idx_out and val_out [nnz]), values widened to fp64.  A NULL output = not wanted.
  * NNLM_ERR_ARG when the handle holds no sparse matrix. */
 int nnlm_debug_sparse_resident(nnlm_handle *h, int side, long long *ptr_out, int *idx_out, double *val_out);
+/* nnlm_set_matrix_csc_weighted for a sparse A AND its weights in device memory.  A is what
+ * nnlm_set_matrix_sparse_device takes.  Wt carries the weights: Wt->val holds Wt->nnz weights of any of the four NNLM_DT_* types, chosen
+ * independently of A's (not NULL when nnz > 0), and
+ *   - Wt->ptr == NULL and Wt->idx == NULL: the weights are in the order of A->val, Wt->nnz must equal A->nnz (the other fields are unused);
+ *   - both given: Wt is a sparse matrix of A's layout and shape, with integer types of its own, whose stored pattern must equal A's.  A
+ *     kernel compares the pattern (pointers, then indices) before any weight is read; a difference is NNLM_ERR_ARG naming the first
+ *     line that differs;
+ *   - one NULL and the other not, or Wt->layout != A->layout in the second form: NNLM_ERR_ARG.
+ * absent_missing as in nnlm_set_matrix_csc_weighted (the weighted handle has no batch and no KL door).  `stream`: the one stream on which
+ * both descriptors' arrays were produced.
+ *
+ * The handle afterwards is the one nnlm_set_matrix_csc_weighted leaves for the fp64 widening of the same values and weights: the six
+ * structural arrays, the weights and the products c a of both sides (c a is ONE fp64 multiply of the widenings, then rounded to the mode's
+ * type), nnz, n_non_missing, any_missing, the byte count, the long-column tables of both orientations, "sparse_weighted"; kl_const is the
+ * weighted constant up to summation order; the observed minima answer as after nnlm_set_matrix_sparse_device.
+ *
+ * Refusals, in this order, each leaving the handle's previous matrix and factors untouched: (1) arguments, descriptors and the
+ * device-memory rules of all arrays of both descriptors; (2) A's pointers; (3) A's entries -- all as nnlm_set_matrix_sparse_device, so
+ * an offence of A anywhere wins over a weight offence at an earlier entry; (4) the pattern of the weights; (5) the first weight that is
+ * not a finite number >= 0, worded as the host entry words it (entry number in the given layout's order; -0.0 is legal); (6)
+ * NNLM_PREC_F32's range rules in the host entry's order and words: entries with |a|, c or |c a| beyond the fp32 range, max |A| too small,
+ * max |weight * A| too small (NNLM_ERR_UNSUPPORTED).  Temporaries: at most 37.1 bytes per stored entry beside the ten new resident arrays
+ * (DESIGN section 4.24). */
+int nnlm_set_matrix_sparse_device_weighted(nnlm_handle *h, const nnlm_dev_sparse *A, const nnlm_dev_sparse *Wt, int n, int m, int absent_missing,
+                                           void *stream);
+/* TEST HOOK, the sibling of nnlm_debug_sparse_resident: the resident weights (wt_out [nnz]) and products c a (wa_out [nnz]) of one side,
+ * widened to fp64.  A NULL output = not wanted.  NNLM_ERR_ARG on a handle without per-entry weights. */
+int nnlm_debug_sparse_resident_weighted(nnlm_handle *h, int side, double *wt_out, double *wa_out);
 
 /*
  * One half-step = update()/update_with_missing() (reference src/update_with_missing.cpp:3-55, :58-139).
@@ -619,7 +647,8 @@ int nnlm_debug_poison_workspaces(int on);
  * n / m without missing entries; counted on the device at the first query; -1 on a sparse handle loaded from host arrays; on one loaded
  * by nnlm_set_matrix_sparse_device the fewest stored entries of a column / row when absent entries are missing, else n / m),
  * "sp_ingest_check_share" / "sp_ingest_sort_tile" (stored entries per workgroup of the entry check and of a radix pass of
- * nnlm_set_matrix_sparse_device: constants of the build),
+ * nnlm_set_matrix_sparse_device: constants of the build), "debug_sparse_values_address" (TEST HOOK: the device address of the resident
+ * by-column values of a sparse handle -- exact in a double --, -1 without one: a buffer of the handle for the aliasing rule's tests),
  * "matrix_absent_missing" (1 after nnlm_set_matrix_csc_missing, else 0), "sp_gram_chunks" / "sp_gram_bytes" (column chunks of the last
  * half-step on such a handle, device bytes of the per-column Gram buffer), "sp_workers" (workers -- groups of 16, 32 or 64 lanes, each
  * owning a range of non-zeros -- of one spmm_kernel launch on the resident sparse matrix at the current rank, 0 without one),

@@ -45,6 +45,7 @@ EXPORTS = [
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
     "nnlm_set_matrix_sparse_device", "nnlm_debug_sparse_resident",
     "nnlm_set_matrix_csc_weighted", "nnlm_c_nnmf_csc_weighted", "nnlm_c_nnlm_csc_weighted",
+    "nnlm_set_matrix_sparse_device_weighted", "nnlm_debug_sparse_resident_weighted",
     "nnlm_svd", "nnlm_get_svd", "nnlm_set_factors_nndsvd", "nnlm_set_factors_nndsvd_batch", "nnlm_debug_set_svd_rotate",
 ]
 NNDSVD_VARIANTS = {"nndsvd": 0, "nndsvda": 1}
@@ -243,6 +244,10 @@ def load():
     lib.nnlm_set_matrix_sparse_device.argtypes = [vp, C.POINTER(DevSparse), C.c_int, C.c_int, C.c_int, vp]
     lib.nnlm_debug_sparse_resident.restype = C.c_int
     lib.nnlm_debug_sparse_resident.argtypes = [vp, C.c_int, lp, ip, dp]
+    lib.nnlm_set_matrix_sparse_device_weighted.restype = C.c_int
+    lib.nnlm_set_matrix_sparse_device_weighted.argtypes = [vp, C.POINTER(DevSparse), C.POINTER(DevSparse), C.c_int, C.c_int, C.c_int, vp]
+    lib.nnlm_debug_sparse_resident_weighted.restype = C.c_int
+    lib.nnlm_debug_sparse_resident_weighted.argtypes = [vp, C.c_int, dp, dp]
     lib.nnlm_predict_entries.restype = C.c_int
     lib.nnlm_predict_entries.argtypes = [vp, C.c_longlong, ip, ip, dp]
     lib.nnlm_svd.argtypes = [vp, C.c_uint, C.c_uint, dp]
@@ -479,6 +484,23 @@ def dev_sparse(ptr, idx, val, shape, layout, device=None):
         raise _dev_restrict("idx has %d entries, val has %d" % (il, vl))
     stream = next((s for s in (s0, s1, s2) if s is not None), None)
     return DevSparse(pp, ip_ or None, vp_ or None, pt, it, vt, SP_LAYOUTS[layout], il), (ptr, idx, val), (n, m), stream
+
+
+def dev_sparse_weights(weights, nnz, shape, layout, device=None):
+    """(DevSparse, keep-alive, stream or None) of the weights of a sparse matrix in device memory with nnz stored entries: a 1-D
+    floating array of nnz weights in the order of the matrix's values, or a (ptr, idx, val) triple -- a sparse matrix of the same layout
+    and shape whose pattern the library compares with the matrix's.  The ValueErrors of dev_sparse, before any device call."""
+    if isinstance(weights, (tuple, list)):
+        if len(weights) != 3:
+            raise _dev_restrict("weights must be a 1-D array of nnz weights or a (ptr, idx, val) triple (got %d items)" % len(weights))
+        d, keep, _, stream = dev_sparse(weights[0], weights[1], weights[2], shape, layout, device)
+        return d, keep, stream
+    if layout not in SP_LAYOUTS:
+        raise ValueError(f"layout must be 'csc' or 'csr' (got {layout!r})")
+    wp, wt, wl, stream = _dev_vector(weights, "weights", "float", device)
+    if wl != int(nnz):
+        raise _dev_restrict("weights has %d entries, val has %d" % (wl, int(nnz)))
+    return DevSparse(None, None, wp or None, IT_I32, IT_I32, wt, SP_LAYOUTS[layout], wl), weights, stream
 
 
 def sparse_tensor_parts(A):
@@ -973,6 +995,29 @@ class Handle:
         self._ck(self._lib.nnlm_set_matrix_sparse_device(self._h, C.byref(d), n, m, door, C.c_void_p(st)))
         self.n, self.m = n, m
         del keep
+
+    def set_matrix_sparse_device_weighted(self, ptr, idx, val, weights, shape, layout="csc", absent="missing", stream=None):
+        """set_matrix_csc_weighted for a sparse matrix AND its weights in device memory (see dev_sparse, dev_sparse_weights): weights is
+        a 1-D device array of nnz floats in the order of val, or a (ptr, idx, val) triple of the same layout and shape whose pattern the
+        library checks against the matrix's.  absent = "missing" | "zero" (a zero of weight 1).  stream: as for set_matrix_device; it
+        orders the matrix's arrays and the weights alike."""
+        if absent not in ("zero", "missing"):
+            raise ValueError(f"absent must be 'zero' or 'missing' (got {absent!r})")
+        d, keep, (n, m), st = dev_sparse(ptr, idx, val, shape, layout, self.device)
+        dw, keepw, stw = dev_sparse_weights(weights, d.nnz, (n, m), layout, self.device)
+        st = st if st is not None else stw
+        st = _stream_of(val if _is_tensor_like(val) else None, stream) if (stream is not None or st is None) else st
+        self._ck(self._lib.nnlm_set_matrix_sparse_device_weighted(self._h, C.byref(d), C.byref(dw), n, m, 1 if absent == "missing" else 0,
+                                                                  C.c_void_p(st)))
+        self.n, self.m = n, m
+        del keep, keepw
+
+    def debug_sparse_resident_weighted(self, side):
+        """(weights fp64, weights * values fp64) of the resident weighted sparse matrix, in the order of side 0 (by columns) or 1 (by rows)."""
+        nnz = max(int(self.get_info("matrix_nnz")), 0)
+        wt, wa = np.zeros(nnz, dtype=np.float64), np.zeros(nnz, dtype=np.float64)
+        self._ck(self._lib.nnlm_debug_sparse_resident_weighted(self._h, int(side), _dp(wt), _dp(wa)))
+        return wt, wa
 
     def debug_sparse_resident(self, side):
         """(ptr int64, idx int32, val fp64) of the resident sparse matrix: side 0 by columns (idx = rows), side 1 by rows."""

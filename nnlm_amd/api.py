@@ -112,18 +112,51 @@ def _absent_arg(absent, x, name):
 # ------------------------------------------------------------------------------------------------
 # per-entry weights on a sparse A (nnlm_set_matrix_csc_weighted)
 # ------------------------------------------------------------------------------------------------
-def _weights_refusals(who, name, x, loss, sparse_kl, init=None):
-    """What `weights` cannot be combined with, each refused by name."""
-    if _lib.is_device_array(x) or str(getattr(x, "layout", "")).startswith("torch.sparse_"):
+def _in_device_memory(x):
+    """A dense or sparse tensor (or __cuda_array_interface__ producer) that does not live on the host."""
+    if str(getattr(x, "layout", "")).startswith("torch.sparse_"):
+        return getattr(getattr(x, "device", None), "type", "cpu") != "cpu"
+    return _lib.is_device_array(x)
+
+
+def _weights_refusals(who, name, x, loss, sparse_kl, init=None, weights=None, device_door=False):
+    """What `weights` cannot be combined with, each refused by name.  True when the pair goes through the device door (device_door: the
+    caller has one): a sparse tensor of the GPU with weights that live there too."""
+    on_device = (device_door and _in_device_memory(weights) and str(getattr(x, "layout", "")).startswith("torch.sparse_")
+                 and _in_device_memory(x))
+    if not on_device and (_lib.is_device_array(x) or str(getattr(x, "layout", "")).startswith("torch.sparse_")):
         raise NnlmStop("%s: weights cannot be combined with a %s in device memory (dense or sparse tensor); pass a host sparse matrix "
                        "(an object with tocsc())." % (who, name))
-    if not is_sparse(x):
+    if not on_device and _in_device_memory(weights):
+        raise NnlmStop("%s: weights live in device memory, but %s is a host matrix; pass the weights as a host array or sparse matrix (or "
+                       "both as sparse tensors of the GPU)." % (who, name))
+    if not on_device and not is_sparse(x):
         raise NnlmStop("%s: weights need a sparse %s (an object with tocsc()): one weight per stored entry; weights on a dense matrix are "
                        "not supported." % (who, name))
     if loss == "mkl" or sparse_kl:
         raise NnlmStop("%s: weights are supported for loss = 'mse' only (not loss = 'mkl' / sparse_kl)." % who)
     if isinstance(init, str):
         raise NnlmStop("%s: weights cannot be combined with init = %r: a matrix with per-entry weights has no SVD start here." % (who, init))
+    return on_device
+
+
+def _device_weights_arg(weights, parts, who):
+    """`weights` of the device door as Handle.set_matrix_sparse_device_weighted takes them: a 1-D array of the GPU aligned with the
+    values of the sparse tensor whose arrays are `parts`, or the (ptr, idx, val) of a sparse tensor of the same layout and shape (its
+    pattern is the library's to check)."""
+    try:
+        wparts = _lib.sparse_tensor_parts(weights)
+    except ValueError as e:
+        raise NnlmStop("%s: weights: %s" % (who, e)) from None
+    if wparts is None:
+        return weights
+    shape, layout = parts[3], parts[4]
+    if wparts[4] != layout:
+        raise NnlmStop("%s: weights is a sparse %s tensor, the matrix a sparse %s tensor; convert one of them (to_sparse_%s())." %
+                       (who, wparts[4].upper(), layout.upper(), layout))
+    if tuple(wparts[3]) != tuple(shape):
+        raise NnlmStop("%s: weights is %d x %d, the matrix %d x %d." % (who, wparts[3][0], wparts[3][1], shape[0], shape[1]))
+    return wparts[:3]
 
 
 def _weights_arg(weights, A, c, who):
@@ -481,11 +514,20 @@ def _sparse_device_refusals(loss, absent, sparse_kl):
         raise NnlmStop("Sparse A is supported for loss = 'mse' only; use a dense matrix for loss = 'mkl'.")
 
 
-def _sparse_device_matrix(parts, h, absent, kl, batch):
-    """The `matrix` of _prepare_nnmf for a sparse tensor in device memory: ingested into h (nnlm_set_matrix_sparse_device); check_k's
-    bound with absent = 'missing' is the fewest stored entries of a row or a column, from the handle."""
+def _sparse_device_matrix(parts, h, absent, kl, batch, weights=None):
+    """The `matrix` of _prepare_nnmf for a sparse tensor in device memory: ingested into h (nnlm_set_matrix_sparse_device, or with
+    `weights` of _device_weights_arg nnlm_set_matrix_sparse_device_weighted); check_k's bound with absent = 'missing' is the fewest
+    stored entries of a row or a column, from the handle."""
     ptr, idx, val, shape, layout = parts
-    h.set_matrix_sparse_device(ptr, idx, val, shape, layout, absent=absent, kl=kl, batch=batch)
+    try:
+        if weights is not None:
+            h.set_matrix_sparse_device_weighted(ptr, idx, val, weights, shape, layout, absent=absent)
+        else:
+            h.set_matrix_sparse_device(ptr, idx, val, shape, layout, absent=absent, kl=kl, batch=batch)
+    except ValueError as e:
+        if weights is None:
+            raise
+        raise NnlmStop("nnmf: %s" % e) from None
     n, m = h.n, h.m
     min_k = min(n, m)
     if absent == "missing" and h.matrix_info()["any_missing"]:
@@ -549,19 +591,22 @@ def _tensor_lib(A):
 
 
 def _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
-                 show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl=False, parts=None):
+                 show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl=False, parts=None, weights=None):
     """nnmf() on a matrix in device memory: ingest, factors, run and export on one Handle; A never visits the host.  parts: the arrays
-    of a sparse CSC / CSR tensor (_lib.sparse_tensor_parts), ingested through the door `absent` and `sparse_kl` name."""
+    of a sparse CSC / CSR tensor (_lib.sparse_tensor_parts), ingested through the door `absent` and `sparse_kl` name -- with `weights`
+    (device memory too, _weights_refusals has passed them) through the weighted door."""
     torch = _tensor_lib(A)
     if parts is not None:
         loss = _match_arg(loss, ("mse", "mkl"), "loss")
         absent = _match_arg(absent, ("zero", "missing"), "absent")
         _sparse_device_refusals(loss, absent, sparse_kl)
         sparse_kl = bool(sparse_kl) and loss == "mkl"
+        if weights is not None:
+            weights = _device_weights_arg(weights, parts, "nnmf")
     g = rng or np.random.default_rng()
     t0 = time.perf_counter()
     with _lib.Handle(_device_index(A), _env_precision()) as h:
-        mat = _device_matrix(A, h) if parts is None else _sparse_device_matrix(parts, h, absent, sparse_kl, False)
+        mat = _device_matrix(A, h) if parts is None else _sparse_device_matrix(parts, h, absent, sparse_kl, False, weights)
         # (a sparse tensor: the handle knows what absent entries are; _prepare_nnmf's `absent` asks for an object with tocsc())
         args, ctx, _ = _prepare_nnmf(A, k, alpha, beta, method, loss, _host_factor_entries(init, "nnmf"), mask, W_norm, check_k, max_iter,
                                      rel_tol, n_threads, trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, matrix=mat,
@@ -791,12 +836,15 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
          weights=None):
     """Non-negative matrix factorisation A ~ W H on the MI355X (drop-in for R's NNLM::nnmf, R/nnmf.R:135-225).
 
-    ``weights`` (host sparse A, loss "mse", k <= 64): one weight c >= 0 per stored entry -- a sparse matrix with A's stored pattern, or a
-    1-D array aligned with the stored entries of a canonical A.  The loss is 1/2 sum of c (a - (WH))^2 over the observed entries + the
+    ``weights`` (sparse A, loss "mse", k <= 64): one weight c >= 0 per stored entry -- a sparse matrix with A's stored pattern, or a
+    1-D array aligned with the stored entries of a canonical A.  With A a sparse CSC / CSR tensor of the GPU the weights live there too:
+    a 1-D tensor (or __cuda_array_interface__ object) aligned with A.values(), or a sparse tensor of A's layout and shape whose pattern
+    the library checks; A and the weights are ingested where they lie.  The loss is 1/2 sum of c (a - (WH))^2 over the observed entries + the
     penalties.  With absent = "missing" the observed entries are the stored ones (weighted NMF: inverse-variance weights, down-weighted
     doubtful ratings).  With absent = "zero" every entry is observed and an absent one is a zero of weight 1: implicit feedback (Hu,
     Koren & Volinsky 2008: store r with weight 1 + alpha r).  The traces are the weighted sums over N = nnz (missing) or n m (zero).
-    Refused by name: a dense A, a tensor in device memory, loss "mkl" / sparse_kl, a string init.
+    Refused by name: a dense A, host weights with an A in device memory (and device weights with a host A), a sparse weights tensor of
+    another layout or shape than A, loss "mkl" / sparse_kl, a string init.
 
     ``init`` = "nndsvd" or "nndsvda": a deterministic, data-driven start (Boutsidis & Gallopoulos 2008) from a truncated SVD of A made on
     the GPU (truncated_svd(): sketch width min(k + svd_oversample, n, m), svd_power_iters power iterations, the sketch matrix drawn from
@@ -827,15 +875,15 @@ def nnmf(A, k=1, alpha=(0, 0, 0), beta=(0, 0, 0), method="scd", loss="mse", init
     as_csc() repairs on the host is refused here, with the library's message.  W and H come back as fp64 tensors on A's device.  Other
     sparse layouts (COO, BSR, BSC) and sparse tensors in host memory are refused by name.
     """
-    if weights is not None:
-        _weights_refusals("nnmf", "A", A, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl, init)
+    device_weights = weights is not None and _weights_refusals("nnmf", "A", A, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl, init,
+                                                               weights, device_door=True)
     parts = _sparse_device_parts(A, "nnmf")
     if isinstance(init, str):
         return _nnmf_svd_init(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
                               show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts, svd_oversample, svd_power_iters)
     if parts is not None or _lib.is_device_array(A):
         return _nnmf_device(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads, trace, verbose,
-                            show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts)
+                            show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl, parts, weights if device_weights else None)
     args, ctx = prepare_nnmf(A, k, alpha, beta, method, loss, init, mask, W_norm, check_k, max_iter, rel_tol, n_threads,
                              trace, verbose, show_warning, inner_max_iter, inner_rel_tol, rng, absent, sparse_kl)
     g = rng or np.random.default_rng()
@@ -1372,7 +1420,7 @@ def nnlm(x, y, alpha=(0, 0, 0), method="scd", loss="mse", init=None, mask=None, 
     stored entries of its column of y only (square loss, at most 64 columns of x).
     ``sparse_kl`` (sparse y, absent = "zero"): True admits loss = 'mkl' (stored values >= 0, at most 64 columns of x); see nnmf()."""
     if weights is not None:
-        _weights_refusals("nnlm", "y", y, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl)
+        _weights_refusals("nnlm", "y", y, _match_arg(loss, ("mse", "mkl"), "loss"), sparse_kl, weights=weights)
     args, ctx = prepare_nnlm(x, y, alpha, method, loss, init, mask, check_x, max_iter, rel_tol, n_threads, show_warning, absent, sparse_kl)
     g = rng or np.random.default_rng()
     cb = _lib.make_callbacks(unif_rand=lambda: g.random())

@@ -11,6 +11,11 @@
 //   3. spi_count_kernel,  run on indices stage 2 has accepted (0 <= idx < lines of the other side): the first kernels that use an
 //      spi_hist_kernel,   index as an address.  The other side is a stable LSD radix sort of the entries by index (8-bit digits), the
 //      spi_scatter_kernel line number and the value as payload; its pointers are the scan of the index histogram.
+// Per-entry weights (nnlm_set_matrix_sparse_device_weighted) add, between stages 2 and 3 and under the same rule:
+//   2a. spi_pattern_ptr_kernel, weights that bring a pattern of their own: their pointers, then (only when those are equal) their indices
+//       spi_pattern_idx_kernel  are COMPARED with the accepted resident ones, never dereferenced;
+//   2b. spi_wcheck_kernel       reads a weight per entry number (in range by construction), checks it, forms c a in fp64 and converts;
+// and the sort carries the weights and the products as two more payloads of the same positions (spi_scatter_kernel<T, true>).
 // Nothing here depends on scheduling: the only atomics are integer counters whose final value is order independent (the histograms), the
 // rank of an entry inside a wavefront comes from ballots, the per-block results are reduced over a fixed tree and summed by the host in
 // block order.
@@ -148,6 +153,78 @@ __global__ void spi_fetch_kernel(const I *__restrict__ idx, const S *__restrict_
     *v_out = prep_load(val + e);
 }
 
+// Stage 2a.  The pointers of the weights' own pattern against the accepted ones (ref [lines + 1], int64), one thread per pointer:
+// blockmin[b] = the smallest line whose extent differs -- pointer t > 0 differing means line t - 1 does (its start was equal or an
+// earlier line already differs) -- or SPI_NONE.
+template <typename P>
+__global__ __launch_bounds__(SPI_THREADS) void spi_pattern_ptr_kernel(const P *__restrict__ ptr, const long long *__restrict__ ref, int lines,
+                                                                      long long *__restrict__ blockmin)
+{
+    __shared__ long long sh[SPI_THREADS];
+    const long long t = (long long)blockIdx.x * SPI_THREADS + threadIdx.x;
+    long long bad = SPI_NONE;
+    if (t <= lines && (long long)ptr[t] != ref[t]) bad = t > 0 ? t - 1 : 0;
+    bad = spi_block_reduce(bad, sh, SpiMin());
+    if (threadIdx.x == 0) blockmin[blockIdx.x] = bad;
+}
+// ... and, on equal pointers, its indices against the accepted resident int32 ones, one thread per entry: blockmin[b] = the smallest
+// entry that differs, or SPI_NONE (the host finds its line in its copy of the pointers).
+template <typename I>
+__global__ __launch_bounds__(SPI_THREADS) void spi_pattern_idx_kernel(const I *__restrict__ idx, const int *__restrict__ ref, long long nnz,
+                                                                      long long *__restrict__ blockmin)
+{
+    __shared__ long long sh[SPI_THREADS];
+    const long long e = (long long)blockIdx.x * SPI_THREADS + threadIdx.x;
+    long long bad = SPI_NONE;
+    if (e < nnz && (long long)idx[e] != (long long)ref[e]) bad = e;
+    bad = spi_block_reduce(bad, sh, SpiMin());
+    if (threadIdx.x == 0) blockmin[blockIdx.x] = bad;
+}
+
+// Stage 2b: the weights, on entries stage 2 has accepted (every value finite).  Same shares as spi_check_kernel.  Per entry c = the weight
+// and v = the value, each widened to fp64 from its own type, and c a = c * v, ONE fp64 multiply (the host's weight[e] * x[e]); c and c a
+// go to the mode's type T twice, as the values do.  blockcode[b] = the first entry whose weight is not a finite number >= 0 (a code of
+// its own: the host reads it only after stage 2 has found no offence of A), blockstat[b] = what the host loop adds for a weighted entry:
+// {entries with |v| <= fp32 max and (|c a| > fp32 max or c > fp32 max), max |(float)(c a)|, sum c ((v + eps) log(v + eps) - v)}.
+template <typename S, typename C, typename T>
+__global__ __launch_bounds__(SPI_THREADS) void spi_wcheck_kernel(const S *__restrict__ val, const C *__restrict__ wgt, long long nnz,
+                                                                 T *__restrict__ wt_out, T *__restrict__ wt_sort, T *__restrict__ wa_out,
+                                                                 T *__restrict__ wa_sort, long long *__restrict__ blockcode,
+                                                                 double *__restrict__ blockstat)
+{
+    __shared__ long long shl[SPI_THREADS];
+    __shared__ double shd[SPI_THREADS];
+    const long long e0 = (long long)blockIdx.x * SPI_CHECK_SHARE;
+    const long long e1 = e0 + SPI_CHECK_SHARE < nnz ? e0 + SPI_CHECK_SHARE : nnz;
+    long long code = SPI_NONE;
+    double over = 0.0, wmx = 0.0, klc = 0.0;
+    for (int it = 0; it < SPI_CHECK_ITEMS; it++) {
+        const long long e = e0 + (long long)it * SPI_THREADS + threadIdx.x;
+        if (e >= e1) continue;
+        const double v = prep_load(val + e), c = prep_load(wgt + e);
+        if ((!isfinite(c) || c < 0.0) && e < code) code = e;
+        const double ca = c * v;
+        wt_out[e] = (T)c;
+        wt_sort[e] = (T)c;
+        wa_out[e] = (T)ca;
+        wa_sort[e] = (T)ca;
+        if (fabs(v) <= 3.4028234663852886e38 && (fabs(ca) > 3.4028234663852886e38 || c > 3.4028234663852886e38)) over += 1.0;
+        const double fca = fabs((double)(float)ca);
+        if (fca > wmx) wmx = fca;
+        klc += c * ((v + NNLM_TINY) * log(v + NNLM_TINY) - v);
+    }
+    code = spi_block_reduce(code, shl, SpiMin());
+    over = spi_block_reduce(over, shd, SpiAdd());
+    wmx = spi_block_reduce(wmx, shd, SpiMax());
+    klc = spi_block_reduce(klc, shd, SpiAdd());
+    if (threadIdx.x == 0) {
+        blockcode[blockIdx.x] = code;
+        blockstat[3 * (size_t)blockIdx.x] = over;
+        blockstat[3 * (size_t)blockIdx.x + 1] = wmx;
+        blockstat[3 * (size_t)blockIdx.x + 2] = klc;
+    }
+}
+
 // Stage 3.  cnt[i] += entries with index i (cnt zeroed, [lines of the other side + 1]); its exclusive scan is the other side's pointers
 __global__ __launch_bounds__(SPI_THREADS) void spi_count_kernel(const int *__restrict__ idx, long long nnz, unsigned long long *__restrict__ cnt)
 {
@@ -234,10 +311,13 @@ __global__ __launch_bounds__(SPI_THREADS) void spi_hist_kernel(const int *__rest
 // The stable scatter of the pass.  Wavefront w of the block owns SPI_SORT_ROUNDS rows of 64 consecutive entries; an entry of digit d lands
 // at goff[d][b] + (entries of d in the wavefronts before w) + (entries of d in w's earlier rows) + (lanes below it in its row with d):
 // input order within a digit, whatever the schedule.  The last term is a popcount over ballots.  kout == NULL: the last pass drops the keys.
-template <typename T>
+// WT: the weights and the products c a (win, ain -> wout, aout) travel to the same positions as the values; otherwise the four are unused.
+template <typename T, bool WT>
 __global__ __launch_bounds__(SPI_THREADS) void spi_scatter_kernel(const int *__restrict__ kin, const int *__restrict__ lin, const T *__restrict__ vin,
                                                                   int *__restrict__ kout, int *__restrict__ lout, T *__restrict__ vout, long long nnz,
-                                                                  int shift, const long long *__restrict__ goff, int nblocks)
+                                                                  int shift, const long long *__restrict__ goff, int nblocks,
+                                                                  const T *__restrict__ win, const T *__restrict__ ain, T *__restrict__ wout,
+                                                                  T *__restrict__ aout)
 {
     constexpr int NW = SPI_THREADS / 64;
     __shared__ int wcnt[NW][256];
@@ -285,6 +365,10 @@ __global__ __launch_bounds__(SPI_THREADS) void spi_scatter_kernel(const int *__r
             if (kout) kout[pos] = key[r];
             lout[pos] = lin[e];
             vout[pos] = vin[e];
+            if constexpr (WT) {
+                wout[pos] = win[e];
+                aout[pos] = ain[e];
+            }
         }
     }
 }

@@ -1196,7 +1196,8 @@ static bool owns_allocation(const nnlm_handle *h, const void *base)
 {
     const void *mine[] = {h->A, h->AT, h->miss, h->missT, h->A16, h->A16T, h->partials, h->W64b[0], h->W64b[1], h->Wopb[0], h->Wopb[1], h->H64,
                           h->Hkq, h->Wmask, h->Hmask, h->Y16, h->W16c, h->H16c, h->Cx, h->red, h->gslabs, h->sg_slabs, h->What, h->What64,
-                          h->sp_cptr, h->sp_rptr, h->sp_ridx, h->sp_cidx, h->sp_cval, h->sp_rval, h->sp_Y, h->bG, h->ho_val};
+                          h->sp_cptr, h->sp_rptr, h->sp_ridx, h->sp_cidx, h->sp_cval, h->sp_rval, h->sp_Y, h->bG, h->ho_val,
+                          h->sp_cwt, h->sp_rwt, h->sp_cwa, h->sp_rwa};
     for (const void *p : mine)
         if (p && p == base) return true;
     return false;
@@ -1519,6 +1520,24 @@ static int sp_finish(nnlm_handle *h, const char *who, const long long *colptr, c
     return NNLM_OK;
 }
 
+// sp_finish for a handle with per-entry weights, behind the four weight arrays as well: klc is the weighted sum (-> kl_const_w), and the
+// per-column path runs for the zero semantics too, so its tables are built for either
+static int sp_finish_weighted(nnlm_handle *h, const char *who, const long long *colptr, const long long *rowptr, double klc, bool absent_missing)
+{
+    int rw = sp_finish(h, who, colptr, rowptr, klc, absent_missing, false);
+    if (rw != NNLM_OK) return rw;
+    if (!absent_missing) {
+        rw = spg_layout(h, 1, colptr, h->m);
+        if (rw == NNLM_OK) rw = spg_layout(h, 0, rowptr, h->n);
+        if (rw != NNLM_OK) {
+            free_matrix(h);
+            return rw;
+        }
+    }
+    h->sp_weighted = true;
+    return NNLM_OK;
+}
+
 // The CSC contract of the sparse set-matrix entries, checked in the order they have always reported it (first offender named)
 static int csc_check(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x, bool absent_missing, const char *who,
                      bool kl)
@@ -1653,18 +1672,7 @@ static int set_matrix_csc_impl(nnlm_handle *h, int n, int m, const long long *co
         free_matrix(h);
         return rw;
     }
-    rw = sp_finish(h, who, colptr, rptr.data(), klc, absent_missing, false); // (klc: the weighted sum -> kl_const_w)
-    if (rw != NNLM_OK) return rw;
-    if (!absent_missing) { // the per-column path runs for the zero semantics too: its tables
-        rw = spg_layout(h, 1, colptr, m);
-        if (rw == NNLM_OK) rw = spg_layout(h, 0, rptr.data(), n);
-        if (rw != NNLM_OK) {
-            free_matrix(h);
-            return rw;
-        }
-    }
-    h->sp_weighted = true;
-    return NNLM_OK;
+    return sp_finish_weighted(h, who, colptr, rptr.data(), klc, absent_missing);
 }
 
 extern "C" int nnlm_set_matrix_csc(nnlm_handle *h, int n, int m, const long long *colptr, const int *rowidx, const double *x)
@@ -1833,9 +1841,13 @@ static int dev_array_check(nnlm_handle *h, const char *who, const char *name, co
     return NNLM_OK;
 }
 
-extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_sparse *A, int n, int m, int door, void *stream)
+// The body of nnlm_set_matrix_sparse_device (weighted = false: Wt is not looked at, `door` holds the door bits) and of
+// nnlm_set_matrix_sparse_device_weighted (weighted = true: `door` holds NNLM_SP_ABSENT_MISSING or 0).  The weights add the descriptor
+// checks, two stages between the entry check and the range rules -- their pattern (when they bring one), then the weights themselves --
+// two payloads of the sort and four resident arrays; everything else is one code path.
+static int sparse_device_impl(nnlm_handle *h, const char *who, const nnlm_dev_sparse *A, bool weighted, const nnlm_dev_sparse *Wt, int n, int m,
+                              int door, void *stream)
 {
-    const char *who = "nnlm_set_matrix_sparse_device";
     if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
     if (!A) return fail(h, NNLM_ERR_ARG, "%s: A is NULL", who);
     if (A->layout != NNLM_SP_CSC && A->layout != NNLM_SP_CSR)
@@ -1860,10 +1872,35 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
     if (nnz > 0 && (!A->idx || !A->val)) return fail(h, NNLM_ERR_ARG, "%s: idx / val is NULL with nnz = %lld", who, nnz);
     const int lines = csc ? m : n, other = csc ? n : m; // lines of the given side, of the side to build
     const bool p64 = A->ptr_dtype == NNLM_IT_I64, i64 = A->idx_dtype == NNLM_IT_I64, f64 = h->prec == NNLM_PREC_F64;
+    // the weights: aligned with A.val (no ptr, no idx), or a sparse matrix of A's layout whose pattern stage 2a compares with A's
+    const bool wpat = weighted && Wt && Wt->ptr && Wt->idx;
+    bool wp64 = false, wi64 = false;
+    if (weighted) {
+        if (!Wt) return fail(h, NNLM_ERR_ARG, "%s: Wt is NULL (one weight per stored entry)", who);
+        if ((Wt->ptr == nullptr) != (Wt->idx == nullptr))
+            return fail(h, NNLM_ERR_ARG, "%s: Wt.ptr and Wt.idx must both be NULL (weights in the order of A.val) or both be given (weights as a "
+                                         "sparse matrix of A's pattern)", who);
+        if (Wt->val_dtype < NNLM_DT_F64 || Wt->val_dtype > NNLM_DT_BF16)
+            return fail(h, NNLM_ERR_ARG, "%s: Wt.val_dtype = %d is not one of NNLM_DT_F64 .. NNLM_DT_BF16", who, Wt->val_dtype);
+        if (Wt->nnz < 0) return fail(h, NNLM_ERR_ARG, "%s: Wt.nnz = %lld is negative", who, Wt->nnz);
+        if (wpat) {
+            if (Wt->layout != A->layout)
+                return fail(h, NNLM_ERR_ARG, "%s: Wt.layout = %d differs from A.layout = %d", who, Wt->layout, A->layout);
+            if ((Wt->ptr_dtype != NNLM_IT_I32 && Wt->ptr_dtype != NNLM_IT_I64) || (Wt->idx_dtype != NNLM_IT_I32 && Wt->idx_dtype != NNLM_IT_I64))
+                return fail(h, NNLM_ERR_ARG, "%s: Wt.ptr_dtype = %d, Wt.idx_dtype = %d: each must be NNLM_IT_I32 or NNLM_IT_I64", who, Wt->ptr_dtype,
+                            Wt->idx_dtype);
+            wp64 = Wt->ptr_dtype == NNLM_IT_I64, wi64 = Wt->idx_dtype == NNLM_IT_I64;
+        } else if (Wt->nnz != nnz) // (weights with a pattern of their own: the pattern stage names the first line that differs)
+            return fail(h, NNLM_ERR_ARG, "%s: Wt.nnz = %lld, but A.nnz = %lld (one weight per stored entry, in the order of A.val)", who, Wt->nnz, nnz);
+        if (Wt->nnz > 0 && !Wt->val) return fail(h, NNLM_ERR_ARG, "%s: Wt.val is NULL with Wt.nnz = %lld", who, Wt->nnz);
+    }
     HIPCHK(h, hipSetDevice(h->device));
     int rc = dev_array_check(h, who, "A.ptr", A->ptr, p64 ? 8 : 4, (long long)lines + 1);
     if (rc == NNLM_OK && nnz > 0) rc = dev_array_check(h, who, "A.idx", A->idx, i64 ? 8 : 4, nnz);
     if (rc == NNLM_OK && nnz > 0) rc = dev_array_check(h, who, "A.val", A->val, dt_size(A->val_dtype), nnz);
+    if (rc == NNLM_OK && wpat) rc = dev_array_check(h, who, "Wt.ptr", Wt->ptr, wp64 ? 8 : 4, (long long)lines + 1);
+    if (rc == NNLM_OK && wpat && Wt->nnz > 0) rc = dev_array_check(h, who, "Wt.idx", Wt->idx, wi64 ? 8 : 4, Wt->nnz);
+    if (rc == NNLM_OK && weighted && Wt->nnz > 0) rc = dev_array_check(h, who, "Wt.val", Wt->val, dt_size(Wt->val_dtype), Wt->nnz);
     if (rc != NNLM_OK) return rc;
     g_attr_err = hipSuccess;
     hipStream_t st = h->stream;
@@ -1886,16 +1923,19 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
     if (!bufs.get(&gptr, (size_t)(lines + 1) * 8) || !bufs.get(&optr, (size_t)(other + 1) * 8) || !bufs.get(&gidx, ib) || !bufs.get(&oidx, ib) ||
         !bufs.get(&gval, vb) || !bufs.get(&oval, vb))
         return nomem("the resident arrays");
+    void *gwt = nullptr, *owt = nullptr, *gwa = nullptr, *owa = nullptr; // the weights and the products c a, given side / built side
+    if (weighted && (!bufs.get(&gwt, vb) || !bufs.get(&owt, vb) || !bufs.get(&gwa, vb) || !bufs.get(&owa, vb))) return nomem("the resident weights");
     std::vector<long long> hg, ho; // host copies of the two pointer arrays
     std::vector<long long> hcode;
     std::vector<double> hstat;
     const int nb_ptr = (lines + 256) / 256;
     const long long share = nnlm_spi_check_share(), tile = nnlm_spi_sort_tile(), stile = nnlm_spi_scan_tile();
     const int nb_chk = (int)((nnz + share - 1) / share), nb_sort = (int)((nnz + tile - 1) / tile);
+    const int nb_pidx = wpat ? (int)((nnz + 255) / 256) : 0; // (the index comparison of the weights' pattern: one thread per entry)
     try {
         hg.resize((size_t)lines + 1);
         ho.resize((size_t)other + 1);
-        hcode.resize((size_t)(nb_ptr > nb_chk ? nb_ptr : nb_chk));
+        hcode.resize((size_t)std::max(std::max(nb_ptr, nb_chk), nb_pidx));
         hstat.resize(3 * (size_t)nb_chk);
     } catch (...) {
         return fail(h, NNLM_ERR_HIP, "%s: host buffers for %d + %d pointers", who, n + 1, m + 1);
@@ -1928,11 +1968,12 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
     // stage 2: the entries, on pointers that hold; the given side's indices and values land in their resident types
     const int bits = other <= 1 ? 0 : 32 - __builtin_clz((unsigned)(other - 1)), passes = (bits + 7) / 8;
     int *ltmp = nullptr, *keyb = nullptr, *keyc = nullptr; // line numbers' other buffer; the keys after an odd / an even pass
-    void *vtmp = nullptr;
+    void *vtmp = nullptr, *wtmp = nullptr, *atmp = nullptr;
     long long *ghist = nullptr, *bsum = nullptr;
     const long long scan_len = 256LL * nb_sort > (long long)other + 1 ? 256LL * nb_sort : (long long)other + 1;
     if (nnz > 0) {
         if (passes >= 1 && (!bufs.get(&ltmp, ib) || !bufs.get(&vtmp, vb) || !bufs.get(&ghist, 256 * (size_t)nb_sort * 8))) return nomem("the sort buffers");
+        if (passes >= 1 && weighted && (!bufs.get(&wtmp, vb) || !bufs.get(&atmp, vb))) return nomem("the sort buffers");
         if (passes >= 2 && !bufs.get(&keyb, ib)) return nomem("the sort buffers");
         if (passes >= 3 && !bufs.get(&keyc, ib)) return nomem("the sort buffers");
     }
@@ -1940,7 +1981,9 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
     // the entries' line numbers and values start where an even number of passes ends in the resident arrays
     int *lcur = (passes & 1) ? ltmp : oidx, *lnext = (passes & 1) ? oidx : ltmp;
     void *vcur = (passes & 1) ? vtmp : oval, *vnext = (passes & 1) ? oval : vtmp;
-    double over = 0.0, mx = 0.0, klc = 0.0;
+    void *wcur = (passes & 1) ? wtmp : owt, *wnext = (passes & 1) ? owt : wtmp;
+    void *acur = (passes & 1) ? atmp : owa, *anext = (passes & 1) ? owa : atmp;
+    double over = 0.0, mx = 0.0, wmx = 0.0, klc = 0.0;
     if (nnz > 0) {
         {
             ProfScope ps(h, P_SP_INGEST_CHECK);
@@ -1981,12 +2024,79 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
             klc += hstat[3 * (size_t)b + 2];
         }
     }
+    // stage 2a: the pattern the weights bring, against the accepted one: pointers first, indices only behind equal pointers
+    if (wpat) {
+        long long first = LLONG_MAX;
+        {
+            ProfScope ps(h, P_SP_INGEST_CHECK);
+            nnlm_tu_spi_pattern_ptr(Wt->ptr, wp64, gptr, lines, dcode, st);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(hcode.data(), dcode, (size_t)nb_ptr * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hipfail("the pattern check of the weights", e);
+        for (int b = 0; b < nb_ptr; b++) first = hcode[b] < first ? hcode[b] : first;
+        if (first == LLONG_MAX && Wt->nnz != nnz)
+            return fail(h, NNLM_ERR_ARG, "%s: Wt.nnz = %lld, but the pointers of the weights end at %lld", who, Wt->nnz, nnz);
+        if (first == LLONG_MAX && nnz > 0) {
+            {
+                ProfScope ps(h, P_SP_INGEST_CHECK);
+                nnlm_tu_spi_pattern_idx(Wt->idx, wi64, gidx, nnz, dcode, st);
+            }
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(hcode.data(), dcode, (size_t)nb_pidx * 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return hipfail("the pattern check of the weights", e);
+            long long eo = LLONG_MAX;
+            for (int b = 0; b < nb_pidx; b++) eo = hcode[b] < eo ? hcode[b] : eo;
+            if (eo != LLONG_MAX) first = (long long)(std::upper_bound(hg.begin(), hg.end(), eo) - hg.begin()) - 1;
+        }
+        if (first != LLONG_MAX)
+            return fail(h, NNLM_ERR_ARG, "%s: the stored pattern of weights differs from the matrix's (first in %s %d)", who, lname, (int)first);
+    }
+    // stage 2b: the weights themselves, c a and what the range rules and the KL constant need of them
+    if (weighted && nnz > 0) {
+        {
+            ProfScope ps(h, P_SP_INGEST_CHECK);
+            nnlm_tu_spi_wcheck(A->val, A->val_dtype, Wt->val, Wt->val_dtype, f64, nnz, gwt, wcur, gwa, acur, dcode, dstat, st);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(hcode.data(), dcode, (size_t)nb_chk * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(hstat.data(), dstat, 3 * (size_t)nb_chk * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return hipfail("the weight check", e);
+        long long eo = LLONG_MAX;
+        for (int b = 0; b < nb_chk; b++) eo = hcode[b] < eo ? hcode[b] : eo;
+        if (eo != LLONG_MAX) {
+            long long oi = 0;
+            double ow = 0.0;
+            nnlm_tu_spi_fetch(A->idx, i64, Wt->val, Wt->val_dtype, eo, dcode, dstat, st);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(&oi, dcode, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipMemcpyAsync(&ow, dstat, 8, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return hipfail("reading the offending weight", e);
+            const int j = (int)(std::upper_bound(hg.begin(), hg.end(), eo) - hg.begin()) - 1;
+            return fail(h, NNLM_ERR_ARG, "%s: weight %g of entry %lld (row %d, column %d) is not a finite number >= 0", who, ow, eo,
+                        csc ? (int)oi : j, csc ? j : (int)oi);
+        }
+        klc = 0.0; // (the weighted sum takes the place of the plain one)
+        for (int b = 0; b < nb_chk; b++) {
+            over += hstat[3 * (size_t)b];
+            if (hstat[3 * (size_t)b + 1] > wmx) wmx = hstat[3 * (size_t)b + 1];
+            klc += hstat[3 * (size_t)b + 2];
+        }
+    }
     if (!f64 && over > 0.0)
-        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
-                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over);
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%.0f entries of A%s exceed the fp32 range (|a| > 3.4e38): the fp32-operand mode cannot hold them; "
+                                             "use the strict fp64 mode (NNLM_PREC_F64, the default of the one-shot entries)", over,
+                    weighted ? " (or their weights, or weight * A)" : "");
     if (!f64 && mx > 0.0 && mx < 7.8886090522101181e-31)
         return fail(h, NNLM_ERR_UNSUPPORTED, "max |A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale A or use "
                                              "the strict fp64 mode", mx);
+    if (!f64 && wmx > 0.0 && wmx < 7.8886090522101181e-31)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "max |weight * A| = %.3g is too close to the bottom of the fp32 range for the fp32-operand mode; rescale "
+                                             "or use the strict fp64 mode", wmx);
 
     // stage 3: the other side, on indices that hold
     {
@@ -1998,10 +2108,13 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
             const int *kin = gidx;
             for (int p = 0; p < passes; p++) {
                 int *kout = p == passes - 1 ? nullptr : ((p & 1) ? keyc : keyb);
-                nnlm_tu_spi_sort_pass(kin, lcur, vcur, kout, lnext, vnext, f64, nnz, 8 * p, ghist, bsum, st);
+                if (weighted) nnlm_tu_spi_sort_pass(kin, lcur, vcur, kout, lnext, vnext, f64, nnz, 8 * p, ghist, bsum, st, wcur, acur, wnext, anext);
+                else nnlm_tu_spi_sort_pass(kin, lcur, vcur, kout, lnext, vnext, f64, nnz, 8 * p, ghist, bsum, st);
                 kin = kout;
                 std::swap(lcur, lnext);
                 std::swap(vcur, vnext);
+                std::swap(wcur, wnext);
+                std::swap(acur, anext);
             }
         }
     }
@@ -2026,8 +2139,14 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
     h->sp_cval = csc ? gval : oval, h->sp_rval = csc ? oval : gval;
     for (void *p : {(void *)gptr, (void *)optr, (void *)gidx, (void *)oidx, gval, oval}) bufs.release(p);
     h->sp_bytes = (size_t)(m + 1) * 8 + (size_t)(n + 1) * 8 + 2 * ib + 2 * vb;
+    if (weighted) {
+        h->sp_cwt = csc ? gwt : owt, h->sp_rwt = csc ? owt : gwt;
+        h->sp_cwa = csc ? gwa : owa, h->sp_rwa = csc ? owa : gwa;
+        for (void *p : {gwt, owt, gwa, owa}) bufs.release(p);
+        h->sp_bytes += 4 * vb;
+    }
     const std::vector<long long> &hc = csc ? hg : ho, &hr = csc ? ho : hg;
-    rc = sp_finish(h, who, hc.data(), hr.data(), klc, absent_missing, kl);
+    rc = weighted ? sp_finish_weighted(h, who, hc.data(), hr.data(), klc, absent_missing) : sp_finish(h, who, hc.data(), hr.data(), klc, absent_missing, kl);
     if (rc != NNLM_OK) return rc;
     h->sp_batch = batch;
     if (absent_missing) { // the fewest stored entries of a column / of a row
@@ -2037,6 +2156,30 @@ extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_spar
         h->min_obs[0] = (int)mc, h->min_obs[1] = (int)mr;
     } else
         h->min_obs[0] = n, h->min_obs[1] = m;
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_set_matrix_sparse_device(nnlm_handle *h, const nnlm_dev_sparse *A, int n, int m, int door, void *stream)
+{
+    return sparse_device_impl(h, "nnlm_set_matrix_sparse_device", A, false, nullptr, n, m, door, stream);
+}
+
+extern "C" int nnlm_set_matrix_sparse_device_weighted(nnlm_handle *h, const nnlm_dev_sparse *A, const nnlm_dev_sparse *Wt, int n, int m,
+                                                      int absent_missing, void *stream)
+{
+    return sparse_device_impl(h, "nnlm_set_matrix_sparse_device_weighted", A, true, Wt, n, m, absent_missing ? NNLM_SP_ABSENT_MISSING : 0, stream);
+}
+
+// One value array of a sparse handle (the mode's type, nnz elements), widened to fp64 on the host
+static int sp_download_values(nnlm_handle *h, double *out, const void *src)
+{
+    const size_t nnz = (size_t)h->nnz;
+    if (h->prec == NNLM_PREC_F64) HIPCHK(h, hipMemcpy(out, src, nnz * 8, hipMemcpyDeviceToHost));
+    else {
+        std::vector<float> f(nnz);
+        HIPCHK(h, hipMemcpy(f.data(), src, nnz * 4, hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < nnz; e++) out[e] = (double)f[e];
+    }
     return NNLM_OK;
 }
 
@@ -2052,16 +2195,22 @@ extern "C" int nnlm_debug_sparse_resident(nnlm_handle *h, int side, long long *p
     const size_t nnz = (size_t)h->nnz;
     if (ptr_out) HIPCHK(h, hipMemcpy(ptr_out, side == 0 ? h->sp_cptr : h->sp_rptr, (size_t)(lines + 1) * 8, hipMemcpyDeviceToHost));
     if (idx_out && nnz) HIPCHK(h, hipMemcpy(idx_out, side == 0 ? h->sp_ridx : h->sp_cidx, nnz * 4, hipMemcpyDeviceToHost));
-    if (val_out && nnz) {
-        const void *src = side == 0 ? h->sp_cval : h->sp_rval;
-        if (h->prec == NNLM_PREC_F64) HIPCHK(h, hipMemcpy(val_out, src, nnz * 8, hipMemcpyDeviceToHost));
-        else {
-            std::vector<float> f(nnz);
-            HIPCHK(h, hipMemcpy(f.data(), src, nnz * 4, hipMemcpyDeviceToHost));
-            for (size_t e = 0; e < nnz; e++) val_out[e] = (double)f[e];
-        }
-    }
+    if (val_out && nnz) return sp_download_values(h, val_out, side == 0 ? h->sp_cval : h->sp_rval);
     return NNLM_OK;
+}
+
+extern "C" int nnlm_debug_sparse_resident_weighted(nnlm_handle *h, int side, double *wt_out, double *wa_out)
+{
+    const char *who = "nnlm_debug_sparse_resident_weighted";
+    if (!h) return fail(nullptr, NNLM_ERR_ARG, "%s: handle is NULL", who);
+    if (!h->sparse || !h->sp_weighted) return fail(h, NNLM_ERR_ARG, "%s: the handle holds no sparse matrix with per-entry weights", who);
+    if (side != 0 && side != 1) return fail(h, NNLM_ERR_ARG, "%s: side = %d is neither 0 (by columns) nor 1 (by rows)", who, side);
+    HIPCHK(h, hipSetDevice(h->device));
+    sync_all(h);
+    int rc = NNLM_OK;
+    if (wt_out && h->nnz) rc = sp_download_values(h, wt_out, side == 0 ? h->sp_cwt : h->sp_rwt);
+    if (rc == NNLM_OK && wa_out && h->nnz) rc = sp_download_values(h, wa_out, side == 0 ? h->sp_cwa : h->sp_rwa);
+    return rc;
 }
 
 extern "C" int nnlm_matrix_info(nnlm_handle *h, double *n_non_missing, int *any_missing, double *kl_const)
@@ -4495,6 +4644,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sparse_kl_short_max") == 0) *value = nnlm_spkl_short_max();
     else if (strcmp(key, "sp_ingest_check_share") == 0) *value = nnlm_spi_check_share();
     else if (strcmp(key, "sp_ingest_sort_tile") == 0) *value = nnlm_spi_sort_tile();
+    else if (strcmp(key, "debug_sparse_values_address") == 0) *value = (h->sparse && h->sp_cval) ? (double)(uintptr_t)h->sp_cval : -1.0;
     else if (strcmp(key, "sparse_kl_batch") == 0) *value = (h->sparse && h->sp_kl && h->sp_batch) ? 1.0 : 0.0;
     else if (strcmp(key, "sparse_kl_batch_form_w") == 0) *value = h->spklb_form[0];
     else if (strcmp(key, "sparse_kl_batch_form_h") == 0) *value = h->spklb_form[1];

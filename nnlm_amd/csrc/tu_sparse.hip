@@ -346,12 +346,56 @@ void nnlm_tu_spi_scan(long long *x, long long len, long long *bsum, hipStream_t 
     spi_scan_apply_kernel<<<nb, SPI_THREADS, 0, st>>>(x, len, bsum);
 }
 
+template <typename T>
+static void spi_scatter(const int *kin, const int *lin, const void *vin, int *kout, int *lout, void *vout, long long nnz, int shift,
+                        const long long *goff, int nb, const void *win, const void *ain, void *wout, void *aout, hipStream_t st)
+{
+    if (win)
+        spi_scatter_kernel<T, true><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const T *)vin, kout, lout, (T *)vout, nnz, shift, goff, nb, (const T *)win,
+                                                                (const T *)ain, (T *)wout, (T *)aout);
+    else
+        spi_scatter_kernel<T, false><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const T *)vin, kout, lout, (T *)vout, nnz, shift, goff, nb, nullptr, nullptr,
+                                                                 nullptr, nullptr);
+}
+
 void nnlm_tu_spi_sort_pass(const int *kin, const int *lin, const void *vin, int *kout, int *lout, void *vout, bool f64, long long nnz, int shift,
-                           long long *ghist, long long *bsum, hipStream_t st)
+                           long long *ghist, long long *bsum, hipStream_t st, const void *win, const void *ain, void *wout, void *aout)
 {
     const int nb = (int)((nnz + SPI_SORT_TILE - 1) / SPI_SORT_TILE);
     spi_hist_kernel<<<nb, SPI_THREADS, 0, st>>>(kin, nnz, shift, ghist, nb);
     nnlm_tu_spi_scan(ghist, 256LL * nb, bsum, st);
-    if (f64) spi_scatter_kernel<double><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const double *)vin, kout, lout, (double *)vout, nnz, shift, ghist, nb);
-    else spi_scatter_kernel<float><<<nb, SPI_THREADS, 0, st>>>(kin, lin, (const float *)vin, kout, lout, (float *)vout, nnz, shift, ghist, nb);
+    if (f64) spi_scatter<double>(kin, lin, vin, kout, lout, vout, nnz, shift, ghist, nb, win, ain, wout, aout, st);
+    else spi_scatter<float>(kin, lin, vin, kout, lout, vout, nnz, shift, ghist, nb, win, ain, wout, aout, st);
+}
+
+void nnlm_tu_spi_pattern_ptr(const void *ptr, bool i64, const long long *ref, int lines, long long *blockmin, hipStream_t st)
+{
+    const int nb = (lines + SPI_THREADS) / SPI_THREADS; // lines + 1 pointers
+    if (i64) spi_pattern_ptr_kernel<long long><<<nb, SPI_THREADS, 0, st>>>((const long long *)ptr, ref, lines, blockmin);
+    else spi_pattern_ptr_kernel<int><<<nb, SPI_THREADS, 0, st>>>((const int *)ptr, ref, lines, blockmin);
+}
+
+void nnlm_tu_spi_pattern_idx(const void *idx, bool i64, const int *ref, long long nnz, long long *blockmin, hipStream_t st)
+{
+    const int nb = (int)((nnz + SPI_THREADS - 1) / SPI_THREADS);
+    if (i64) spi_pattern_idx_kernel<long long><<<nb, SPI_THREADS, 0, st>>>((const long long *)idx, ref, nnz, blockmin);
+    else spi_pattern_idx_kernel<int><<<nb, SPI_THREADS, 0, st>>>((const int *)idx, ref, nnz, blockmin);
+}
+
+void nnlm_tu_spi_wcheck(const void *val, int dtype, const void *wgt, int wdtype, bool f64, long long nnz, void *wt_out, void *wt_sort, void *wa_out,
+                        void *wa_sort, long long *blockcode, double *blockstat, hipStream_t st)
+{
+    const int nb = (int)((nnz + SPI_CHECK_SHARE - 1) / SPI_CHECK_SHARE);
+    spi_with_types(false, dtype, [&](auto, auto s) {
+        spi_with_types(false, wdtype, [&](auto, auto c) {
+            typedef decltype(s) S;
+            typedef decltype(c) Cw;
+            if (f64)
+                spi_wcheck_kernel<S, Cw, double><<<nb, SPI_THREADS, 0, st>>>((const S *)val, (const Cw *)wgt, nnz, (double *)wt_out, (double *)wt_sort,
+                                                                             (double *)wa_out, (double *)wa_sort, blockcode, blockstat);
+            else
+                spi_wcheck_kernel<S, Cw, float><<<nb, SPI_THREADS, 0, st>>>((const S *)val, (const Cw *)wgt, nnz, (float *)wt_out, (float *)wt_sort,
+                                                                            (float *)wa_out, (float *)wa_sort, blockcode, blockstat);
+        });
+    });
 }

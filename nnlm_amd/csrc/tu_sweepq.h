@@ -170,6 +170,15 @@ void nnlm_tu_spi_count(const int *idx, long long nnz, long long *cnt, hipStream_
 // x [len] -> its exclusive scan, in place; bsum: scratch of ceil(len / nnlm_spi_scan_tile()) elements
 void nnlm_tu_spi_scan(long long *x, long long len, long long *bsum, hipStream_t st);
 // One stable radix pass by (key >> shift) & 255 (kout == NULL: keys not written).  ghist: 256 ceil(nnz / nnlm_spi_sort_tile()) elements;
-// bsum: scratch of the scan of ghist
+// bsum: scratch of the scan of ghist.  win != NULL: the weights and the products c a (mode's type) go to wout / aout at the same positions
 void nnlm_tu_spi_sort_pass(const int *kin, const int *lin, const void *vin, int *kout, int *lout, void *vout, bool f64, long long nnz, int shift,
-                           long long *ghist, long long *bsum, hipStream_t st);
+                           long long *ghist, long long *bsum, hipStream_t st, const void *win = nullptr, const void *ain = nullptr,
+                           void *wout = nullptr, void *aout = nullptr);
+// Per-entry weights.  The weights' own pattern against the accepted resident one: blockmin [(lines + 256) / 256] =
+// the first line whose extent differs; blockmin [ceil(nnz / 256)] = the first entry whose index differs (nnz > 0)
+void nnlm_tu_spi_pattern_ptr(const void *ptr, bool i64, const long long *ref, int lines, long long *blockmin, hipStream_t st);
+void nnlm_tu_spi_pattern_idx(const void *idx, bool i64, const int *ref, long long nnz, long long *blockmin, hipStream_t st);
+// nnz > 0, on values the entry check has accepted.  wdtype: the weights' NNLM_DT_*; blockcode [nb] = first offending weight's entry,
+// blockstat [nb][3] = {entries beyond fp32 through c or c a, max |(float)(c a)|, the weighted KL sum}, nb as for nnlm_tu_spi_check
+void nnlm_tu_spi_wcheck(const void *val, int dtype, const void *wgt, int wdtype, bool f64, long long nnz, void *wt_out, void *wt_sort, void *wa_out,
+                        void *wa_sort, long long *blockcode, double *blockstat, hipStream_t st);
