@@ -298,6 +298,30 @@ int nnlm_predict_entries(nnlm_handle *h, long long count, const int *rows, const
  * by / exclude outside {0, 1}.  nnlm_profile_get names: "topn", "topn_merge" ("predict_entries" for the entry above);
  * nnlm_get_info "topn_slices": candidate slices of the last launch. */
 int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, long long n_lines, int exclude, int *idx_out, double *score_out);
+/* Ranking metrics of those lists against held-out entries, on the device: the lists of a round of lines are evaluated where
+ * nnlm_top_n's kernels leave them and are never copied to the host.  by, lines, n_lines and exclude mean what they mean for nnlm_top_n
+ * and carry its checks.  cutoffs: host int32[n_cut], 1 <= n_cut <= 8, strictly ascending values in 1 .. 128; n_top = the last one.
+ * held_ptr / held_idx: the held-out pattern on the host IN THE ORIENTATION OF by -- by = 0: a CSC, m + 1 int64 pointers and int32 row
+ * indices; by = 1: a CSR, n + 1 pointers and column indices -- indices strictly ascending inside a line and in range; a pattern without
+ * entries is legal (held_idx may then be NULL); entries of lines that are not listed are ignored.  The whole pattern is checked on the
+ * host before anything is uploaded (NNLM_ERR_ARG names the first offending line or entry); the entries of the listed lines are then
+ * uploaded once.  With exclude = 1 a held-out entry that the resident matrix STORES could never be listed: the call is refused with
+ * NNLM_ERR_ARG naming the first such entry in (position in lines, index) order, and nothing is evaluated.
+ * Per listed line l with held-out set T, t = |T|, and list L[0 .. n_top) exactly as nnlm_top_n returns it (padding -1 never hits), for
+ * a cutoff c:  hits_c = #{p < c : L[p] in T};  first = the smallest p with L[p] in T, or -1;  dcg_c = sum over hits p < c of d[p],
+ * d[p] = 1 / log2(p + 2) (a table computed once on the host in fp64);  apn_c = sum over hits p < c of hits_(p+1) / (p + 1); both sums in
+ * ascending p.  From them: precision = hits_c / c, recall = hits_c / t, hit rate = [hits_c > 0], NDCG = dcg_c / sum_{p < min(c, t)} d[p],
+ * AP = apn_c / min(c, t), RR = 1 / (first + 1) if 0 <= first < c, else 0.
+ * A line is EVALUATED iff it is listed and t > 0; *n_eval_out = their number.  agg_out: double[n_cut][6], the means over the evaluated
+ * lines of precision, recall, hit rate, NDCG, AP and RR (all NaN when no line is evaluated).  The sums are fp64 in a fixed order (a
+ * fixed-shape reduction per round of 16384 lines, then the rounds in order; no atomics on data): two calls give identical bits, and
+ * a line's values do not depend on which other lines were asked for.  line_out: NULL, or double[n_lines][2 + 3 n_cut]: t, first, then
+ * hits_c, dcg_c, apn_c per cutoff (the integers exactly); a listed line with t = 0 gets t = 0, first = -1 and zeros.
+ * NNLM_ERR_UNSUPPORTED: a cutoff above 128, and whatever nnlm_top_n refuses so.  NNLM_ERR_ARG: n_cut outside 1 .. 8, a cutoff below 1 or
+ * not ascending, and whatever nnlm_top_n refuses so.  nnlm_profile_get name: "topn_eval" (next to "topn", "topn_merge");
+ * nnlm_get_info "topn_eval_lines": the evaluated lines of the last call.  Synchronises. */
+int nnlm_top_n_eval(nnlm_handle *h, int by, const int *cutoffs, int n_cut, const int *lines, long long n_lines, int exclude,
+                    const long long *held_ptr, const int *held_idx, double *agg_out, long long *n_eval_out, double *line_out);
 
 /* Number of finite entries of A (N_non_missing, src/nnmf.cpp:51,69) and the any_missing flag.  Sparse A: n m and 0, and kl_const counts
  * the zeros ((n m - nnz) eps log eps); absent entries missing (nnlm_set_matrix_csc_missing): nnz and (nnz < n m). */

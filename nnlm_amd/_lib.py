@@ -39,7 +39,7 @@ EXPORTS = [
     "nnlm_set_factors_batch", "nnlm_get_factors_batch", "nnlm_run_batch", "nnlm_c_nnmf_batch",
     "nnlm_set_matrix_holdout", "nnlm_holdout_errors", "nnlm_c_nnmf_holdout_batch",
     "nnlm_set_matrix_device", "nnlm_set_factors_device", "nnlm_get_factors_device",
-    "nnlm_predict_entries", "nnlm_top_n",
+    "nnlm_predict_entries", "nnlm_top_n", "nnlm_top_n_eval",
     "nnlm_set_matrix_csc_batch", "nnlm_c_nnmf_csc_batch",
     "nnlm_set_matrix_csc_kl_batch", "nnlm_c_nnmf_csc_kl_batch",
     "nnlm_set_matrix_csc_missing_batch", "nnlm_c_nnmf_csc_missing_batch",
@@ -50,6 +50,7 @@ EXPORTS = [
 ]
 NNDSVD_VARIANTS = {"nndsvd": 0, "nndsvda": 1}
 TOPN_MAX = 128  # largest n_top of nnlm_top_n
+TOPN_EVAL_MAX_CUT = 8  # cutoffs per nnlm_top_n_eval call
 BY = {"column": 0, "row": 1}
 
 
@@ -257,6 +258,9 @@ def load():
     lib.nnlm_set_factors_nndsvd_batch.argtypes = [vp, C.c_uint, up, C.c_int]
     lib.nnlm_top_n.restype = C.c_int
     lib.nnlm_top_n.argtypes = [vp, C.c_int, C.c_int, ip, C.c_longlong, C.c_int, ip, dp]
+    lib.nnlm_top_n_eval.restype = C.c_int
+    lib.nnlm_top_n_eval.argtypes = [vp, C.c_int, ip, C.c_int, ip, C.c_longlong, C.c_int, C.POINTER(C.c_longlong), ip, dp,
+                                    C.POINTER(C.c_longlong), dp]
     _lib = lib
     return lib
 
@@ -1084,6 +1088,36 @@ class Handle:
         idx, score = np.full((L, width), -1, dtype=np.int32), np.full((L, width), np.nan)
         self._ck(self._lib.nnlm_top_n(self._h, code, n_top, _ip(ln), L, int(bool(exclude)), _ip(idx), _dp(score)))
         return idx, score
+
+    def top_n_eval(self, cutoffs, by="column", lines=None, exclude=False, held_ptr=None, held_idx=None, per_line=False):
+        """Ranking metrics of the top-n lists (n = the last cutoff) against held-out entries; the lists stay on the device.  held_ptr /
+        held_idx: the held-out pattern in the orientation of ``by`` (a CSC for "column", a CSR for "row").  Returns dict(cutoffs,
+        n_evaluated, precision, recall, hit_rate, ndcg, map, mrr: means over the lines with held-out entries, one value per cutoff)
+        and with per_line also n_heldout, first_hit (int64 [L]), hits (int64), dcg, apn (float64) [L, n_cut]."""
+        code = by_code(by)
+        cut = index_array(np.atleast_1d(np.asarray(cutoffs)), "cutoffs")
+        ln = None if lines is None else index_array(lines, "lines")
+        L = (self.m if code == 0 else self.n) if ln is None else ln.size
+        if held_ptr is None:
+            raise ValueError("held_ptr: the held-out pattern is required")
+        hp = np.ascontiguousarray(held_ptr, dtype=np.int64)
+        hi = index_array([] if held_idx is None else held_idx, "held_idx")
+        side = self.m if code == 0 else self.n
+        if hp.ndim != 1 or hp.size != side + 1 or (hp.size and hi.size < hp[-1]):
+            raise ValueError(f"held_ptr must hold {side + 1} pointers into held_idx (got {hp.shape} and {hi.size} indices)")
+        nc = min(cut.size, TOPN_EVAL_MAX_CUT)  # (more cutoffs are the library's refusal: nothing is written then)
+        agg, n_eval = np.full((nc, 6), np.nan), C.c_longlong(0)
+        rec = np.zeros((L, 2 + 3 * nc)) if per_line else None
+        self._ck(self._lib.nnlm_top_n_eval(self._h, code, _ip(cut), cut.size, _ip(ln), L, int(bool(exclude)),
+                                           _lp(hp), _ip(hi), _dp(agg), C.byref(n_eval), _dp(rec)))
+        out = dict(cutoffs=cut.copy(), n_evaluated=int(n_eval.value))
+        for s, name in enumerate(("precision", "recall", "hit_rate", "ndcg", "map", "mrr")):
+            out[name] = agg[:, s].copy()
+        if per_line:
+            body = rec[:, 2:].reshape(L, nc, 3)
+            out.update(n_heldout=rec[:, 0].astype(np.int64), first_hit=rec[:, 1].astype(np.int64), hits=body[:, :, 0].astype(np.int64),
+                       dcg=body[:, :, 1].copy(), apn=body[:, :, 2].copy())
+        return out
 
     def matrix_info(self):
         nn, am, kc = C.c_double(0), C.c_int(0), C.c_double(0)

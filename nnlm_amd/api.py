@@ -34,6 +34,7 @@ class NnlmStop(ValueError):
 # ------------------------------------------------------------------------------------------------
 CSC = namedtuple("CSC", "indptr indices data shape")
 CSC.__doc__ = "Canonical CSC of a sparse matrix: int64 indptr[m+1], int32 indices (sorted, unique within a column), fp64 data, (n, m)."
+CSC.tocsc = lambda self: self  # (a CSC is itself a sparse argument: what holdout_split returns goes into nnmf() and seen=)
 
 
 def is_sparse(A):
@@ -1550,3 +1551,107 @@ def top_n(fit, n_top, by="column", lines=None, seen=None):
         pattern = as_csc(seen)
     with _scoring_handle(W, H, pattern, None) as h:
         return h.top_n(n_top, by=by, lines=ln, exclude=pattern is not None)
+
+
+# ------------------------------------------------------------------------------------------------
+# ranking evaluation of the top-n lists against held-out entries (nnlm_top_n_eval)
+# ------------------------------------------------------------------------------------------------
+def _csc_transposed(c):
+    """The CSR of a canonical CSC as (pointers int64 [n + 1], column indices int32, ascending inside a row) and the permutation that
+    takes the CSC's entries there."""
+    n, m = c.shape
+    cols = np.repeat(np.arange(m, dtype=np.int64), np.diff(c.indptr))
+    order = np.argsort(np.asarray(c.indices, dtype=np.int64), kind="stable")  # (columns ascend inside a row: the sort is stable)
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(np.asarray(c.indices, dtype=np.int64), minlength=n), out=ptr[1:])
+    return ptr, cols[order].astype(np.int32), order
+
+
+def _cutoffs_arg(n_top):
+    try:
+        cut = _lib.index_array(np.atleast_1d(np.asarray(n_top)), "n_top")
+    except ValueError as e:
+        raise NnlmStop(str(e)) from None
+    if not 1 <= cut.size <= _lib.TOPN_EVAL_MAX_CUT:
+        raise NnlmStop("n_top must be one cutoff or 1 .. %d ascending cutoffs (got %d)." % (_lib.TOPN_EVAL_MAX_CUT, cut.size))
+    if cut.min() < 1 or cut.max() > _lib.TOPN_MAX:
+        raise NnlmStop("n_top must be in 1 .. %d (got %s)." % (_lib.TOPN_MAX, cut.tolist()))
+    if np.any(np.diff(cut) <= 0):
+        raise NnlmStop("n_top must hold strictly ascending cutoffs (got %s)." % (cut.tolist(),))
+    return cut
+
+
+def evaluate_top_n(fit, heldout, n_top=10, by="column", lines=None, seen=None, per_line=False):
+    """Precision, recall, hit rate, NDCG, MAP and MRR at n_top of the lists top_n(fit, n_top, by, lines, seen) would return, against the
+    entries of ``heldout`` -- computed on the device from the factors: neither W H nor the lists reach the host.  n_top: an int or up
+    to 8 strictly ascending cutoffs in 1 .. 128.  heldout / seen: objects with tocsc() of the shape of W H; only the stored PATTERN of
+    heldout is read, and it must not overlap seen (such an entry could never be listed).  A line is evaluated iff it is listed and holds
+    a held-out entry.  Returns dict(cutoffs, n_evaluated, precision, recall, hit_rate, ndcg, map, mrr) -- each metric a float64 array
+    over the cutoffs, the mean over the evaluated lines (NaN without any) -- and with per_line=True also lines, n_heldout, first_hit
+    (-1: none), hits, dcg and ap (the line's average precision; NaN on a line that is not evaluated), arrays over the listed lines."""
+    W, H = _fit_factors(fit, "evaluate_top_n")
+    n, m = W.shape[0], H.shape[1]
+    if by not in _lib.BY:
+        raise NnlmStop("by must be 'column' or 'row' (got %r)." % (by,))
+    cut = _cutoffs_arg(n_top)
+    side = m if by == "column" else n
+    ln = None if lines is None else _index_arg(lines, "lines", side)
+    patterns = {}
+    for name, x in (("heldout", heldout), ("seen", seen)):
+        if x is None and name == "seen":
+            continue
+        _refuse_device(x, "evaluate_top_n", name)
+        if not is_sparse(x):
+            raise NnlmStop("%s must be a sparse matrix (an object with tocsc()): its stored entries are what is %s." %
+                           (name, "held out" if name == "heldout" else "excluded"))
+        if tuple(int(v) for v in x.shape) != (n, m):
+            raise NnlmStop("Dimension of %s %s does not match the fit (%d x %d)." % (name, tuple(x.shape), n, m))
+        patterns[name] = as_csc(x)
+    held, pattern = patterns["heldout"], patterns.get("seen")
+    hp, hi = (held.indptr, held.indices) if by == "column" else _csc_transposed(held)[:2]
+    with _scoring_handle(W, H, pattern, None) as h:
+        try:
+            out = h.top_n_eval(cut, by=by, lines=ln, exclude=pattern is not None, held_ptr=hp, held_idx=hi, per_line=per_line)
+        except _lib.NnlmError as e:
+            if e.code == _lib.ERR_ARG and "is stored in the resident matrix" in str(e):
+                raise NnlmStop("heldout overlaps seen: %s" % (e,)) from None
+            raise
+    if per_line:
+        t = out["n_heldout"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["ap"] = out.pop("apn") / np.minimum(cut[None, :], t[:, None])
+        out["lines"] = np.arange(side, dtype=np.int32) if ln is None else ln.copy()
+    return out
+
+
+def holdout_split(A, per_line=1, by="column", min_keep=1, rng=None):
+    """Leave-some-out split of a sparse A for ranking evaluation, on the host: (train, heldout), two CSC with disjoint patterns whose union
+    is A's (values kept).  Every line (column for by = "column", row for "row") with more than min_keep stored entries gives up
+    min(per_line, stored - min_keep) of them, drawn without replacement from ``rng`` (a numpy Generator, a seed, or None); lines with at
+    most min_keep entries keep everything.  The same rng state gives the same split.  train is what one fits and passes as seen=."""
+    if not is_sparse(A):
+        raise NnlmStop("A must be a sparse matrix (an object with tocsc()).")
+    if by not in _lib.BY:
+        raise NnlmStop("by must be 'column' or 'row' (got %r)." % (by,))
+    per_line, min_keep = int(per_line), int(min_keep)
+    if per_line < 1 or min_keep < 0:
+        raise NnlmStop("per_line must be >= 1 and min_keep >= 0 (got %d and %d)." % (per_line, min_keep))
+    c = as_csc(A)
+    rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    if by == "column":
+        ptr, where = c.indptr, None
+    else:
+        ptr, _, where = _csc_transposed(c)  # (where: the CSC position of each entry in row order)
+    out = np.zeros(c.indices.size, dtype=bool)
+    counts = np.diff(ptr)
+    for l in np.flatnonzero(counts > min_keep):  # (lines in ascending order: the draws are a function of the rng state alone)
+        take = int(min(per_line, counts[l] - min_keep))
+        e = ptr[l] + rng.choice(int(counts[l]), size=take, replace=False)
+        out[e if where is None else where[e]] = True
+    cols = np.repeat(np.arange(c.shape[1], dtype=np.int64), np.diff(c.indptr))
+
+    def part(keep):
+        indptr = np.zeros(c.shape[1] + 1, dtype=np.int64)
+        np.cumsum(np.bincount(cols[keep], minlength=c.shape[1]), out=indptr[1:])
+        return CSC(indptr, np.ascontiguousarray(c.indices[keep]), np.ascontiguousarray(c.data[keep]), c.shape)
+    return part(~out), part(out)

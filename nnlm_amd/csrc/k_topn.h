@@ -241,3 +241,122 @@ __global__ __launch_bounds__(256) void topn_merge_kernel(const double *__restric
         }
     }
 }
+
+// ---------------------------------------------------------------------------------------------
+// Ranking metrics of the merged lists against held-out entries (nnlm_top_n_eval).  Nothing here computes a
+// score: the kernels read the index lists topn_merge_kernel left in device memory.
+//
+// topn_eval_kernel: one wavefront per line, four lines per workgroup, nothing shared between them and no barrier.  Lane p looks list
+// positions p and p + 64 up in the line's sorted held-out indices (a binary search each); two ballots give the 128 hit bits.  Lane c
+// then serves cutoff c alone: hits by popcount under the cutoff's mask, dcg and apn by walking its set bits from the lowest -- the
+// ascending-p order of the definitions, at most 128 fp64 additions each.  It writes the cutoff's three record values (when asked) and
+// its six derived values into the line's slot of the round's partial; a line without held-out entries writes zeros and is not counted.
+// topn_eval_reduce_kernel adds a column of the partial over the round's lines in a fixed shape and adds that to the call's sum: round
+// after round on one stream, so the order is fixed and two calls give the same bits.
+// ---------------------------------------------------------------------------------------------
+// is c among idx[lo .. hi) (ascending)?
+__device__ static inline bool topn_eval_held(const int *__restrict__ idx, long long lo, long long hi, int c)
+{
+    const long long end = hi;
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        if (idx[mid] < c) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && idx[lo] == c;
+}
+
+// the bits of `b` (list positions base .. base + 63) from the lowest: one more hit each
+__device__ static inline void topn_eval_walk(unsigned long long b, int base, const double *__restrict__ disc, int &h, double &dcg, double &apn)
+{
+    while (b) {
+        const int p = base + __builtin_ctzll(b);
+        b &= b - 1;
+        ++h;
+        dcg += disc[p];
+        apn += (double)h / (double)(p + 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void topn_eval_kernel(const TopnEvalArgs a)
+{
+    const int lane = threadIdx.x & 63, ll = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ll >= a.nlines) return; // (the whole wavefront)
+    const long long h0 = a.hptr[ll], h1 = a.hptr[ll + 1];
+    const int t = (int)(h1 - h0);
+    const int *L = a.idx + (size_t)ll * a.ntop;
+    const int c0 = lane < a.ntop ? L[lane] : -1, c1 = lane + 64 < a.ntop ? L[lane + 64] : -1; // (padding is -1 too: it never hits)
+    const unsigned long long b0 = __ballot(c0 >= 0 && topn_eval_held(a.hidx, h0, h1, c0));
+    const unsigned long long b1 = __ballot(c1 >= 0 && topn_eval_held(a.hidx, h0, h1, c1));
+    const int first = b0 ? __builtin_ctzll(b0) : (b1 ? 64 + __builtin_ctzll(b1) : -1);
+    const int rw = 2 + 3 * a.ncut;
+    if (lane == 0) {
+        a.part[(size_t)6 * a.ncut * a.pstride + ll] = t > 0 ? 1.0 : 0.0;
+        if (a.rec) a.rec[(size_t)ll * rw] = (double)t, a.rec[(size_t)ll * rw + 1] = (double)first;
+    }
+    if (lane >= a.ncut) return;
+    int C = 0;
+#pragma unroll
+    for (int q = 0; q < TOPN_EVAL_MAX_CUT; q++)
+        if (q == lane) C = a.cut[q]; // (constant indices: the argument block is never indexed by a register)
+    const unsigned long long m0 = C >= 64 ? b0 : b0 & ((1ull << C) - 1ull);
+    const unsigned long long m1 = C <= 64 ? 0ull : (C >= 128 ? b1 : b1 & ((1ull << (C - 64)) - 1ull));
+    const int hits = __popcll(m0) + __popcll(m1);
+    int h = 0;
+    double dcg = 0.0, apn = 0.0;
+    topn_eval_walk(m0, 0, a.disc, h, dcg, apn);
+    topn_eval_walk(m1, 64, a.disc, h, dcg, apn);
+    if (a.rec) {
+        double *r = a.rec + (size_t)ll * rw + 2 + 3 * lane;
+        r[0] = (double)hits, r[1] = dcg, r[2] = apn;
+    }
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (t > 0) {
+        const int best = min(C, t);
+        v[0] = (double)hits / (double)C;
+        v[1] = (double)hits / (double)t;
+        v[2] = hits > 0 ? 1.0 : 0.0;
+        v[3] = dcg / a.idcg[best];
+        v[4] = apn / (double)best;
+        v[5] = (first >= 0 && first < C) ? 1.0 / (double)(first + 1) : 0.0;
+    }
+#pragma unroll
+    for (int s = 0; s < 6; s++) a.part[(size_t)(6 * lane + s) * a.pstride + ll] = v[s];
+}
+
+// acc[blockIdx.x] += sum over l < nlines of part[blockIdx.x pstride + l]: thread sums over l = tid (mod 256), the wavefront's lanes, the
+// four wavefronts in order -- a shape that depends on nlines alone
+__global__ __launch_bounds__(256) void topn_eval_reduce_kernel(const double *__restrict__ part, int pstride, int nlines, double *__restrict__ acc)
+{
+    __shared__ double red[4];
+    const double *p = part + (size_t)blockIdx.x * pstride;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int b = threadIdx.x;
+    for (; b + 768 < nlines; b += 1024) s0 += p[b], s1 += p[b + 256], s2 += p[b + 512], s3 += p[b + 768];
+    for (; b < nlines; b += 256) s0 += p[b];
+    const double s = wave_sum((s0 + s1) + (s2 + s3));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) acc[blockIdx.x] = acc[blockIdx.x] + (((red[0] + red[1]) + red[2]) + red[3]);
+}
+
+// exclude = 1: a held-out entry that the resident matrix stores could never be listed.  One wavefront per listed line; a lane takes
+// every 64th held-out entry of the line and searches it among the line's stored indices; the entries ascend, so a lane's first find is
+// its smallest.  The smallest (list position, index) key of all wins: an integer minimum on one word, whatever the order of arrival.
+__global__ __launch_bounds__(256) void topn_eval_overlap_kernel(const int *__restrict__ lines, long long nlines, const long long *__restrict__ hptr,
+                                                                const int *__restrict__ hidx, const long long *__restrict__ xptr,
+                                                                const int *__restrict__ xidx, unsigned long long *first_key)
+{
+    const long long ll = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (ll >= nlines) return;
+    const int line = lines ? lines[ll] : (int)ll;
+    const long long x0 = xptr[line], x1 = xptr[line + 1], h1 = hptr[ll + 1];
+    if (x0 == x1) return;
+    for (long long e = hptr[ll] + (threadIdx.x & 63); e < h1; e += 64) {
+        const int c = hidx[e];
+        if (topn_eval_held(xidx, x0, x1, c)) {
+            atomicMin(first_key, ((unsigned long long)ll << 32) | (unsigned long long)(unsigned)c);
+            break;
+        }
+    }
+}

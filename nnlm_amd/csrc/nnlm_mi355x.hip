@@ -48,7 +48,7 @@
 static thread_local std::string g_last_error;
 
 enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, P_XPROD_W_ERR, P_ALLGATHER, P_ALLREDUCE, P_UNPACK, P_ERR_REDUCE,
-              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES,
+              P_SPMM_H, P_SPMM_W, P_SP_ERRORS, P_BATCH_ERRORS, P_BATCH_PEN, P_SP_GRAM, P_INGEST, P_TOPN, P_TOPN_MERGE, P_PREDICT_ENTRIES, P_TOPN_EVAL,
               P_SPKL_COPY, P_SPKL_H, P_SPKL_W, P_SP_BATCH_ERRORS, P_SPKL_BATCH_H, P_SPKL_BATCH_W,
               P_SP_INGEST, P_SP_INGEST_PTR, P_SP_INGEST_CHECK, P_SP_INGEST_BUILD, P_COUNT };
 // ("xprod_w_err": W half-step cross products that also evaluate the error sums -- the fused launches have a scope of their own;
@@ -62,7 +62,8 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  "batch_pen": its per-member penalty sums; "sp_gram": the per-column Grams of a sparse A whose absent entries are missing (sp_gram_kernel
 //  + its fix-up, both half-steps); "ingest": the ingest kernels of nnlm_set_matrix_device (k_ingest.h), without the common tail
 //  "topn" / "topn_merge" / "predict_entries": topn_kernel, topn_merge_kernel and predict_entries_kernel alone (k_topn.h; the row copies
-//  and the transfers around them are not in it)
+//  and the transfers around them are not in it); "topn_eval": the kernels of nnlm_top_n_eval behind them (topn_eval_kernel + its reduction
+//  per round, topn_eval_overlap_kernel once)
 //  "spkl_copy": the row copy and the column sums of the fixed factor of a KL half-step on a sparse A; "spkl_solve_h" / "spkl_solve_w": its
 //  solver launches (k_sparse_kl.h: starting states in the prologue, short and long form)
 //  "sp_batch_errors": the error block of a batched factorisation on a sparse A (k_sparse_batch.h: the row copies, the stacked Grams and
@@ -73,7 +74,7 @@ enum ProfId { P_XPROD_H = 0, P_XPROD_W, P_GRAM, P_SWEEP_H, P_SWEEP_W, P_ERRORS, 
 //  between the stages are inside it); "sp_ingest_ptr" / "sp_ingest_check" / "sp_ingest_build": the kernels of its stages alone -- the
 //  pointer check, the entry check with the conversions, the index histogram + its scan + the radix passes
 static const char *kProfNames[P_COUNT] = {"xprod_h", "xprod_w", "gram", "sweep_h", "sweep_w", "errors", "xprod_w_err", "allgather", "allreduce", "unpack", "err_reduce",
-                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries",
+                                          "spmm_h", "spmm_w", "sp_errors", "batch_errors", "batch_pen", "sp_gram", "ingest", "topn", "topn_merge", "predict_entries", "topn_eval",
                                           "spkl_copy", "spkl_solve_h", "spkl_solve_w", "sp_batch_errors", "spkl_batch_h", "spkl_batch_w",
                                           "sp_ingest", "sp_ingest_ptr", "sp_ingest_check", "sp_ingest_build"};
 
@@ -275,6 +276,7 @@ struct nnlm_handle {
     void *ho_val = nullptr;
 
     int topn_slices = 0; // candidate slices of the last topn_kernel launch (nnlm_get_info "topn_slices")
+    long long topn_eval_lines = 0; // evaluated lines of the last nnlm_top_n_eval (nnlm_get_info "topn_eval_lines")
 
     // truncated SVD of the resident matrix (nnlm_svd): the leading svd_l triplets, one row per triplet as the factor
     // masters keep their components; they live as long as the matrix.  svd_l = 0: none
@@ -4655,6 +4657,7 @@ extern "C" int nnlm_get_info(nnlm_handle *h, const char *key, double *value)
     else if (strcmp(key, "sp_gram_workers") == 0) *value = h->spg_workers;
     else if (strcmp(key, "sp_gram_batch_pairs") == 0) *value = h->bspg_pairs;
     else if (strcmp(key, "topn_slices") == 0) *value = h->topn_slices;
+    else if (strcmp(key, "topn_eval_lines") == 0) *value = (double)h->topn_eval_lines;
     else if (strcmp(key, "svd_width") == 0) *value = h->svd_l > 0 ? h->svd_l : -1;
     else if (strcmp(key, "svd_kept") == 0) *value = h->svd_l > 0 ? h->svd_kept : -1;
     else if (strcmp(key, "svd_ms_cross") == 0) *value = h->svd_ms[0];
@@ -5729,32 +5732,34 @@ static void topn_slicing(int ngroups, int ncand, int cus, int &nslices, int &sli
     nslices = (ncand + slice_len - 1) / slice_len;
 }
 
-extern "C" int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, long long n_lines, int exclude, int *idx_out, double *score_out)
+// by, exclude, n_top, lines and the out arrays of nnlm_top_n and nnlm_top_n_eval (`outs`: what must not be NULL there)
+static int topn_check_args(nnlm_handle *h, const char *who, int by, int n_top, const int *lines, long long n_lines, int exclude, bool have_outs,
+                           const char *outs)
 {
-    const char *who = "nnlm_top_n";
-    if (h) {
-        if (by != 0 && by != 1) return fail(h, NNLM_ERR_ARG, "%s: by = %d (0: per column, 1: per row)", who, by);
-        if (exclude != 0 && exclude != 1) return fail(h, NNLM_ERR_ARG, "%s: exclude = %d (0 or 1)", who, exclude);
-        if (n_top < 1) return fail(h, NNLM_ERR_ARG, "%s: n_top = %d (1 .. %d)", who, n_top, TOPN_MAX);
-        if (n_top > TOPN_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: n_top = %d, at most %d are selected", who, n_top, TOPN_MAX);
-        if (lines && n_lines < 0) return fail(h, NNLM_ERR_ARG, "%s: n_lines = %lld", who, n_lines);
-        if (!idx_out || !score_out) return fail(h, NNLM_ERR_ARG, "%s: idx_out and score_out must not be NULL", who);
-        if (exclude && has_matrix(h) && !h->sparse)
-            return fail(h, NNLM_ERR_UNSUPPORTED, "%s: exclude = 1 needs a sparse matrix on the handle (its stored entries are what is excluded)", who);
-        if (lines && has_matrix(h)) {
-            const int side = by == 0 ? h->m : h->n;
-            for (long long l = 0; l < n_lines; l++)
-                if (lines[l] < 0 || lines[l] >= side)
-                    return fail(h, NNLM_ERR_ARG, "%s: lines[%lld] = %d is out of range (%s = %d)", who, l, lines[l], by == 0 ? "m" : "n", side);
-        }
+    if (by != 0 && by != 1) return fail(h, NNLM_ERR_ARG, "%s: by = %d (0: per column, 1: per row)", who, by);
+    if (exclude != 0 && exclude != 1) return fail(h, NNLM_ERR_ARG, "%s: exclude = %d (0 or 1)", who, exclude);
+    if (n_top < 1) return fail(h, NNLM_ERR_ARG, "%s: n_top = %d (1 .. %d)", who, n_top, TOPN_MAX);
+    if (n_top > TOPN_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: n_top = %d, at most %d are selected", who, n_top, TOPN_MAX);
+    if (lines && n_lines < 0) return fail(h, NNLM_ERR_ARG, "%s: n_lines = %lld", who, n_lines);
+    if (!have_outs) return fail(h, NNLM_ERR_ARG, "%s: %s must not be NULL", who, outs);
+    if (exclude && has_matrix(h) && !h->sparse)
+        return fail(h, NNLM_ERR_UNSUPPORTED, "%s: exclude = 1 needs a sparse matrix on the handle (its stored entries are what is excluded)", who);
+    if (lines && has_matrix(h)) {
+        const int side = by == 0 ? h->m : h->n;
+        for (long long l = 0; l < n_lines; l++)
+            if (lines[l] < 0 || lines[l] >= side)
+                return fail(h, NNLM_ERR_ARG, "%s: lines[%lld] = %d is out of range (%s = %d)", who, l, lines[l], by == 0 ? "m" : "n", side);
     }
-    CallBufs bufs;
-    int K4 = 0;
-    double *Wrow = nullptr, *Hrow = nullptr;
-    if (const int rc = score_prepare(h, who, bufs, K4, Wrow, Hrow); rc != NNLM_OK) {
-        if (h && h->stream) (void)hipStreamSynchronize(h->stream);
-        return rc;
-    }
+    return NNLM_OK;
+}
+
+// The rounds of 16384 lines behind nnlm_top_n and nnlm_top_n_eval, after score_prepare: per round the lines go up, the candidates are
+// sliced, topn_kernel and topn_merge_kernel leave the round's lists in id / sd [nl][n_top] (device), round(l0, nl, id, sd) enqueues what
+// the entry does with them (a hipError_t), and the stream is drained before the next round reuses the buffers.
+template <typename Round>
+static int topn_rounds(nnlm_handle *h, const char *who, CallBufs &bufs, int K4, const double *Wrow, const double *Hrow, int by, int n_top,
+                       const int *lines, long long n_lines, int exclude, Round round)
+{
     hipStream_t st = h->stream;
     const long long L = lines ? n_lines : (by == 0 ? h->m : h->n);
     const int LCH = 16384; // lines per round (a multiple of the 64 lines of a full workgroup)
@@ -5806,12 +5811,172 @@ extern "C" int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, l
             nnlm_tu_topn_merge(a, id, sd, st);
         }
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(idx_out + (size_t)l0 * n_top, id, (size_t)nl * n_top * sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(score_out + (size_t)l0 * n_top, sd, (size_t)nl * n_top * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = round(l0, nl, (const int *)id, (const double *)sd);
         if (e == hipSuccess) e = hipStreamSynchronize(st); // (the round's buffers are reused)
     }
     if (e != hipSuccess) return score_fail(h, who, e);
+    return NNLM_OK;
+}
+
+extern "C" int nnlm_top_n(nnlm_handle *h, int by, int n_top, const int *lines, long long n_lines, int exclude, int *idx_out, double *score_out)
+{
+    const char *who = "nnlm_top_n";
+    if (h)
+        if (const int rc = topn_check_args(h, who, by, n_top, lines, n_lines, exclude, idx_out && score_out, "idx_out and score_out"); rc != NNLM_OK)
+            return rc;
+    CallBufs bufs;
+    int K4 = 0;
+    double *Wrow = nullptr, *Hrow = nullptr;
+    if (const int rc = score_prepare(h, who, bufs, K4, Wrow, Hrow); rc != NNLM_OK) {
+        if (h && h->stream) (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    hipStream_t st = h->stream;
+    const int rc = topn_rounds(h, who, bufs, K4, Wrow, Hrow, by, n_top, lines, n_lines, exclude, [&](long long l0, int nl, const int *id, const double *sd) {
+        hipError_t e = hipMemcpyAsync(idx_out + (size_t)l0 * n_top, id, (size_t)nl * n_top * sizeof(int), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(score_out + (size_t)l0 * n_top, sd, (size_t)nl * n_top * 8, hipMemcpyDeviceToHost, st);
+        return e;
+    });
+    if (rc != NNLM_OK) return rc;
     sync_all(h);
+    return NNLM_OK;
+}
+
+// Ranking metrics of the top-n lists against held-out entries (k_topn.h): the lists never leave the device
+extern "C" int nnlm_top_n_eval(nnlm_handle *h, int by, const int *cutoffs, int n_cut, const int *lines, long long n_lines, int exclude,
+                               const long long *held_ptr, const int *held_idx, double *agg_out, long long *n_eval_out, double *line_out)
+{
+    const char *who = "nnlm_top_n_eval";
+    int n_top = 1;
+    if (h) {
+        if (n_cut < 1 || n_cut > TOPN_EVAL_MAX_CUT) return fail(h, NNLM_ERR_ARG, "%s: n_cut = %d (1 .. %d cutoffs)", who, n_cut, TOPN_EVAL_MAX_CUT);
+        if (!cutoffs) return fail(h, NNLM_ERR_ARG, "%s: cutoffs must not be NULL", who);
+        for (int c = 0; c < n_cut; c++) {
+            if (cutoffs[c] < 1) return fail(h, NNLM_ERR_ARG, "%s: cutoffs[%d] = %d (1 .. %d)", who, c, cutoffs[c], TOPN_MAX);
+            if (cutoffs[c] > TOPN_MAX) return fail(h, NNLM_ERR_UNSUPPORTED, "%s: cutoffs[%d] = %d, at most %d are selected", who, c, cutoffs[c], TOPN_MAX);
+            if (c > 0 && cutoffs[c] <= cutoffs[c - 1])
+                return fail(h, NNLM_ERR_ARG, "%s: cutoffs[%d] = %d does not ascend (cutoffs[%d] = %d)", who, c, cutoffs[c], c - 1, cutoffs[c - 1]);
+        }
+        n_top = cutoffs[n_cut - 1];
+        if (const int rc = topn_check_args(h, who, by, n_top, lines, n_lines, exclude, agg_out && n_eval_out, "agg_out and n_eval_out"); rc != NNLM_OK)
+            return rc;
+        if (!held_ptr) return fail(h, NNLM_ERR_ARG, "%s: held_ptr must not be NULL", who);
+        if (has_matrix(h)) { // the pattern, in the orientation of `by`: canonical, as nnlm_set_matrix_csc checks a CSC
+            const int side = by == 0 ? h->m : h->n, ncand = by == 0 ? h->n : h->m;
+            const char *ln = by == 0 ? "column" : "row", *cn = by == 0 ? "row" : "column";
+            if (held_ptr[0] != 0) return fail(h, NNLM_ERR_ARG, "%s: held_ptr[0] = %lld, must be 0", who, held_ptr[0]);
+            for (int j = 0; j < side; j++)
+                if (held_ptr[j + 1] < held_ptr[j]) return fail(h, NNLM_ERR_ARG, "%s: held_ptr decreases at %s %d", who, ln, j);
+            if (held_ptr[side] > 0 && !held_idx) return fail(h, NNLM_ERR_ARG, "%s: held_idx is NULL with %lld held-out entries", who, held_ptr[side]);
+            for (int j = 0; j < side; j++)
+                for (long long e = held_ptr[j]; e < held_ptr[j + 1]; e++) {
+                    const int i = held_idx[e];
+                    if (i < 0 || i >= ncand)
+                        return fail(h, NNLM_ERR_ARG, "%s: held-out %s index %d out of range at entry %lld (%s %d)", who, cn, i, e, ln, j);
+                    if (e > held_ptr[j] && i <= held_idx[e - 1])
+                        return fail(h, NNLM_ERR_ARG, "%s: held-out %s indices of %s %d are not strictly increasing (entry %lld)", who, cn, ln, j, e);
+                }
+        }
+    }
+    CallBufs bufs;
+    int K4 = 0;
+    double *Wrow = nullptr, *Hrow = nullptr;
+    if (const int rc = score_prepare(h, who, bufs, K4, Wrow, Hrow); rc != NNLM_OK) {
+        if (h && h->stream) (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    hipStream_t st = h->stream;
+    const long long L = lines ? n_lines : (by == 0 ? h->m : h->n);
+    // the held-out entries of the listed lines by list position (all lines: the caller's arrays as they are)
+    std::vector<long long> hp;
+    std::vector<int> hi;
+    const long long *hp_host = held_ptr;
+    const int *hi_host = held_idx;
+    if (lines) {
+        hp.resize((size_t)L + 1);
+        hp[0] = 0;
+        for (long long l = 0; l < L; l++) hp[l + 1] = hp[l] + (held_ptr[lines[l] + 1] - held_ptr[lines[l]]);
+        hi.resize((size_t)hp[L]);
+        for (long long l = 0; l < L; l++)
+            if (hp[l + 1] > hp[l]) memcpy(hi.data() + hp[l], held_idx + held_ptr[lines[l]], (size_t)(hp[l + 1] - hp[l]) * sizeof(int));
+        hp_host = hp.data();
+        hi_host = hi.data();
+    }
+    const long long hn = hp_host[L];
+    long long n_eval = 0;
+    for (long long l = 0; l < L; l++) n_eval += hp_host[l + 1] > hp_host[l] ? 1 : 0;
+    double disc[TOPN_MAX], idcg[TOPN_MAX + 1];
+    idcg[0] = 0.0;
+    for (int p = 0; p < TOPN_MAX; p++) disc[p] = 1.0 / std::log2((double)p + 2.0), idcg[p + 1] = idcg[p] + disc[p];
+    const int LCH = 16384, nv = 6 * n_cut + 1, rw = 2 + 3 * n_cut;
+    const size_t chl = (size_t)(L < LCH ? L : LCH);
+    TopnEvalArgs ea{};
+    ea.ntop = n_top;
+    ea.ncut = n_cut;
+    for (int c = 0; c < n_cut; c++) ea.cut[c] = cutoffs[c];
+    ea.pstride = LCH;
+    long long *hpd = nullptr;
+    int *hid = nullptr, *lall = nullptr;
+    double *tab = nullptr, *acc = nullptr;
+    unsigned long long *key = nullptr;
+    hipError_t e = bufs.get(&hpd, (size_t)L + 1);
+    if (e == hipSuccess) e = bufs.get(&hid, (size_t)hn);
+    if (e == hipSuccess) e = bufs.get(&tab, (size_t)2 * TOPN_MAX + 1);
+    if (e == hipSuccess) e = bufs.get(&acc, (size_t)nv);
+    if (e == hipSuccess) e = bufs.get(&ea.part, (size_t)nv * LCH);
+    if (e == hipSuccess && line_out) e = bufs.get(&ea.rec, chl * rw);
+    if (e == hipSuccess) e = hipMemcpyAsync(hpd, hp_host, ((size_t)L + 1) * sizeof(long long), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && hn > 0) e = hipMemcpyAsync(hid, hi_host, (size_t)hn * sizeof(int), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tab, disc, sizeof(disc), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tab + TOPN_MAX, idcg, sizeof(idcg), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(acc, 0, (size_t)nv * 8, st);
+    ea.hidx = hid;
+    ea.disc = tab;
+    ea.idcg = tab + TOPN_MAX;
+    if (e == hipSuccess && exclude && hn > 0) { // a held-out entry the matrix stores is never a candidate: refuse the first one
+        unsigned long long none = ~0ull, got = ~0ull;
+        e = bufs.get(&key, 1);
+        if (e == hipSuccess && lines) e = bufs.get(&lall, (size_t)L);
+        if (e == hipSuccess && lines) e = hipMemcpyAsync(lall, lines, (size_t)L * sizeof(int), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(key, &none, sizeof(none), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            ProfScope ps(h, P_TOPN_EVAL);
+            nnlm_tu_topn_eval_overlap(lall, L, hpd, hid, by == 0 ? h->sp_cptr : h->sp_rptr, by == 0 ? h->sp_ridx : h->sp_cidx, key, st);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&got, key, sizeof(got), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e == hipSuccess && got != none) {
+            const long long l = (long long)(got >> 32);
+            const int c = (int)(got & 0xffffffffull), line = lines ? lines[l] : (int)l;
+            return fail(h, NNLM_ERR_ARG, "%s: the held-out entry (row %d, column %d) of lines[%lld] is stored in the resident matrix; with exclude = 1 "
+                        "it could never be listed", who, by == 0 ? c : line, by == 0 ? line : c, l);
+        }
+    }
+    if (e != hipSuccess) return score_fail(h, who, e);
+    const int rc = topn_rounds(h, who, bufs, K4, Wrow, Hrow, by, n_top, lines, n_lines, exclude, [&](long long l0, int nl, const int *id, const double *) {
+        ea.idx = id;
+        ea.nlines = nl;
+        ea.hptr = hpd + l0;
+        {
+            ProfScope ps(h, P_TOPN_EVAL);
+            nnlm_tu_topn_eval(ea, st);
+            nnlm_tu_topn_eval_reduce(ea, acc, st);
+        }
+        hipError_t e2 = hipGetLastError();
+        if (e2 == hipSuccess && line_out) e2 = hipMemcpyAsync(line_out + (size_t)l0 * rw, ea.rec, (size_t)nl * rw * 8, hipMemcpyDeviceToHost, st);
+        return e2;
+    });
+    if (rc != NNLM_OK) return rc;
+    double sums[6 * TOPN_EVAL_MAX_CUT + 1];
+    e = hipMemcpyAsync(sums, acc, (size_t)nv * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return score_fail(h, who, e);
+    sync_all(h);
+    if ((long long)sums[nv - 1] != n_eval) return fail(h, NNLM_ERR_HIP, "%s: %lld lines were evaluated on the device, %lld have held-out entries", who, (long long)sums[nv - 1], n_eval);
+    for (int v = 0; v < nv - 1; v++) agg_out[v] = n_eval > 0 ? sums[v] / (double)n_eval : std::nan("");
+    *n_eval_out = n_eval;
+    h->topn_eval_lines = n_eval;
     return NNLM_OK;
 }
 

@@ -32,3 +32,28 @@ void nnlm_tu_topn_merge(const TopnArgs &a, int *idx_out, double *score_out, hipS
 // out[e] = sum over q < k of Wrow[rows[e]][q] Hrow[cols[e]][q], q ascending; Wrow [n][K4], Hrow [m][K4]
 void nnlm_tu_predict_entries(const int *rows, const int *cols, long long count, const double *Wrow, const double *Hrow, int K4, int k, double *out,
                              hipStream_t st);
+
+// ---- ranking metrics of the merged lists against held-out entries (nnlm_top_n_eval) ----
+#define TOPN_EVAL_MAX_CUT 8 // cutoffs per call
+
+// One round: the merged index lists of `nlines` lines as topn_merge_kernel left them, and the held-out indices of those lines.
+struct TopnEvalArgs {
+    const int *idx;        // [nlines][ntop] merged lists, -1 behind a short one
+    int nlines, ntop, ncut;
+    int cut[TOPN_EVAL_MAX_CUT]; // ascending, cut[ncut - 1] = ntop
+    const long long *hptr; // [nlines + 1] the held-out indices of the round's line l are hidx[hptr[l] .. hptr[l + 1]), ascending
+    const int *hidx;
+    const double *disc;    // [TOPN_MAX] d[p] = 1 / log2(p + 2)
+    const double *idcg;    // [TOPN_MAX + 1] idcg[j] = d[0] + .. + d[j - 1], added in that order
+    double *rec;           // [nlines][2 + 3 ncut] per-line records (t, first, then hits, dcg, apn per cutoff), or nullptr
+    double *part;          // [6 ncut + 1][pstride] column major: value v of line l at part[v pstride + l]; workgroup w owns l = 4 w .. 4 w + 3.
+    int pstride;           //   v = 6 c + (precision, recall, hit rate, NDCG, AP, RR) of cutoff c; v = 6 ncut: 1 if the line is evaluated
+};
+// one wavefront per line, four per workgroup
+void nnlm_tu_topn_eval(const TopnEvalArgs &a, hipStream_t st);
+// acc[v] += the sum of column v of a.part over the round's lines, in a fixed order (one workgroup per column)
+void nnlm_tu_topn_eval_reduce(const TopnEvalArgs &a, double *acc, hipStream_t st);
+// *first_key = min over the held-out entries (list position l, index c) that are stored in the line's xidx range of (l << 32 | c); the
+// caller sets it to all ones.  lines: device [nlines] or nullptr = 0 .. nlines - 1; hptr / hidx: of all listed lines, by list position
+void nnlm_tu_topn_eval_overlap(const int *lines, long long nlines, const long long *hptr, const int *hidx, const long long *xptr, const int *xidx,
+                               unsigned long long *first_key, hipStream_t st);

@@ -46,3 +46,16 @@ void nnlm_tu_predict_entries(const int *rows, const int *cols, long long count, 
     const long long chunk = (count + nbx - 1) / nbx;
     predict_entries_kernel<<<(unsigned)nbx, 256, 0, st>>>(rows, cols, count, chunk, Wrow, Hrow, K4, k, out);
 }
+
+void nnlm_tu_topn_eval(const TopnEvalArgs &a, hipStream_t st) { topn_eval_kernel<<<(a.nlines + 3) / 4, 256, 0, st>>>(a); }
+
+void nnlm_tu_topn_eval_reduce(const TopnEvalArgs &a, double *acc, hipStream_t st)
+{
+    topn_eval_reduce_kernel<<<6 * a.ncut + 1, 256, 0, st>>>(a.part, a.pstride, a.nlines, acc);
+}
+
+void nnlm_tu_topn_eval_overlap(const int *lines, long long nlines, const long long *hptr, const int *hidx, const long long *xptr, const int *xidx,
+                               unsigned long long *first_key, hipStream_t st)
+{
+    if (nlines > 0) topn_eval_overlap_kernel<<<(unsigned)((nlines + 3) / 4), 256, 0, st>>>(lines, nlines, hptr, hidx, xptr, xidx, first_key);
+}
